@@ -1,7 +1,8 @@
 """bench.py -- frames/s of the PointPillars collaborative-perception hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config disco|car|ego|early|lately6] [--batch B] [--dist uniform|ring]
-                    [--no-pipeline] [--pipeline-replicas R] [--layer-table FILE] [--host-input] [--no-secondary]
+                    [--no-pipeline] [--pipeline-replicas R] [--host-input] [--dump-outputs DIR]
+                    [--full [--layer-table FILE] [--no-secondary] [--no-configs] [--no-cpu-baseline]]
 
 A "step" is one pass of the hot path (points resident in HBM -> final boxes) over one batch of B synthetic frames per GPU.
 Default workload = the one BASELINE.json's metric is quoted on ("60k-pt cloud, 6 agents"): v2x_pointpillar_disco.yaml, mid fusion of
@@ -12,17 +13,23 @@ Inference steps are software-pipelined by default (pcdet/models/pipelined.py, la
 queued before the box counts of step i are read on the host, the BEV-maker streams of step i+1 start at that step's points, and steps
 alternate between --pipeline-replicas (2) copies of the model on their own HIP streams.  All K steps AND their K host reads lie inside the
 timed region (the last read is flushed before the closing synchronize); every step's detections are bit-identical to the batch-by-batch
-ones (GPU tests).  --no-pipeline measures batch by batch: every step ends in its own host read.  --layer-table FILE writes the per-shape
-kernel table of the instrumented pass.  --host-input uploads the batch from pinned host memory every step (the PCIe-inclusive rate,
-informational); the default line also carries `secondary_ring`, the same command on the LiDAR-like cloud (--no-secondary skips it).
-Per-launch times of the roofline blocks are HIP-event brackets less what an empty event pair reads in this process (raw: *_uncorrected).
+ones (GPU tests).  --no-pipeline measures batch by batch: every step ends in its own host read.  --host-input uploads the batch from pinned
+host memory every step (the PCIe-inclusive rate, informational).
+
+A plain run sets up, warms up W steps, times K steps and prints the line; --dump-outputs DIR then also writes what the last timed step
+returned (the detections of every frame, or the loss and the updated parameters of a training step) as DIR/<name>.npy, float32 / float64.
+The inputs and weights are seeded, so two builds compare output for output.  --full adds everything else the line can carry: the
+instrumented pass (roofline, roofline_hbm, kernel_ms_per_step; --layer-table FILE writes its per-shape kernel table), the cpu_baseline
+sample, `secondary_ring` (the same command on the LiDAR-like cloud; --no-secondary skips it), `secondary_pipeline_graph` and the `configs`
+block (--no-configs skips it).  Per-launch times of the roofline blocks are HIP-event brackets less what an empty event pair reads in this
+process (raw: *_uncorrected).
 
 --gpus N > 1: bench.py starts N ranks ITSELF (a `python -m torch.distributed.run` child, spawned before this process touches the GPU)
 unless it already runs under a launcher (WORLD_SIZE set; it then insists on WORLD_SIZE == N).  One rank per GPU, backend nccl (= RCCL).
 Frames are independent, so ranks are replicas on different frames (weak scaling, no data-path collective); value = all ranks' frames /
 max-over-ranks time.  --shard agent / --train add the collectives those modes need.
 
-Rank 0 prints ONE JSON line with the contract keys plus
+Rank 0 prints ONE JSON line with the contract keys plus, with --full,
   roofline     : the kernel with the LARGEST measured share of the step (HIP events around every C-ABI launch of an instrumented pass),
                  `achieved` = the flops that kernel EXECUTES on the matrix pipe / its measured time (never above the peak); the
                  direct-convolution-equivalent ("algorithmic") rate is a separate key; `traffic` from the committed rocprofv3 --pmc pass
@@ -71,9 +78,9 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=0, help='frames per GPU per step (0 = BATCH_SIZE_PER_GPU of the YAML)')
     ap.add_argument('--dist', default='uniform', choices=['uniform', 'ring'], help='synthetic cloud distribution (SURVEY 8(d)): uniform in x, y '
                     '(about 53.6k pillars per 60k points) or the LiDAR-like ring (r = 70 u^2; 20-30k pillars)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the informational second measurement on the LiDAR-like cloud (--dist ring)')
-    ap.add_argument('--no-configs', action='store_true', help='skip the `configs` block (the default N = 1 disco line also times BASELINE configs 1 - 4 and '
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the cpu_baseline sample')
+    ap.add_argument('--no-secondary', action='store_true', help='--full: skip the informational second measurement on the LiDAR-like cloud (--dist ring)')
+    ap.add_argument('--no-configs', action='store_true', help='--full: skip the `configs` block (the --full N = 1 disco line also times BASELINE configs 1 - 4 and '
                     "config 5's bf16 training loop, each in a bounded child process)")
     ap.add_argument('--cpu-baseline-budget', type=float, default=25.0, help='seconds of host-core time the oracle may spend on the cpu_baseline sample')
     ap.add_argument('--dense-first-layer', action='store_true', help='A/B switch: always write the dense canvas and run the first backbone '
@@ -113,6 +120,12 @@ def parse_args(argv=None):
                     'where the config supports it')
     ap.add_argument('--train', action='store_true', help='configs ego / early / disco: time full training iterations (forward + backward + '
                     'clip + fused Adam one-cycle step; data parallel over ranks with one RCCL all-reduce of the flat gradient)')
+    ap.add_argument('--full', action='store_true', help='everything beside the headline: the instrumented pass (roofline, roofline_hbm, '
+                    'kernel_ms_per_step, decode_nms_us, --layer-table), the cpu_baseline sample, the secondary_ring / secondary_pipeline_graph '
+                    'child runs and the `configs` block.  Off by default: a plain run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step returned '
+                    '(per frame: pred_boxes / pred_scores / pred_labels ...; training: the loss and a seeded sample of the updated parameters) '
+                    'as DIR/<name>.npy in float32 / float64')
     return ap.parse_args(argv)
 
 
@@ -623,7 +636,7 @@ def run_config_children(steps, warmup, timeout_s=120):
     out = {}
     for name, extra, cpu_budget, note in CONFIG_CHILDREN:
         cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(min(steps, 20)), '--warmup', str(min(warmup, 5))] + extra + \
-              ['--no-secondary', '--no-configs'] + (['--cpu-baseline-budget', str(cpu_budget)] if cpu_budget > 0 else ['--no-cpu-baseline'])
+              ['--no-secondary', '--no-configs', '--full'] + (['--cpu-baseline-budget', str(cpu_budget)] if cpu_budget > 0 else ['--no-cpu-baseline'])
         t0 = time.time()
         try:
             res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s, check=False)
@@ -636,6 +649,40 @@ def run_config_children(steps, warmup, timeout_s=120):
         except Exception as e:                                         # the headline line must not depend on these extras
             out[name] = {'error': repr(e)[:300]}
     return out
+
+
+DUMP_PARAMS_MAX = 8 * 2 ** 20          # float32 elements of the parameter dump (32 MB); a larger model is sampled at fixed seeded indices
+
+
+def outputs_to_host(preds, train_state=None, model=None):
+    """what the caller of the timed path received from its last step, as {name: float32 / float64 numpy array}: per frame every tensor of
+    the detection dict (inference), or the loss and the updated trainable parameters (training).  Copied at once: the pipelined runners
+    hand out views of buffers that later steps overwrite."""
+    import numpy as np
+    import torch
+
+    def host(t):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        return a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+    out = {}
+    for b, p in enumerate(preds or []):
+        for k in sorted(p):
+            if isinstance(p[k], torch.Tensor):
+                out['frame%d_%s' % (b, k)] = host(p[k])
+    if train_state is not None:
+        out['loss'] = np.array([train_state['last_loss']], dtype=np.float64)
+        flat = torch.cat([q.detach().float().reshape(-1) for q in model.parameters() if q.requires_grad]).cpu().numpy()
+        if flat.size > DUMP_PARAMS_MAX:
+            flat = flat[np.sort(np.random.RandomState(0).choice(flat.size, DUMP_PARAMS_MAX, replace=False))]
+        out['params'] = flat
+    return out
+
+
+def write_outputs(out_dir, arrays, prefix=''):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + '.npy'), a)
 
 
 def dry_run(args, world, rank):
@@ -698,6 +745,8 @@ def dry_run(args, world, rank):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.layer_table and not args.full:
+        raise SystemExit('bench.py: --layer-table is written by the instrumented pass of --full')
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args, argv))            # nothing in this process has initialised the GPU
@@ -907,6 +956,8 @@ def main(argv=None):
             n_last = int(sum(p['pred_boxes'].shape[0] for p in preds))          # exact-shape tensors: the count was read on the host
             torch.cuda.synchronize()
             lat.append(1e3 * (time.perf_counter() - t1))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs_to_host(preds), 'rank%d_' % rank if world > 1 else '')
         lat = np.sort(np.array(lat))
         if rank == 0:
             print(json.dumps({'metric': 'latency per frame (60k-pt cloud, %d agent%s), B = %d' % (conf['agents_in_cloud'], 's' if conf['agents_in_cloud'] > 1 else '', batch),
@@ -965,6 +1016,8 @@ def main(argv=None):
         if backend == 'nccl' and (len(set(rank_pci)) != world if min(rank_pci) >= 0 else sorted(rank_devices) != list(range(world))):
             raise SystemExit('bench.py: ranks do not sit on distinct devices: ordinals %s, PCI %s' % (rank_devices, rank_pci))
     n_boxes = int(sum(p['pred_boxes'].shape[0] for p in preds))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, outputs_to_host(preds, train_state, model), 'rank%d_' % rank if world > 1 else '')
 
     # instrumented pass (HIP events around every C-ABI launch).  Training and agent-sharded steps contain collectives, so in those modes
     # every rank has to take part in the extra steps; only rank 0 records.
@@ -993,37 +1046,42 @@ def main(argv=None):
                 f.write('%6.1f  %-38s %s\n' % (n / 2.0, op, site))
 
     INSTR_STEPS = 3
-    timer = None
+    timer = fams = None
     was_pipelined = pipelined is not None or lately_pipe is not None
-    pipelined = None                            # the instrumented pass runs batch by batch
-    lately_pipe = None
-    if rank == 0:
-        graphed = None                          # the instrumented pass runs eagerly (events around individual launches)
-        if getattr(model, 'overlap_makers', False):
-            model.overlap_makers = False        # ... and on ONE stream: an event pair must not time other streams' kernels
-    if rank == 0 or ((args.train or args.shard == 'agent') and world > 1):
-        # one untimed step in the instrumented pass's own form first: the launch stream changes (the caller's stream instead of the
-        # replicas'), so per-stream scratch buffers are allocated on first use -- a first step read 176 us for the 41-us agent compaction
-        step()
-        torch.cuda.synchronize()
-    if rank == 0:
-        timer = AbiTimer()
-        timer.install()
-    if rank == 0 or ((args.train or args.shard == 'agent') and world > 1):
-        for _ in range(INSTR_STEPS):
+    if args.full or args.optin:
+        pipelined = None                        # the instrumented pass (and the --optin timings) run batch by batch
+        lately_pipe = None
+        if rank == 0:
+            graphed = None                      # the instrumented pass runs eagerly (events around individual launches)
+            if getattr(model, 'overlap_makers', False):
+                model.overlap_makers = False    # ... and on ONE stream: an event pair must not time other streams' kernels
+    if args.full:
+        if rank == 0 or ((args.train or args.shard == 'agent') and world > 1):
+            # one untimed step in the instrumented pass's own form first: the launch stream changes (the caller's stream instead of the
+            # replicas'), so per-stream scratch buffers are allocated on first use -- a first step read 176 us for the 41-us agent compaction
             step()
+            torch.cuda.synchronize()
+        if rank == 0:
+            timer = AbiTimer()
+            timer.install()
+        if rank == 0 or ((args.train or args.shard == 'agent') and world > 1):
+            for _ in range(INSTR_STEPS):
+                step()
+        if rank == 0:
+            fams = timer.families(INSTR_STEPS)
+            timer.remove()
+            if args.layer_table:
+                with open(args.layer_table, 'w') as f:
+                    f.write('%-28s %-44s %9s %10s %9s %9s\n' % ('kernel', 'shape', 'per step', 'us/launch', 'exec TF', 'ms/step'))
+                    for (lab, shape), (ms, n, ex, alg) in sorted(timer.layers.items(), key=lambda kv: -kv[1][0]):
+                        f.write('%-28s %-44s %9.2f %10.1f %9.1f %9.3f\n' % (lab, shape, n / INSTR_STEPS, ms / n * 1e3, ex / ms / 1e9 if ms else 0.0,
+                                                                         ms / INSTR_STEPS))
     if rank == 0:
-        fams = timer.families(INSTR_STEPS)
-        timer.remove()
-        if args.layer_table and rank == 0:
-            with open(args.layer_table, 'w') as f:
-                f.write('%-28s %-44s %9s %10s %9s %9s\n' % ('kernel', 'shape', 'per step', 'us/launch', 'exec TF', 'ms/step'))
-                for (lab, shape), (ms, n, ex, alg) in sorted(timer.layers.items(), key=lambda kv: -kv[1][0]):
-                    f.write('%-28s %-44s %9.2f %10.1f %9.1f %9.3f\n' % (lab, shape, n / INSTR_STEPS, ms / n * 1e3, ex / ms / 1e9 if ms else 0.0,
-                                                                     ms / INSTR_STEPS))
-        dom = fams[0]
         frames = (world if args.shard == 'frame' else 1) * batch * args.steps
         algo = os.environ.get('PCP_CONV_ALGO', 'auto')
+        full_keys = {}
+    if rank == 0 and args.full:
+        dom = fams[0]
         if dom['bound'] == 'mfma' and dom['ms'] > 0:
             ach = dom['exec_flops'] / (dom['ms'] * 1e-3) / 1e12
             roof = {'bound': 'mfma', 'kernel': dom['kernel'], 'achieved': round(ach, 3), 'peak': dom['peak'], 'unit': 'TFLOP/s',
@@ -1073,6 +1131,14 @@ def main(argv=None):
                                 '(roofline.event_bracket_overhead_us); *_uncorrected keep the raw brackets'}
         decode_nms_us = round(1e3 * sum(f['ms_per_step'] for f in fams if f['kernel'].split(' ')[0] in
                                         ('pcp_centerhead_decode', 'pcp_nms_rotated', 'pcp_nms_normal', 'pcp_gather_detections', 'pcp_anchor_decode', 'pcp_topk_boxes')), 1)
+        full_keys = {
+            'roofline': roof,
+            'roofline_hbm': vfe_roof,
+            'decode_nms_us': decode_nms_us,
+            'kernel_ms_per_step': {f['kernel'].split(' ')[0]: round(f['ms_per_step'], 4) for f in fams[:14]},
+            'kernel_ms_per_step_total': round(sum(f['ms_per_step'] for f in fams), 3),
+        }
+    if rank == 0:
         line = {
             'metric': ('frames/sec (60k-pt cloud, 6 agents)' if conf['agents_in_cloud'] == 6 else 'frames/sec (60k-pt cloud, 1 agent)') +
                       (' [dead BEV-maker passes elided: NOT the headline]' if args.elide_dead_makers else ''),
@@ -1114,12 +1180,8 @@ def main(argv=None):
                        'peak_device_memory_mb': round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1),
                        **({'elided': 'rsu BEV maker (overwritten by the car maker) and early BEV maker (training-only output): reference quirk F3'} if args.elide_dead_makers else {}),
                        'final_boxes_last_step': n_boxes, **({'loss_last_step': train_state['last_loss']} if args.train else {})},
-            'roofline': roof,
-            'roofline_hbm': vfe_roof,
-            'decode_nms_us': decode_nms_us,
             'pipelined_replicas': (max(1, args.pipeline_replicas) if was_pipelined else 0),
-            'kernel_ms_per_step': {f['kernel'].split(' ')[0]: round(f['ms_per_step'], 4) for f in fams[:14]},
-            'kernel_ms_per_step_total': round(sum(f['ms_per_step'] for f in fams), 3),
+            **full_keys,
         }
         if world > 1 and backend != 'nccl':
             line['data'] += ' -- FUNCTIONAL CHECK ONLY: backend %s, %d ranks on %d device(s)' % (backend, world, n_dev)
@@ -1172,20 +1234,20 @@ def main(argv=None):
                                          'final_boxes_matching_fp32_within_1e-3': '%d of %d' % (matched, total),
                                          'note': 'NOT the headline, batch by batch on one stream: ' + note + '; enable with PCP_CONV_ALGO=' + mode}
             set_algo('auto')
-        if not args.no_cpu_baseline and world == 1:                    # rank 0 at N = 1 only (the contract); N > 1 lines carry null
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (the contract); N > 1 lines carry null
             if args.config == 'lately6':
                 line['cpu_baseline'] = cpu_baseline_lately(car_cfg, car_state, cfg, state, lately_frames[0], budget_s=args.cpu_baseline_budget)
             else:
                 line['cpu_baseline'] = cpu_baseline(conf, cfg, state, pts_np, metas, budget_s=args.cpu_baseline_budget)
         else:
             line['cpu_baseline'] = None
-        if (world == 1 and args.dist == 'uniform' and not args.no_secondary and not args.train and not args.graph and not args.latency
+        if (args.full and world == 1 and args.dist == 'uniform' and not args.no_secondary and not args.train and not args.graph and not args.latency
                 and args.shard == 'frame' and algo == 'auto' and not args.plugin_default):
             # the LiDAR-like cloud ("ring") is reported alongside -- the same command on it, in a child process (this one keeps its
             # pipeline state); informational, never part of `value`
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), '--config', args.config, '--dist', 'ring', '--steps', str(min(args.steps, 20)),
-                   '--warmup', str(min(args.warmup, 5)), '--no-cpu-baseline', '--no-secondary']
+                   '--warmup', str(min(args.warmup, 5)), '--no-cpu-baseline', '--no-secondary', '--full']
             try:
                 res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300, check=False)
                 rl = [ln for ln in res.stdout.decode().splitlines() if ln.startswith('{')]
@@ -1211,7 +1273,7 @@ def main(argv=None):
                 'vfe_stage_ms_per_step': (r.get('roofline_hbm') or {}).get('ms_per_step'),
                 'note': 'the same command with --dist ring (r = 70 u^2: 48 % of the points in multi-point pillars, ~850 in the cell under the '
                         'sensor); NOT the headline'}
-        if (world == 1 and args.config == 'disco' and args.dist == 'uniform' and not args.no_configs and not args.train and not args.graph
+        if (args.full and world == 1 and args.config == 'disco' and args.dist == 'uniform' and not args.no_configs and not args.train and not args.graph
                 and not args.latency and args.shard == 'frame' and algo == 'auto' and not args.plugin_default and not args.elide_dead_makers
                 and not args.host_input and not args.no_pipeline):
             # every BASELINE.json workload in the one line the driver records: this run's headline (config 5 inference) + bounded child runs

@@ -2052,9 +2052,40 @@ def g17_bench_b4(dist='uniform'):
         WEIGHT_SCHEME = 'survey'
 
 
+def g19_ref_cpu_functions():
+    """tests/golden/g19_ref_cpu_functions.npz: the reference's compiled CPU functions (oracle/_ref, built by oracle/build_ref.py) run on
+    seeded inputs, inputs and results both stored, so the pins of tests/test_oracle_pins.py hold where oracle/_ref cannot be built:
+    boxes_iou_bev_cpu on 300 boxes (the 300 x 300 matrix as its SHA-256) and points_in_boxes_cpu on 60 boxes / 5060 points (the
+    first-true box index per point of its mask)"""
+    sys.path.insert(0, REPO)
+    from oracle import build_ref
+    ref = build_ref.load_ref()
+    n, s = 300, 777
+    b = np.zeros((n, 7), np.float32)
+    b[:, 0] = synth.uniform(s, 1, n, -10, 10)
+    b[:, 1] = synth.uniform(s, 2, n, -10, 10)
+    b[:, 3] = synth.uniform(s, 3, n, 0.5, 6)
+    b[:, 4] = synth.uniform(s, 4, n, 0.5, 3)
+    b[:, 5] = 1.5
+    b[:, 6] = synth.uniform(s, 5, n, -6.3, 6.3)
+    iou = torch.zeros(n, n)
+    ref.boxes_iou_bev_cpu(torch.from_numpy(b), torch.from_numpy(b), iou)
+    rs = np.random.RandomState(17)
+    b2 = np.concatenate([rs.uniform(-20, 20, (60, 2)), rs.uniform(-3, 0, (60, 1)), rs.uniform(0.5, 6, (60, 3)), rs.uniform(-7, 7, (60, 1))], 1).astype(np.float32)
+    b2[7, 3:6] = 0
+    p2 = np.concatenate([b2[rs.randint(0, 60, 5000), :3] + rs.uniform(-3.2, 3.2, (5000, 3)), b2[:60, :3]], 0).astype(np.float32)
+    m2 = build_ref.ref_points_in_boxes_cpu(p2, b2)
+    np.savez_compressed(os.path.join(HERE, 'g19_ref_cpu_functions.npz'), iou_boxes=b,
+                        iou_sha=np.array(hashlib.sha256(np.ascontiguousarray(iou.numpy()).tobytes()).hexdigest()),
+                        pib_boxes=b2, pib_points=p2, pib_box_idx=np.where(m2.any(0), m2.argmax(0), -1).astype(np.int32),
+                        pib_mask_sum=np.array(int(m2.sum())))
+
+
 if __name__ == '__main__':
     todo = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4']
     torch.set_num_threads(8)
+    if 'g19' in todo:
+        g19_ref_cpu_functions()
     if 'g17r' in todo:
         g17_ring_full()
     if 'g17b' in todo:

@@ -392,8 +392,8 @@ def test_bench_pipelined_default_and_batch_by_batch_agree(tmp_path):
     """bench.py's default inference mode queues step i+1 before it reads step i's box counts (pcdet/models/pipelined.py); --no-pipeline runs
     batch by batch.  Same workload, same final boxes; the line says which mode it measured; --layer-table writes the per-shape kernel table."""
     table = tmp_path / 'layers.txt'
-    piped = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--layer-table', str(table)])
-    plain = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-pipeline'])
+    piped = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--full', '--layer-table', str(table)])
+    plain = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--full', '--no-pipeline'])
     assert 'software-pipelined' in piped['config']['mode'] and 'software-pipelined' not in plain['config']['mode']
     assert piped['config']['final_boxes_last_step'] == plain['config']['final_boxes_last_step'] > 0
     assert piped['roofline']['kernel'] == plain['roofline']['kernel'] and piped['roofline']['next_mfma_kernels']
@@ -406,6 +406,35 @@ def test_bench_pipelined_default_and_batch_by_batch_agree(tmp_path):
         assert h['ms_per_step'] < h['ms_per_step_uncorrected']
     rows = table.read_text().splitlines()
     assert rows[0].split()[:2] == ['kernel', 'shape'] and any(r.startswith('k_wino4c') for r in rows[1:])
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline keys and none of the --full extras; --dump-outputs writes the detections of the last
+    timed step, one float32 file per frame and key, as many boxes as the line counts.  The pipelined default and the batch-by-batch run
+    dump the same detections (seeded inputs and weights)."""
+    _setup_paths()
+    from helpers import assert_same_final_set
+    piped_dir, plain_dir = tmp_path / 'piped', tmp_path / 'plain'
+    piped = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(piped_dir)])
+    plain = _bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--no-pipeline', '--dump-outputs', str(plain_dir)])
+    for line in (piped, plain):
+        assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line)
+        assert line['steps'] == 3 and line['value'] > 0 and line['ms_per_step'] > 0 and line['cpu_baseline'] is None
+        assert not {'roofline', 'roofline_hbm', 'kernel_ms_per_step', 'secondary_ring', 'secondary_pipeline_graph', 'configs'} & set(line)
+    frames = piped['config']['frames_per_gpu_per_step']
+    assert sorted(os.listdir(piped_dir)) == sorted(os.listdir(plain_dir)) == sorted(
+        'frame%d_%s.npy' % (f, k) for f in range(frames) for k in ('pred_boxes', 'pred_scores', 'pred_labels'))
+    n = 0
+    for f in range(frames):
+        got = {d: {k: np.load(os.path.join(d, 'frame%d_%s.npy' % (f, k))) for k in ('pred_boxes', 'pred_scores', 'pred_labels')}
+               for d in (piped_dir, plain_dir)}
+        a, b = got[piped_dir], got[plain_dir]
+        assert a['pred_boxes'].dtype == np.float32 and a['pred_boxes'].shape == (a['pred_scores'].shape[0], 7)
+        assert a['pred_labels'].dtype == np.float64 and a['pred_labels'].shape == a['pred_scores'].shape
+        assert_same_final_set(a['pred_boxes'], a['pred_scores'], b['pred_boxes'], b['pred_scores'])
+        assert np.array_equal(np.sort(a['pred_labels']), np.sort(b['pred_labels']))
+        n += a['pred_boxes'].shape[0]
+    assert n == piped['config']['final_boxes_last_step'] == plain['config']['final_boxes_last_step'] > 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

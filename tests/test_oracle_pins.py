@@ -148,9 +148,15 @@ def test_g15_multi_classes_nms():
 
 
 def test_ref_build_matches_oracle_when_present():
+    """the oracle's rotated BEV IoU is bit-equal to the reference's compiled boxes_iou_bev_cpu on 300 seeded boxes: against the digest of
+    its matrix in tests/golden/g19_ref_cpu_functions.npz always, and against the live function where oracle/_ref is built"""
+    import hashlib
+    g = load_golden('g19_ref_cpu_functions.npz')
+    mine = onms.iou_matrix(g['iou_boxes'], g['iou_boxes'])
+    assert hashlib.sha256(np.ascontiguousarray(mine, dtype=np.float32).tobytes()).hexdigest() == str(g['iou_sha'])
     so = os.path.join(os.path.dirname(onms.__file__), '_ref', 'ref_iou3d_cpu.so')
     if not os.path.isfile(so):
-        pytest.skip('oracle/_ref not built (reference absent)')
+        return                                                    # the fixture half of the pin ran; the live half needs oracle/_ref
     from oracle import build_ref
     ref = build_ref.load_ref()
     n = 300
@@ -162,6 +168,7 @@ def test_ref_build_matches_oracle_when_present():
     b[:, 4] = synth.uniform(s, 4, n, 0.5, 3)
     b[:, 5] = 1.5
     b[:, 6] = synth.uniform(s, 5, n, -6.3, 6.3)
+    assert np.array_equal(b, g['iou_boxes'])
     out = torch.zeros(n, n)
     ref.boxes_iou_bev_cpu(torch.from_numpy(b), torch.from_numpy(b), out)
     mine = onms.iou_matrix(b, b)
@@ -273,6 +280,10 @@ def test_points_in_boxes_pinned_on_the_references_compiled_cpu_function():
     band = g['box_idx_margin_band']
     assert np.array_equal(gpu[~band], g['box_idx_ref_cpu'][~band]) and 0 < int(band.sum()) < 20
     assert np.array_equal(gpu, g['box_idx'])
+    # fresh seeded geometry, larger than the fixture (every heading quadrant, a zero-size box, points on box centres): the reference's
+    # first-true index per point, recorded in tests/golden/g19_ref_cpu_functions.npz
+    r = load_golden('g19_ref_cpu_functions.npz')
+    assert np.array_equal(oex.points_in_boxes(r['pib_points'], r['pib_boxes'], margin=1e-2), r['pib_box_idx']) and int(r['pib_mask_sum']) > 500
     so = os.path.join(os.path.dirname(oex.__file__), '_ref', 'ref_roiaware_pool3d.so')
     if not os.path.isfile(so) and not os.path.isdir('/root/reference'):
         return                                                    # the fixture half of the pin ran; the live half needs oracle/_ref
@@ -285,6 +296,7 @@ def test_points_in_boxes_pinned_on_the_references_compiled_cpu_function():
     b2 = np.concatenate([rs.uniform(-20, 20, (60, 2)), rs.uniform(-3, 0, (60, 1)), rs.uniform(0.5, 6, (60, 3)), rs.uniform(-7, 7, (60, 1))], 1).astype(np.float32)
     b2[7, 3:6] = 0
     p2 = np.concatenate([b2[rs.randint(0, 60, 5000), :3] + rs.uniform(-3.2, 3.2, (5000, 3)), b2[:60, :3]], 0).astype(np.float32)
+    assert np.array_equal(b2, r['pib_boxes']) and np.array_equal(p2, r['pib_points'])
     m2 = build_ref.ref_points_in_boxes_cpu(p2, b2)
     assert np.array_equal(np.where(m2.any(0), m2.argmax(0), -1).astype(np.int32), oex.points_in_boxes(p2, b2, margin=1e-2))
     assert int(m2.sum()) > 500
