@@ -560,6 +560,58 @@ int pcp_anchor_decode(const pcp_anchor_t *desc, const float *head, const float *
 int pcp_topk_boxes(const uint32_t *score_keys, const int32_t *labels, const float *boxes, int32_t batch, int64_t n, int32_t k,
                    float *out_boxes, float *out_scores, int32_t *out_labels, int32_t *out_index, int32_t *count, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * SC backbone (SCConvBackbone2dStride4 / Stride1, the nuScenes PointPillar-Jr models).
+ * Replaces workspace/sc_conv.py:14-44 (SCConv.forward: AvgPool2d(4, 4), F.interpolate nearest, sigmoid, mul); the 3x3 convs
+ * around it run on pcp_conv3x3 and friends, the bottleneck's residual on pcp_pointwise with relu = PCP_RELU_PRE_RESIDUAL.
+ * All maps NHWC float32; every pointer below is the first channel of a channel window (base + channel offset), ld the pixel
+ * stride of its buffer.  Channel counts, offsets and ld are multiples of 4 and pointers 16-byte aligned (16-byte accesses).
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* pcp_pointwise relu value: PLAIN only, residual required -- out = relu(x W^T + b + residual) (the residual added BEFORE the
+ * activation, SCBottleneck.forward).  relu = 0 / 1 keep their meaning (1: residual added after the activation). */
+#define PCP_RELU_PRE_RESIDUAL 2
+
+/* nn.AvgPool2d(r, r) without padding: out (B, in_h / r, in_w / r) (floor sizes), sum of the r x r window in row-major order
+ * divided by r * r.  r in [1, 8]. */
+int pcp_avgpool_nhwc(const float *in, int32_t batch, int32_t in_h, int32_t in_w, int32_t c, int32_t ld_in, int32_t r, float *out,
+                     int32_t ld_out, void *stream);
+
+/* SC gate: out = t * sigmoid(x + up(s)), up = F.interpolate(s, size=(h, w)) with torch's nearest rule per axis
+ * (in == out: identity; out == 2 * in: i >> 1; else min(floor(i * (float)in / out), in - 1)).
+ * t, x, out: (B, h, w, ld_*) windows of c channels; s: (B, sh, sw, ld_s).  out may equal t (in place). */
+int pcp_sc_gate(const float *t, int32_t ld_t, const float *x, int32_t ld_x, const float *s, int32_t ld_s, int32_t sh, int32_t sw,
+                float *out, int32_t ld_out, int32_t batch, int32_t h, int32_t w, int32_t c, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * CenterHead decode with velocity / IoU calibration, all heads of a batch in ONE launch (grid = heads x frames).
+ * Replaces center_head.py:302-333 + centernet_utils.py:150-214 for heads with a `vel` branch (pred_boxes (n, 9)) and for
+ * POST_PROCESSING.CALIB_CLS_SCORE (score = sigmoid(hm)^(1 - alpha) * clamp((iou + 1) / 2, 0, 1)^alpha before the top-K).
+ * Same top-K semantics as pcp_centerhead_decode (ties to the lower flat (class, cell) index); up to 32768 (class, cell)
+ * candidates per frame and head.  Velocity goes out as a separate (B, k, 2) array so the 7-wide boxes feed
+ * pcp_nms_rotated unchanged.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  pcp_decode_t d;                 /* geometry / channels / K / thresholds of this head; num_class * h * w <= 32768 */
+  const float *head;              /* (B, h, w, d.ld) NHWC */
+  int32_t ch_vel;                 /* vel (2 channels) offset, -1 = no vel output */
+  int32_t ch_iou;                 /* iou (1 channel) offset, -1 = no score calibration */
+  float iou_alpha;                /* CALIB_CLS_SCORE_ALPHA (0.5: the powers are square roots) */
+  float *boxes, *scores;          /* (B, k, 7), (B, k) */
+  int32_t *labels, *cell;         /* (B, k), may be NULL */
+  int32_t *count;                 /* (B,) */
+  float *vel;                     /* (B, k, 2); required when ch_vel >= 0 */
+} pcp_decode_head_t;
+int pcp_centerhead_decode_ext(const pcp_decode_head_t *heads, int32_t n_heads, void *stream);
+
+/* pcp_gather_detections with velocity: out_boxes (B, out_max, 9) = [box(7) | vel(2)] of each head's kept candidates in keep order
+ * (vel NULL: zeros); the other outputs as pcp_gather_detections. */
+typedef struct {
+  pcp_det_head_t h;
+  const float *vel;               /* (B, h.k, 2) or NULL */
+} pcp_det_head_ext_t;
+int pcp_gather_detections_ext(const pcp_det_head_ext_t *heads, int32_t n_heads, int32_t batch, int32_t out_max, float *out_boxes,
+                              float *out_scores, int64_t *out_labels, int32_t *out_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_pointwise(PwParams p) {
         if (co >= p.cout) continue;
         const f32x4 bias = *reinterpret_cast<const f32x4 *>(p.bias + co);          // bias is padded to cout_pad
         f32x4 v = f32x4{acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]} + bias;
-        if (p.relu) {
+        if (p.relu && p.relu != PCP_RELU_PRE_RESIDUAL) {
           v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         }
         if (MODE == PCP_PW_PLAIN && p.residual) {
@@ -410,6 +410,9 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_pointwise(PwParams p) {
           if (co + 1 < p.cout) v.y += rr[1];
           if (co + 2 < p.cout) v.z += rr[2];
           if (co + 3 < p.cout) v.w += rr[3];
+        }
+        if (MODE == PCP_PW_PLAIN && p.relu == PCP_RELU_PRE_RESIDUAL) {       // SCBottleneck: relu(bn3(conv3(.)) + residual)
+          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         }
         if (co + 3 < p.cout && p.vec_out) {
           *reinterpret_cast<f32x4 *>(orow + co) = v;
@@ -491,6 +494,8 @@ extern "C" int pcp_pointwise(const pcp_pointwise_t *d, const float *in, const fl
     if (p.in2 && (p.k_split <= 0 || p.k_split % CK != 0 || p.k_split >= d->cin || (p.ld_in2 & 3) || (((uintptr_t)p.in2) & 15)))
       return PCP_ERR_ARG;
   }
+  // relu: 0 none, 1 relu (residual, if any, added after it), PCP_RELU_PRE_RESIDUAL relu(. + residual) -- PLAIN with a residual only
+  if (d->relu == PCP_RELU_PRE_RESIDUAL && (d->mode != PCP_PW_PLAIN || !d->residual)) return PCP_ERR_ARG;
   p.in_h = d->in_h; p.in_w = d->in_w;
   p.cin = d->cin; p.cout = d->cout; p.cout_pad = d->cout_pad;
   p.ld_in = d->ld_in; p.ld_out = d->ld_out; p.relu = d->relu;

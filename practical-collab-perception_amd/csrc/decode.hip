@@ -57,23 +57,32 @@ __device__ __forceinline__ int block_excl_scan(int v, int *scratch, int *total) 
   return res;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
+// Optional parts of the velocity decode (pcp_centerhead_decode_ext); ch_vel / ch_iou < 0 = absent (pcp_centerhead_decode)
+struct DecExt {
+  int ch_vel, ch_iou;
+  float alpha;
+  float *vel;
+};
+
+// one frame of one head per workgroup; IPT items per thread cover IPT * 1024 (class, cell) candidates
+template <int IPT>
+__device__ __forceinline__ void decode_frame(const pcp_decode_t &d, const float *head, int b, const DecExt &ex, float *boxes_out,
+                                             float *scores_out, int *labels_out, int *cell_out, int *count_out) {
   __shared__ int hist[HIST_BINS];
   __shared__ u64 cand[DEC_KMAX];
   __shared__ int scratch[32];
   __shared__ int sel_digit, sel_above, cand_count;
 
-  const pcp_decode_t &d = p.d;
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const int HW = d.h * d.w;
   const int total = HW * d.num_class;
   const int K = min(d.k, total);
-  const float *hb = p.head + (long long)b * HW * d.ld;
+  const float *hb = head + (long long)b * HW * d.ld;
 
   // ---- scores: item i of thread t is flat index i*1024 + t (coalesced across the wave) -----------------------------------
-  unsigned key[DEC_IPT];
+  unsigned key[IPT];
 #pragma unroll
-  for (int i = 0; i < DEC_IPT; i++) {
+  for (int i = 0; i < IPT; i++) {
     int idx = i * DEC_THREADS + tid;
     key[i] = 0u;
     if (idx < total) {
@@ -81,6 +90,13 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
       float hm = hb[(long long)cellid * d.ld + d.ch_hm + cls];
       // activated = 1: the caller already applied sigmoid (centernet_utils.decode_bbox_from_heatmap's convention): the value IS the score
       float s = d.activated ? fminf(fmaxf(hm, 0.0f), 1.0f) : 1.0f / (1.0f + expf(-hm));
+      if (ex.ch_iou >= 0) {
+        // CALIB_CLS_SCORE (center_head.py:318-320): pow(hm, 1 - alpha) * pow(clamp((iou + 1) / 2, 0, 1), alpha); torch's pow with
+        // exponent 0.5 is sqrt, so the default alpha takes the correctly rounded square roots
+        float c = (hb[(long long)cellid * d.ld + ex.ch_iou] + 1.0f) / 2.0f;
+        c = fminf(fmaxf(c, 0.0f), 1.0f);
+        s = ex.alpha == 0.5f ? sqrtf(s) * sqrtf(c) : powf(s, 1.0f - ex.alpha) * powf(c, ex.alpha);
+      }
       key[i] = __float_as_uint(s) + 1u;        // s in [0,1]: bits are monotone; +1 keeps 0 for "absent"
     }
   }
@@ -96,7 +112,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
     for (int i = tid; i < HIST_BINS; i += DEC_THREADS) hist[i] = 0;
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < DEC_IPT; i++)
+    for (int i = 0; i < IPT; i++)
       if (key[i] != 0u && (key[i] & pmask) == prefix) atomicAdd(&hist[(key[i] >> sh) & dm], 1);
     __syncthreads();
     if (tid < 64) {
@@ -131,7 +147,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
   // ---- selection; ties at the threshold go to the lowest flat indices ----------------------------------------------------
   int eq_local = 0;
 #pragma unroll
-  for (int i = 0; i < DEC_IPT; i++) eq_local += (key[i] == kth && kth != 0u) ? 1 : 0;
+  for (int i = 0; i < IPT; i++) eq_local += (key[i] == kth && kth != 0u) ? 1 : 0;
   int eq_total;
   block_excl_scan(eq_local, scratch, &eq_total);
   if (tid == 0) cand_count = 0;
@@ -139,7 +155,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
   __syncthreads();
   int eq_before_item = 0;           // equals in items < i (all threads)
 #pragma unroll
-  for (int i = 0; i < DEC_IPT; i++) {
+  for (int i = 0; i < IPT; i++) {
     bool is_eq = (key[i] == kth) && kth != 0u;
     bool take = key[i] > kth;
     if (eq_total == need) {
@@ -204,19 +220,47 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
   if (ok) {
     long long o = (long long)b * d.k + pos;
 #pragma unroll
-    for (int c = 0; c < 7; c++) p.boxes[o * 7 + c] = box[c];
-    p.scores[o] = score;
-    if (p.labels) p.labels[o] = flat / HW;
-    if (p.cell) p.cell[o] = flat % HW;
+    for (int c = 0; c < 7; c++) boxes_out[o * 7 + c] = box[c];
+    scores_out[o] = score;
+    if (labels_out) labels_out[o] = flat / HW;
+    if (cell_out) cell_out[o] = flat % HW;
+    if (ex.ch_vel >= 0) {
+      const float *px = hb + (long long)(flat % HW) * d.ld;
+      ex.vel[o * 2] = px[ex.ch_vel];
+      ex.vel[o * 2 + 1] = px[ex.ch_vel + 1];
+    }
   }
-  if (tid == 0) p.count[b] = n_ok;
+  if (tid == 0) count_out[b] = n_ok;
 }
+
+__global__ __launch_bounds__(DEC_THREADS) void k_decode(DecParams p) {
+  const DecExt none = {-1, -1, 0.0f, nullptr};
+  decode_frame<DEC_IPT>(p.d, p.head, blockIdx.x, none, p.boxes, p.scores, p.labels, p.cell, p.count);
+}
+
+constexpr int DEC_EXT_IPT = 32;                 // up to 32768 (class, cell) pairs: two classes on a 128 x 128 map
+constexpr int DEC_EXT_CAP = DEC_THREADS * DEC_EXT_IPT;
+
+struct DecExtParams {
+  pcp_decode_head_t heads[PCP_DET_MAX_HEADS];
+  int batch;
+};
+
+// grid = heads x frames: block (h * batch + b)
+__global__ __launch_bounds__(DEC_THREADS) void k_decode_ext(DecExtParams p) {
+  const int hi = blockIdx.x / p.batch, b = blockIdx.x % p.batch;
+  const pcp_decode_head_t &h = p.heads[hi];
+  const DecExt ex = {h.ch_vel, h.ch_iou, h.iou_alpha, h.vel};
+  decode_frame<DEC_EXT_IPT>(h.d, h.head, b, ex, h.boxes, h.scores, h.labels, h.cell, h.count);
+}
+
 
 
 // ---- a8 / a9 tail: the per-frame "boxes[keep], scores[keep], mapping[labels[keep]] + 1, cat over heads" of
 //      center_head.py:335-357 as ONE launch for all frames and heads -------------------------------------------------------------
 struct GatherParams {
   pcp_det_head_t heads[PCP_DET_MAX_HEADS];
+  const float *vel[PCP_DET_MAX_HEADS];      // pcp_gather_detections_ext only: (B, k, 2) per head or nullptr
   int n_heads, batch, out_max;
   float *out_boxes;
   float *out_scores;
@@ -224,6 +268,8 @@ struct GatherParams {
   int *out_count;
 };
 
+// BW = 7: pcp_gather_detections; BW = 9: pcp_gather_detections_ext (box + vel)
+template <int BW>
 __global__ __launch_bounds__(256) void k_gather_detections(GatherParams p) {
   const int b = blockIdx.x;
   int base = 0;
@@ -236,7 +282,12 @@ __global__ __launch_bounds__(256) void k_gather_detections(GatherParams p) {
       const int src = h.keep[(long long)b * h.keep_max + i];
       const long long so = (long long)b * h.k + src, dq = (long long)b * p.out_max + base + i;
 #pragma unroll
-      for (int c = 0; c < 7; c++) p.out_boxes[dq * 7 + c] = h.boxes[so * 7 + c];
+      for (int c = 0; c < 7; c++) p.out_boxes[dq * BW + c] = h.boxes[so * 7 + c];
+      if (BW == 9) {
+        const float *v = p.vel[hi];
+        p.out_boxes[dq * BW + 7] = v ? v[so * 2] : 0.0f;
+        p.out_boxes[dq * BW + 8] = v ? v[so * 2 + 1] : 0.0f;
+      }
       p.out_scores[dq] = h.scores[so];
       const int lab = h.labels ? h.labels[so] : 0;
       p.out_labels[dq] = (long long)(h.class_map ? h.class_map[lab] : lab) + 1;
@@ -280,10 +331,53 @@ extern "C" int pcp_gather_detections(const pcp_det_head_t *heads, int32_t n_head
     if (!heads[i].boxes || !heads[i].scores || !heads[i].keep || !heads[i].keep_count || heads[i].k <= 0 || heads[i].keep_max <= 0)
       return PCP_ERR_ARG;
     p.heads[i] = heads[i];
+    p.vel[i] = nullptr;
   }
   p.n_heads = n_heads; p.batch = batch; p.out_max = out_max;
   p.out_boxes = out_boxes; p.out_scores = out_scores; p.out_labels = reinterpret_cast<long long *>(out_labels); p.out_count = out_count;
-  hipLaunchKernelGGL(k_gather_detections, dim3(batch), dim3(256), 0, (hipStream_t)stream_, p);
+  hipLaunchKernelGGL(k_gather_detections<7>, dim3(batch), dim3(256), 0, (hipStream_t)stream_, p);
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
+
+extern "C" int pcp_centerhead_decode_ext(const pcp_decode_head_t *heads, int32_t n_heads, void *stream_) {
+  if (!heads || n_heads <= 0 || n_heads > PCP_DET_MAX_HEADS) return PCP_ERR_ARG;
+  DecExtParams p;
+  const int batch = heads[0].d.batch;
+  if (batch <= 0) return PCP_ERR_ARG;
+  for (int i = 0; i < n_heads; i++) {
+    const pcp_decode_head_t &h = heads[i];
+    const pcp_decode_t &d = h.d;
+    if (!h.head || !h.boxes || !h.scores || !h.count) return PCP_ERR_ARG;
+    if (d.batch != batch || d.h <= 0 || d.w <= 0 || d.k <= 0 || d.num_class <= 0 || d.ld <= 0) return PCP_ERR_ARG;
+    if (d.k > DEC_KMAX) return PCP_ERR_UNSUPPORTED;
+    if ((long long)d.h * d.w * d.num_class > DEC_EXT_CAP) return PCP_ERR_UNSUPPORTED;
+    if (h.ch_vel >= 0 && (!h.vel || h.ch_vel + 2 > d.ld)) return PCP_ERR_ARG;
+    if (h.ch_iou >= d.ld) return PCP_ERR_ARG;
+    if (d.ch_hm + d.num_class > d.ld || d.ch_center + 2 > d.ld || d.ch_z >= d.ld || d.ch_dim + 3 > d.ld || d.ch_rot + 2 > d.ld)
+      return PCP_ERR_ARG;
+    p.heads[i] = h;
+  }
+  p.batch = batch;
+  hipLaunchKernelGGL(k_decode_ext, dim3(n_heads * batch), dim3(DEC_THREADS), 0, (hipStream_t)stream_, p);
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
+
+extern "C" int pcp_gather_detections_ext(const pcp_det_head_ext_t *heads, int32_t n_heads, int32_t batch, int32_t out_max,
+                                         float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count, void *stream_) {
+  if (!heads || n_heads <= 0 || n_heads > PCP_DET_MAX_HEADS || batch <= 0 || out_max <= 0) return PCP_ERR_ARG;
+  if (!out_boxes || !out_scores || !out_labels || !out_count) return PCP_ERR_ARG;
+  GatherParams p;
+  for (int i = 0; i < n_heads; i++) {
+    const pcp_det_head_t &h = heads[i].h;
+    if (!h.boxes || !h.scores || !h.keep || !h.keep_count || h.k <= 0 || h.keep_max <= 0) return PCP_ERR_ARG;
+    p.heads[i] = h;
+    p.vel[i] = heads[i].vel;
+  }
+  p.n_heads = n_heads; p.batch = batch; p.out_max = out_max;
+  p.out_boxes = out_boxes; p.out_scores = out_scores; p.out_labels = reinterpret_cast<long long *>(out_labels); p.out_count = out_count;
+  hipLaunchKernelGGL(k_gather_detections<9>, dim3(batch), dim3(256), 0, (hipStream_t)stream_, p);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }

@@ -58,6 +58,8 @@ def build_network_from_meta(meta):
     for key in ('BEV_MAKER_RSU', 'BEV_MAKER_CAR', 'BEV_MAKER_EARLY'):
         if cfg.get(key, None) is not None:
             cfg[key].CKPT = None
-    n_feat = {'car': 7, 'early': 7, 'lately': 13, 'disco': 6}.get(meta.get('layout', 'car'), 7)
+    # point columns without the batch index: 'nusc' = the 7-column nuScenes cloud of pointpillar_jr_nomap, 'nusc_map' = the 12-column
+    # cloud of pointpillar_jr_withmap (five HD-map layers after the timestamp)
+    n_feat = {'car': 7, 'early': 7, 'lately': 13, 'disco': 6, 'nusc': 7, 'nusc_map': 12}.get(meta.get('layout', 'car'), 7)
     ds = DatasetInfo(meta['class_names'], meta['pc_range'], meta['voxel_size'], n_feat)
     return build_network(cfg, len(meta['class_names']), ds)

@@ -5,7 +5,8 @@ unchanged.  Inference forward:
   shared 3x3 conv+BN+ReLU            -> one MFMA launch
   all first convs of all branches    -> ONE launch (weights concatenated along cout: 5 x 64 = 320 channels)
   all final convs                    -> ONE launch (block-diagonal weights, 9 real output channels)
-  sigmoid/exp/atan2 + top-K + decode -> one kernel per head (pcp_centerhead_decode), no host sync
+  sigmoid/exp/atan2 + top-K + decode -> one kernel per head (pcp_centerhead_decode), no host sync; heads with a vel branch or
+                                        CALIB_CLS_SCORE: one kernel for all heads (pcp_centerhead_decode_ext), pred_boxes (n, 9) with vel
   rotated NMS                        -> sort-free (already ordered) mask + single-wavefront greedy, per frame
   one device->host copy of the per-frame keep counts at the very end to size the returned tensors.
 """
@@ -146,26 +147,45 @@ class CenterHead(PackedModule):
         off = {n: int(o) for n, o in zip(entry['names'], entry['offs'][:-1])}
         for need in ('center', 'center_z', 'dim', 'rot', 'hm'):
             assert need in off, 'CenterHead decode kernel needs the %s branch' % need
-        assert 'vel' not in off and 'iou' not in off, 'vel / iou branches are not used by the five configs'
-        return dict(k=pp.MAX_OBJ_PER_SAMPLE, num_class=entry['outs'][entry['names'].index('hm')], ch_center=off['center'],
-                    ch_z=off['center_z'], ch_dim=off['dim'], ch_rot=off['rot'], ch_hm=off['hm'],
-                    stride=float(self.feature_map_stride), voxel_x=float(np.float32(self.voxel_size[0])),
-                    voxel_y=float(np.float32(self.voxel_size[1])), min_x=float(self.point_cloud_range[0]),
-                    min_y=float(self.point_cloud_range[1]), limit=list(pp.POST_CENTER_LIMIT_RANGE),
-                    score_thresh=pp.SCORE_THRESH)
+        kw = dict(k=pp.MAX_OBJ_PER_SAMPLE, num_class=entry['outs'][entry['names'].index('hm')], ch_center=off['center'],
+                  ch_z=off['center_z'], ch_dim=off['dim'], ch_rot=off['rot'], ch_hm=off['hm'],
+                  stride=float(self.feature_map_stride), voxel_x=float(np.float32(self.voxel_size[0])),
+                  voxel_y=float(np.float32(self.voxel_size[1])), min_x=float(self.point_cloud_range[0]),
+                  min_y=float(self.point_cloud_range[1]), limit=list(pp.POST_CENTER_LIMIT_RANGE),
+                  score_thresh=pp.SCORE_THRESH)
+        if self._with_vel():
+            assert 'vel' in off, "HEAD_ORDER lists 'vel' but the head has no vel branch"
+            kw['ch_vel'] = off['vel']
+        if pp.get('CALIB_CLS_SCORE', False):
+            assert 'iou' in off, 'CALIB_CLS_SCORE needs the iou branch'
+            kw['ch_iou'] = off['iou']
+            kw['iou_alpha'] = float(pp.get('CALIB_CLS_SCORE_ALPHA', 0.5))
+        return kw
+
+    def _with_vel(self):
+        """reference :313: the decode appends vel (pred_boxes (n, 9)) whenever HEAD_ORDER names it"""
+        return 'vel' in self.separate_head_cfg.HEAD_ORDER
+
+    def _ext_decode(self):
+        """heads with vel or CALIB_CLS_SCORE run pcp_centerhead_decode_ext (all heads in one launch); the others keep pcp_centerhead_decode"""
+        return self._with_vel() or bool(self.model_cfg.POST_PROCESSING.get('CALIB_CLS_SCORE', False))
 
     def device_postprocess(self, head_bufs, pk):
         """decode + NMS for every head, everything left on the device (hipGraph-capturable: no host sync)."""
         nms_cfg = self.model_cfg.POST_PROCESSING.NMS_CONFIG
         assert nms_cfg.NMS_TYPE == 'nms_gpu', 'only the rotated nms_gpu of the five configs is built'
         per_head = []
-        for idx, (buf, entry) in enumerate(zip(head_bufs, pk['heads'])):
-            boxes, scores, labels, _cell, count = ops.centerhead_decode(buf, self._decode_kwargs(entry))
+        if self._ext_decode():
+            # vel / CALIB_CLS_SCORE: one decode launch for every head and frame; vel rides beside the 7-wide boxes the NMS reads
+            decoded = ops.centerhead_decode_ext([(buf, self._decode_kwargs(entry)) for buf, entry in zip(head_bufs, pk['heads'])])
+        else:
+            decoded = [ops.centerhead_decode(buf, self._decode_kwargs(entry)) + (None,) for buf, entry in zip(head_bufs, pk['heads'])]
+        for idx, (boxes, scores, labels, _cell, count, vel) in enumerate(decoded):
             k = boxes.shape[1]
             # candidates are already in descending score order: scores=None skips the device sort; all frames in one call
             keep, kcnt = ops.nms_rotated(boxes, None, nms_cfg.NMS_THRESH, min(nms_cfg.NMS_PRE_MAXSIZE, k), nms_cfg.NMS_POST_MAXSIZE,
                                          n_dev=count)
-            per_head.append((boxes, scores, labels, keep, kcnt, idx))
+            per_head.append((boxes, scores, labels, keep, kcnt, idx) if vel is None else (boxes, scores, labels, keep, kcnt, idx, vel))
         return per_head
 
     def finalize(self, per_head, batch_size):
@@ -177,17 +197,22 @@ class CenterHead(PackedModule):
                 for b in range(batch_size)]
 
     def gather_pending(self, per_head, batch_size):
-        """the gather launch of finalize() WITHOUT its host read: padded (B, M, 7) boxes, (B, M) scores, (B, M) int64 1-based labels and the
-        (B,) int32 counts, all on the device (consumers that stay on the device: pcdet/models/lately_chain.py)"""
+        """the gather launch of finalize() WITHOUT its host read: padded (B, M, 7) boxes ((B, M, 9) = [box | vel] for a head with a vel
+        branch), (B, M) scores, (B, M) int64 1-based labels and the (B,) int32 counts, all on the device (consumers that stay on the device:
+        pcdet/models/lately_chain.py)"""
         heads = []
-        for boxes, scores, labels, keep, kcnt, idx in per_head:
+        for entry in per_head:
+            boxes, scores, labels, keep, kcnt, idx = entry[:6]
             cmap = self._class_maps.get(idx) if hasattr(self, '_class_maps') else None
             if cmap is None or cmap.device != boxes.device:
                 if not hasattr(self, '_class_maps'):
                     self._class_maps = {}
                 cmap = self.class_id_mapping_each_head[idx].to(device=boxes.device, dtype=torch.int32).contiguous()
                 self._class_maps[idx] = cmap
-            heads.append(dict(boxes=boxes, scores=scores, labels=labels, keep=keep, keep_count=kcnt, class_map=cmap))
+            heads.append(dict(boxes=boxes, scores=scores, labels=labels, keep=keep, keep_count=kcnt, class_map=cmap,
+                              vel=entry[6] if len(entry) > 6 else None))
+        if any(h['vel'] is not None for h in heads):
+            return ops.gather_detections_ext(heads, batch_size)
         return ops.gather_detections(heads, batch_size)
 
     def generate_predicted_boxes(self, batch_size, head_bufs, pk):

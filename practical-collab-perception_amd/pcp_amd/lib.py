@@ -85,6 +85,16 @@ class Decode(ctypes.Structure):
                 ('use_score_thresh', c_i32), ('score_thresh', c_f), ('activated', c_i32)]
 
 
+class DecodeHead(ctypes.Structure):
+    """pcp_decode_head_t: one head of pcp_centerhead_decode_ext"""
+    _fields_ = [('d', Decode), ('head', vp), ('ch_vel', c_i32), ('ch_iou', c_i32), ('iou_alpha', c_f), ('boxes', vp), ('scores', vp),
+                ('labels', vp), ('cell', vp), ('count', vp), ('vel', vp)]
+
+
+class DetHeadExt(ctypes.Structure):
+    _fields_ = [('h', DetHead), ('vel', vp)]
+
+
 class Anchor(ctypes.Structure):
     _fields_ = [('batch', c_i32), ('h', c_i32), ('w', c_i32), ('ld', c_i32), ('anchors_per_loc', c_i32), ('num_class', c_i32),
                 ('num_dir_bins', c_i32), ('ch_cls', c_i32), ('ch_box', c_i32), ('ch_dir', c_i32), ('dir_offset', c_f),
@@ -134,6 +144,7 @@ class HunterLoss(ctypes.Structure):
 
 
 PW_PLAIN, PW_SPACE2DEPTH, PW_DEPTH2SPACE = 0, 1, 2
+RELU_PRE_RESIDUAL = 2          # pcp_pointwise relu value: relu(x W^T + b + residual)
 
 # every symbol include/pcp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -175,6 +186,10 @@ SYMBOLS = {
     'pcp_pointwise': (c_i32, [ctypes.POINTER(Pointwise), vp, vp, vp, vp, vp]),
     'pcp_decode_workspace_bytes': (c_sz, [ctypes.POINTER(Decode)]),
     'pcp_centerhead_decode': (c_i32, [ctypes.POINTER(Decode), vp, vp, c_sz, vp, vp, vp, vp, vp, vp]),
+    'pcp_centerhead_decode_ext': (c_i32, [ctypes.POINTER(DecodeHead), c_i32, vp]),
+    'pcp_gather_detections_ext': (c_i32, [ctypes.POINTER(DetHeadExt), c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
+    'pcp_avgpool_nhwc': (c_i32, [vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32, vp]),
+    'pcp_sc_gate': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, c_i32, c_i32, c_i32, vp]),
     'pcp_column_id_mask': (c_i32, [vp, ctypes.c_int64, c_i32, c_i32, vp, vp]),
     'pcp_column_id_counts': (c_i32, [vp, ctypes.c_int64, c_i32, c_i32, vp, vp]),
     'pcp_agent_frame_live': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, vp, vp]),

@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from . import lib as _lib
-from .lib import Conv3x3, Decode, DetHead, Grid, Pointwise, check
+from .lib import Conv3x3, Decode, DecodeHead, DetHead, DetHeadExt, Grid, Pointwise, check
 
 
 _RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
@@ -483,9 +483,10 @@ def conv3x3_grouped_small(x, weights, bias, offsets, out):
 
 
 def pointwise(x, packed, bias, mode, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0, x2=None,
-              k_split=0, x2_ch_off=0, residual=None, res_ch_off=0):
+              k_split=0, x2_ch_off=0, residual=None, res_ch_off=0, residual_before_relu=False):
     """mode PW_PLAIN: x (..., ld_in) rows; PW_SPACE2DEPTH / PW_DEPTH2SPACE: x (B, H, W, ld_in).
-    PLAIN extras: x2 supplies contraction channels [k_split, cin) (a cat without the copy); residual is added last."""
+    PLAIN extras: x2 supplies contraction channels [k_split, cin) (a cat without the copy); residual is added last, or, with
+    residual_before_relu, before the activation: relu(x W^T + b + residual) (SCBottleneck's conv3 + bn3 + identity)."""
     _need_cuda(x, packed, bias, out, x2, residual)
     _need_f32('pcp_pointwise', x, out, x2, residual)
     L = _lib.load()
@@ -503,7 +504,10 @@ def pointwise(x, packed, bias, mode, cin, cout, cout_pad, relu=True, out=None, i
             out = torch.empty(shp, dtype=torch.float32, device=x.device)
     assert bias.numel() >= cout_pad, 'bias must hold cout_pad values (the epilogue reads it 16 bytes at a time)'
     assert x.is_contiguous() and out.is_contiguous()
-    d = Pointwise(mode, rows, B, H, W, cin, cout, cout_pad, ld_in, out.shape[-1], 1 if relu else 0)
+    if residual_before_relu:
+        assert mode == _lib.PW_PLAIN and residual is not None and relu, 'residual_before_relu: PLAIN 1x1 with a residual and a ReLU'
+    d = Pointwise(mode, rows, B, H, W, cin, cout, cout_pad, ld_in, out.shape[-1],
+                  _lib.RELU_PRE_RESIDUAL if residual_before_relu else (1 if relu else 0))
     if x2 is not None:
         assert mode == _lib.PW_PLAIN and x2.is_contiguous() and x2.numel() // x2.shape[-1] == rows
         d.in2 = x2.data_ptr() + 4 * x2_ch_off
@@ -548,6 +552,124 @@ def centerhead_decode(head, desc_kwargs):
     check(L.pcp_centerhead_decode(ctypes.byref(d), _p(head), ctypes.c_void_p(0), 0, _p(boxes), _p(scores), _p(labels), _p(cell),
                                   _p(count), _stream()), 'pcp_centerhead_decode')
     return boxes, scores, labels, cell, count
+
+
+def _decode_desc(d, B, H, W, ld, desc_kwargs):
+    d.batch, d.h, d.w, d.ld = B, H, W, ld
+    d.num_class = desc_kwargs.get('num_class', 1)
+    d.ch_center, d.ch_z, d.ch_dim, d.ch_rot, d.ch_hm = (desc_kwargs[n] for n in ('ch_center', 'ch_z', 'ch_dim', 'ch_rot', 'ch_hm'))
+    d.k = desc_kwargs['k']
+    d.stride = float(desc_kwargs['stride'])
+    d.voxel_x, d.voxel_y = desc_kwargs['voxel_x'], desc_kwargs['voxel_y']
+    d.min_x, d.min_y = desc_kwargs['min_x'], desc_kwargs['min_y']
+    for i, v in enumerate(desc_kwargs['limit']):
+        d.limit[i] = float(v)
+    st = desc_kwargs.get('score_thresh', None)
+    d.use_score_thresh = 0 if st is None else 1
+    d.score_thresh = 0.0 if st is None else float(st)
+    d.activated = 1 if desc_kwargs.get('activated', False) else 0
+
+
+def centerhead_decode_ext(heads):
+    """heads: list of (head (B, H, W, ld) NHWC, desc_kwargs) -- the keys of centerhead_decode plus optional ch_vel (vel channels) and
+    ch_iou / iou_alpha (CALIB_CLS_SCORE).  ONE launch for all heads and frames (pcp_centerhead_decode_ext).  Returns per head
+    (boxes (B,K,7), scores (B,K), labels (B,K) i32, cell (B,K) i32, count (B,) i32, vel (B,K,2) | None)."""
+    L = _lib.load()
+    assert 0 < len(heads) <= 8, 'pcp_centerhead_decode_ext takes 1 .. 8 heads'
+    arr = (DecodeHead * len(heads))()
+    specs, metas = [], []
+    B = heads[0][0].shape[0]
+    for buf, kw in heads:
+        _need_cuda(buf)
+        _need_f32('pcp_centerhead_decode_ext', buf)
+        assert buf.is_contiguous() and buf.shape[0] == B
+        k = kw['k']
+        has_vel = kw.get('ch_vel', None) is not None
+        metas.append((k, has_vel))
+        specs += [((B, k, 7), torch.float32), ((B, k), torch.float32), ((B, k), torch.int32), ((B, k), torch.int32), ((B,), torch.int32)]
+        if has_vel:
+            specs.append(((B, k, 2), torch.float32))
+    views = _zeros_views(heads[0][0].device, specs)
+    out, j = [], 0
+    for i, ((buf, kw), (k, has_vel)) in enumerate(zip(heads, metas)):
+        Bh, H, W, ld = buf.shape
+        _decode_desc(arr[i].d, Bh, H, W, ld, kw)
+        boxes, scores, labels, cell, count = views[j:j + 5]
+        j += 5
+        vel = None
+        if has_vel:
+            vel = views[j]
+            j += 1
+        arr[i].head = _p(buf).value
+        arr[i].ch_vel = int(kw['ch_vel']) if has_vel else -1
+        iou = kw.get('ch_iou', None)
+        arr[i].ch_iou = -1 if iou is None else int(iou)
+        arr[i].iou_alpha = float(kw.get('iou_alpha', 0.5))
+        arr[i].boxes, arr[i].scores, arr[i].labels, arr[i].cell = _p(boxes).value, _p(scores).value, _p(labels).value, _p(cell).value
+        arr[i].count, arr[i].vel = _p(count).value, _p(vel).value
+        out.append((boxes, scores, labels, cell, count, vel))
+    check(L.pcp_centerhead_decode_ext(arr, len(heads), _stream()), 'pcp_centerhead_decode_ext')
+    return out
+
+
+def gather_detections_ext(heads, batch):
+    """gather_detections with velocity: every head dict may carry 'vel' (B, k, 2) (None: zeros).  Returns (boxes (B,M,9) = [box | vel],
+    scores (B,M), labels (B,M) int64 1-based, count (B,) int32), M = sum of keep_max; rows beyond count[b] are zero."""
+    L = _lib.load()
+    arr = (DetHeadExt * len(heads))()
+    out_max = 0
+    for i, h in enumerate(heads):
+        _need_cuda(h['boxes'], h['scores'], h['labels'], h['keep'], h['keep_count'], h.get('class_map'), h.get('vel'))
+        assert h['boxes'].is_contiguous() and h['scores'].is_contiguous() and h['keep'].is_contiguous() and h['keep'].dtype == torch.int32
+        assert h['boxes'].shape[0] == batch and h['keep'].shape[0] == batch
+        v = h.get('vel')
+        if v is not None:
+            assert v.is_contiguous() and v.dtype == torch.float32 and tuple(v.shape) == (batch, h['boxes'].shape[1], 2)
+        a = arr[i].h
+        a.boxes, a.scores, a.labels = _p(h['boxes']).value, _p(h['scores']).value, _p(h['labels']).value
+        a.keep, a.keep_count, a.class_map = _p(h['keep']).value, _p(h['keep_count']).value, _p(h.get('class_map')).value
+        a.k, a.keep_max = int(h['boxes'].shape[1]), int(h['keep'].shape[1])
+        arr[i].vel = _p(v).value
+        out_max += int(h['keep'].shape[1])
+    dev = heads[0]['boxes'].device
+    ob, os_, cnt = _zeros_views(dev, [((batch, out_max, 9), torch.float32), ((batch, out_max), torch.float32), ((batch,), torch.int32)])
+    ol = torch.zeros((batch, out_max), dtype=torch.int64, device=dev)
+    check(L.pcp_gather_detections_ext(arr, len(heads), batch, out_max, _p(ob), _p(os_), _p(ol), _p(cnt), _stream()),
+          'pcp_gather_detections_ext')
+    return ob, os_, ol, cnt
+
+
+def avgpool_nhwc(x, r, out=None, in_ch_off=0, c=None):
+    """nn.AvgPool2d(r, r) on a (B, H, W, ld) NHWC channel window [in_ch_off, in_ch_off + c) -> (B, H // r, W // r, c) (or `out`)"""
+    _need_cuda(x, out)
+    _need_f32('pcp_avgpool_nhwc', x, out)
+    L = _lib.load()
+    B, H, W, ld = x.shape
+    c = ld - in_ch_off if c is None else c
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty((B, H // r, W // r, c), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape[:3]) == (B, H // r, W // r) and out.shape[-1] >= c
+    check(L.pcp_avgpool_nhwc(_chan_ptr(x, in_ch_off), B, H, W, c, ld, int(r), _p(out), out.shape[-1], _stream()), 'pcp_avgpool_nhwc')
+    return out
+
+
+def sc_gate(t, x, s, c, out=None, t_ch_off=0, x_ch_off=0, s_ch_off=0, out_ch_off=0):
+    """SCConv gate out = t * sigmoid(x + nearest_up(s)) on NHWC channel windows of c channels: t, x (B, H, W, ld) at (H, W),
+    s (B, sh, sw, ld) at the pooled size.  out None: written in place over t's window."""
+    _need_cuda(t, x, s, out)
+    _need_f32('pcp_sc_gate', t, x, s, out)
+    L = _lib.load()
+    if out is None:
+        out, out_ch_off = t, t_ch_off
+    B, H, W, _ = t.shape
+    assert tuple(x.shape[:3]) == (B, H, W) and tuple(out.shape[:3]) == (B, H, W) and s.shape[0] == B
+    assert t.is_contiguous() and x.is_contiguous() and s.is_contiguous() and out.is_contiguous()
+    for ten, off in ((t, t_ch_off), (x, x_ch_off), (s, s_ch_off), (out, out_ch_off)):
+        assert off + c <= ten.shape[-1]
+    check(L.pcp_sc_gate(_chan_ptr(t, t_ch_off), t.shape[-1], _chan_ptr(x, x_ch_off), x.shape[-1], _chan_ptr(s, s_ch_off), s.shape[-1],
+                        s.shape[1], s.shape[2], _chan_ptr(out, out_ch_off), out.shape[-1], B, H, W, int(c), _stream()), 'pcp_sc_gate')
+    return out
 
 
 def nms_normal(boxes, scores, thresh, pre_max, post_max, n_dev=None, workspace=None):

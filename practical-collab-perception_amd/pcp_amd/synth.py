@@ -105,6 +105,19 @@ def agent_cloud(agent, n_points=60000, layout='car', seed=SEED_BASE, xy_half=52.
     return np.stack(cols, axis=1).astype(np.float32)
 
 
+def nusc_cloud(frame, n_points, xy_half=52.0, with_map=False, dist='uniform'):
+    """one nuScenes-like frame WITHOUT the batch column: the 7 columns [x, y, z, intensity, timestamp, sweep_idx, instance_idx] of
+    pointpillar_jr_nomap (the 'car' layout, z in the nuScenes range [-5, 3)); with_map: the 12 columns of pointpillar_jr_withmap
+    (five HD-map layers after the timestamp: four 0/1 masks and a lane direction in [-pi, pi))"""
+    c = agent_cloud(agent=40 + frame, n_points=n_points, layout='car', xy_half=xy_half, z_range=(-5.0, 3.0), dist=dist)
+    if not with_map:
+        return c
+    s = lambda col: stream_id(40 + frame, 100 + col)
+    layers = [(uniform01(SEED_BASE, s(j), n_points) < 0.3).astype(np.float32) for j in range(4)]
+    lane = uniform(SEED_BASE, s(4), n_points, -math.pi, math.pi)
+    return np.concatenate([c[:, :5], np.stack(layers + [lane], axis=1), c[:, 5:]], axis=1).astype(np.float32)
+
+
 def mask_outside_range(points_xyz_first, pc_range):
     """Host pre-mask applied by the dataset in configs 1-4 (reference: data_processor.py:78-92 ->
     common_utils.py:64-68): keep rows with min <= p < max on x, y and z.  The synthetic benchmark clouds are

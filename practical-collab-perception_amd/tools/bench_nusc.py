@@ -1,0 +1,139 @@
+"""Throughput of the nuScenes PointPillar-Jr model (pointpillar_jr_nomap: DynPillarVFE -> scatter -> SCConvBackbone2dStride4 -> CenterHead
+with six heads and vel / iou branches) on seeded synthetic 7-column clouds, B = 1 and B = 4, eager model(batch) per step (one host read of
+the box counts per step, as in tools/test.py).  Prints a per-layer table of the backbone (B = 4, CUDA events around every launch group)
+and, last, one JSON line.
+
+    python practical-collab-perception_amd/tools/bench_nusc.py [--points 260000] [--steps 20] [--warmup 5]
+
+Synthetic weights (pcp_amd.synth.fill_state_dict, gain 1.6): the arithmetic does not depend on them, only the number of boxes that reach
+the NMS does.  A 10-sweep nuScenes cloud holds about 250 000 - 300 000 points.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.dirname(HERE)
+sys.path.insert(0, PKG)
+
+from pcdet.config import EasyDict, cfg_from_yaml_file  # noqa: E402
+from pcdet.models import DatasetInfo, build_network  # noqa: E402
+from pcp_amd import lib, ops, synth  # noqa: E402
+
+YAML = os.path.join(HERE, 'cfgs', 'nuscenes_models', 'pointpillar_jr_nomap.yaml')
+
+
+def build_model():
+    cfg = cfg_from_yaml_file(YAML, EasyDict())
+    vs = [p['VOXEL_SIZE'] for p in cfg.DATA_CONFIG.DATA_PROCESSOR if 'VOXEL_SIZE' in p][0]
+    ds = DatasetInfo(cfg.CLASS_NAMES, cfg.DATA_CONFIG.POINT_CLOUD_RANGE, vs, len(cfg.DATA_CONFIG.POINT_FEATURE_ENCODING.used_feature_list))
+    model = build_network(cfg.MODEL, len(cfg.CLASS_NAMES), ds)
+    shapes = {k: list(v.shape) for k, v in model.state_dict().items()}
+    state = synth.fill_state_dict(shapes, scheme='gain:1.6')
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    return model.cuda().eval()
+
+
+def time_steps(model, pts, batch_size, steps, warmup):
+    dev_pts = torch.from_numpy(pts).cuda()
+    boxes = 0
+    with torch.no_grad():
+        for i in range(warmup + steps):
+            if i == warmup:
+                torch.cuda.synchronize()
+                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+            preds, _ = model({'points': dev_pts, 'batch_size': batch_size, 'metadata': [{}] * batch_size})
+            boxes = sum(int(p['pred_boxes'].shape[0]) for p in preds)
+        end.record()
+        torch.cuda.synchronize()
+    ms = start.elapsed_time(end) / steps
+    return ms, boxes
+
+
+def backbone_table(model, pts, batch_size, reps=10):
+    """GPU time per launch group of the backbone, on the canvas of one forward"""
+    bd = {'points': torch.from_numpy(pts).cuda(), 'batch_size': batch_size, 'metadata': [{}] * batch_size}
+    with torch.no_grad():
+        model(bd)
+    bb = model.backbone_2d
+    pk = bb.packed()
+    rows = []
+
+    def timed(name, fn):
+        out = fn()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(reps):
+            out = fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        rows.append((name, ev[0].elapsed_time(ev[1]) / reps))
+        return out
+
+    def block(prefix, blk, x):
+        gw = blk.gw
+        B, H, W, _ = x.shape
+        ab = timed(prefix + 'conv1_a|b 1x1', lambda: blk.conv1.run(x))
+        cat = torch.empty((B, H, W, 2 * gw), dtype=torch.float32, device=x.device)
+        timed(prefix + 'k1 3x3', lambda: blk.k1.run(ab, out=cat, in_ch_off=0, out_ch_off=0))
+        pooled = timed(prefix + 'avgpool (SC)', lambda: ops.avgpool_nhwc(ab, 4, in_ch_off=gw, c=gw))
+        s = timed(prefix + 'k2 3x3 @1/4', lambda: blk.k2.run(pooled))
+        t = timed(prefix + 'k3 3x3', lambda: blk.k3.run(ab, in_ch_off=gw))
+        t0 = t.clone()
+        timed(prefix + 'gate (SC)', lambda: ops.sc_gate(t0, ab, s, gw, x_ch_off=gw, out=t))
+        timed(prefix + 'k4 3x3', lambda: blk.k4.run(t, out=cat, out_ch_off=gw))
+        c3 = blk.conv3
+        return timed(prefix + 'conv3 1x1 + residual', lambda: ops.pointwise(cat, c3.w, c3.b, lib.PW_PLAIN, c3.cin, c3.cout, c3.cout_pad,
+                                                                                   relu=True, residual=x, residual_before_relu=True))
+
+    with torch.no_grad():
+        x = ops.as_nhwc(bd['spatial_features'])
+        x = timed('stem.0 3x3 s2', lambda: pk['stem0'].run(x))
+        for i, blk in enumerate(pk['stem_blocks']):
+            x = block('stem.%d ' % (i + 1), blk, x)
+        B, H, W, _ = x.shape
+        merged = torch.empty((B, H, W, pk['up'].cout + pk['skip'].cout), dtype=torch.float32, device=x.device)
+        timed('conv_skip 1x1', lambda: pk['skip'].run(x, out=merged, out_ch_off=pk['up'].cout))
+        y = timed('main_pass.0 3x3 s2', lambda: pk['main0'].run(x))
+        for i, blk in enumerate(pk['main_blocks']):
+            y = block('main_pass.%d ' % (i + 1), blk, y)
+        timed('main_pass.4 convT 2x2', lambda: pk['up'].run(y, out=merged, out_ch_off=0))
+        timed('conv_out 3x3 s2', lambda: pk['out'].run(merged))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--points', type=int, default=260000)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    args = ap.parse_args()
+    model = build_model()
+    res = {'metric': 'pointpillar_jr_nomap', 'points_per_frame': args.points, 'cloud': 'synth.nusc_cloud ring, seeded',
+           'conv_algo': os.environ.get('PCP_CONV_ALGO', 'auto')}
+    clouds = [synth.nusc_cloud(b, args.points, dist='ring') for b in range(4)]
+    for B in (1, 4):
+        pts = synth.collate(clouds[:B])
+        ms, boxes = time_steps(model, pts, B, args.steps, args.warmup)
+        res['b%d_ms_per_step' % B] = round(ms, 3)
+        res['b%d_frames_per_s' % B] = round(1000.0 * B / ms, 1)
+        res['b%d_boxes' % B] = boxes
+    rows = backbone_table(model, synth.collate(clouds), 4)
+    total = sum(t for _, t in rows)
+    sc = sum(t for n, t in rows if '(SC)' in n)
+    print('backbone per launch group, B = 4 (ms per step, CUDA events, mean of 10):')
+    for n, t in rows:
+        print('  %-36s %8.3f  %5.1f %%' % (n, t, 100.0 * t / total))
+    print('  %-36s %8.3f' % ('total', total))
+    print('  %-36s %8.3f  %5.1f %%' % ('SC-specific kernels (pool, gate)', sc, 100.0 * sc / total))
+    res['b4_backbone_ms'] = round(total, 3)
+    res['b4_sc_specific_share'] = round(sc / total, 4)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
