@@ -121,6 +121,62 @@ size_t pcp_loss_workspace_bytes(void);
 int pcp_centerhead_loss(const pcp_headloss_t *desc, const float *head, const float *heatmap, const float *target_boxes,
                         const int32_t *inds, const int32_t *mask, float grad_scale, void *workspace, float *losses, float *dhead,
                         void *stream);
+/* ------------------------------------------------------------------------------------------------------------------
+ * a15x  CenterHead training for several heads, velocity codes and the IoU branch (the nuScenes PointPillar-Jr head).
+ * Replaces: center_head.py:168-268 (assign_targets: per head and frame a class-name filter in python, .cpu(), the per-box loop),
+ *           :213-242 with dense_heads/box_utils.py:6-67 (the IoU target: decode the prediction at each ground-truth centre,
+ *           axis-aligned IoU), :105-166 with 9- and 10-column rows (velocity targets, the IoU column), :274-300 (get_loss over
+ *           every head) and their autograd.  The one-head, 8-code entry points above keep serving the five V2X-Sim configs.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_TGT_MAX_CLASSES 32
+#define PCP_HEADLOSS_MAX_CODES 16
+
+typedef struct {
+  int32_t num_class;                              /* classes of this head = channels of its heat map */
+  int32_t class_to_local[PCP_TGT_MAX_CLASSES];    /* indexed by the class column of gt_boxes (0 = padding row): 0 = not in this head,
+                                                   * else the 1-based index inside the head */
+  float *heatmap;                                 /* (B, H, W, num_class) NHWC */
+  float *target_boxes;                            /* (B, k, T) */
+  int32_t *inds, *mask;                           /* (B, k) */
+  const float *head;                              /* raw head maps (B, H, W, ld) for the IoU target; read only when with_iou */
+  int32_t ld, ch_center, ch_z, ch_dim, ch_rot;         /* ch_z is validated but not read: the IoU is that of the BEV rectangles */
+} pcp_target_head_t;
+
+/* ONE launch for every (frame, head); desc->num_class is not read (each head brings its own).
+ * gt_boxes (B, max_boxes, box_width), box_width 8 = [x,y,z,dx,dy,dz,heading,class] or 10 = [.., heading, vx, vy, class]; max_boxes <= 1024;
+ * gt_boxes is only read (the reference rewrites the class column in place, center_head.py:203-204: the caller checks that this is inert).
+ * A row's slot is its rank among the rows of its head in row order; ranks >= k are dropped.
+ * target_boxes columns, T = 8 (+2 if box_width = 10) (+1 if with_iou): [dx, dy, z, log dims(3), cos, sin, (vx, vy), (iou)],
+ * iou = 2 * axis_aligned_iou(box decoded from head at the clamped, truncated centre, gt box) - 1, a constant of the step (no gradient).
+ * Rows are finite by contract: a NaN velocity is copied as it is and makes the loss NaN. */
+int pcp_centerhead_targets_ext(const pcp_target_t *desc, const pcp_target_head_t *heads, int32_t n_heads, const float *gt_boxes,
+                               int32_t max_boxes, int32_t box_width, int32_t with_iou, void *stream);
+
+typedef struct {
+  const float *head;              /* raw head maps (B, H, W, ld) */
+  float *dhead;                   /* gradient (B, H, W, ld_d), same channel numbering; NULL for every head or for none */
+  const float *heatmap, *target_boxes;
+  const int32_t *inds, *mask;
+  int32_t ld, ld_d, ch_hm, num_class;
+  int32_t n_codes;                /* <= PCP_HEADLOSS_MAX_CODES */
+  int32_t reg_ch[PCP_HEADLOSS_MAX_CODES];   /* channel of each regression code, in HEAD_ORDER concatenation order */
+  int32_t tb_width;               /* row width of target_boxes; must equal n_codes (column j pairs with code j, center_head.py:286-292) */
+} pcp_headloss_head_t;
+
+typedef struct {
+  int32_t batch, h, w, k;
+  float cls_weight, loc_weight, code_weights[PCP_HEADLOSS_MAX_CODES];
+} pcp_headloss_ext_t;
+
+size_t pcp_centerhead_loss_ext_workspace_bytes(int32_t n_heads);
+/* All heads in four launches, whatever n_heads (<= PCP_DET_MAX_HEADS).  losses (n_heads, 4) = per head [hm_loss * cls_weight,
+ * loc_loss * loc_weight, their sum, num_pos]; total (1,) = the sum of the third column, added in head order.  The arithmetic per head
+ * is pcp_centerhead_loss's; block partials are float64 and added in a fixed order, and the gradient of boxes that share a cell is added
+ * in slot order, so the result is the same bits on every run.  dhead of every head is written completely (zero where no term reads the
+ * map), scaled by grad_scale.  Targets are finite by contract: NaN targets (the reference's isnotnan mask) are out of scope. */
+int pcp_centerhead_loss_ext(const pcp_headloss_ext_t *desc, const pcp_headloss_head_t *heads, int32_t n_heads, float grad_scale,
+                            void *workspace, size_t workspace_bytes, float *losses, float *total, void *stream);
+
 /* loss (1,) = weight * mean smooth_l1(softmax_c(fused) - softmax_c(early)); dfused (pixels, ld_d) written or accumulated (NULL: none);
  * c <= 512.  Shares the workspace of pcp_centerhead_loss. */
 int pcp_distill_loss(const float *fused, int32_t ld_f, const float *early, int32_t ld_e, int64_t pixels, int32_t c, float weight,

@@ -376,7 +376,396 @@ __global__ void k_masked_sl1_finalize(const double *__restrict__ acc, int nb, fl
 }
 }  // namespace
 
+// ---- a15x: several heads, velocity codes, the IoU branch (center_head.py:168-300 for the nuScenes head) ------------------------
+namespace {
+
+struct TgtExtParams {
+  pcp_target_t d;
+  pcp_target_head_t heads[PCP_DET_MAX_HEADS];
+  int bw, with_iou, tw;            // row width of gt_boxes, IoU column requested, row width of target_boxes
+};
+
+// box_utils.py:6-25 as it stands: the (3, 4) sign table is reshaped with .view(4, 3), NOT transposed, so the four "corners" are
+// (+,+), (-,-), (+,-), (+,+) -- three distinct points.  The rectangle is the axis-aligned hull of those, rotated (common_utils.py:39-61:
+// x' = x cos - y sin, y' = x sin + y cos) and shifted to the centre.
+__device__ void aa_rect(float x, float y, float dx, float dy, float angle, float *r) {
+  const float c = cosf(angle), s = sinf(angle);
+  const float hx = 0.5f * dx, hy = 0.5f * dy;
+  const float sx[4] = {1.f, -1.f, 1.f, 1.f}, sy[4] = {1.f, -1.f, -1.f, 1.f};
+  float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float lx = hx * sx[i], ly = hy * sy[i];
+    const float wx = lx * c + ly * (-s) + x;
+    const float wy = lx * s + ly * c + y;
+    x0 = fminf(x0, wx); x1 = fmaxf(x1, wx);
+    y0 = fminf(y0, wy); y1 = fmaxf(y1, wy);
+  }
+  r[0] = x0; r[1] = y0; r[2] = x1; r[3] = y1;
+}
+
+// box_utils.py:39-67
+__device__ float aa_iou(const float *a, const float *b) {
+  const float ix1 = fminf(a[2], b[2]), iy1 = fminf(a[3], b[3]);
+  const float ix0 = fmaxf(a[0], b[0]), iy0 = fmaxf(a[1], b[1]);
+  const float inter = fmaxf(ix1 - ix0, 0.f) * fmaxf(iy1 - iy0, 0.f);
+  const float a1 = fmaxf(a[2] - a[0], 0.f) * fmaxf(a[3] - a[1], 0.f);
+  const float a2 = fmaxf(b[2] - b[0], 0.f) * fmaxf(b[3] - b[1], 0.f);
+  const float uni = a1 + a2 - inter;
+  return uni > 0.f ? inter / uni : 0.f;
+}
+
+// grid = heads x frames: block (h * batch + b).  k_targets with a per-head class table, 8- or 10-column rows and the IoU column; the
+// block also zeroes its own heat-map slab, so the whole assignment is this one launch.
+__global__ __launch_bounds__(TGT_THREADS) void k_targets_ext(TgtExtParams p, const float *__restrict__ gt, int m) {
+  __shared__ BoxT boxes[TGT_MAX_BOXES];
+  __shared__ int rank_of[TGT_MAX_BOXES];
+  __shared__ int wave_tot[TGT_THREADS / 64];
+  __shared__ int base;
+  const pcp_target_t &d = p.d;
+  const int hi = blockIdx.x / d.batch, b = blockIdx.x % d.batch;
+  const pcp_target_head_t &hd = p.heads[hi];
+  const int tid = threadIdx.x;
+  const int bw = p.bw, tw = p.tw, ncls = hd.num_class;
+  const float *g = gt + (long long)b * m * bw;
+  float *tbox = hd.target_boxes + (long long)b * d.k * tw;
+  int *inds = hd.inds + (long long)b * d.k, *mask = hd.mask + (long long)b * d.k;
+  float *heat = hd.heatmap + (long long)b * d.h * d.w * ncls;
+  if (tid == 0) base = 0;
+  for (int i = tid; i < d.k * tw; i += TGT_THREADS) tbox[i] = 0.f;
+  for (int i = tid; i < d.k; i += TGT_THREADS) { inds[i] = 0; mask[i] = 0; }
+  for (int i = tid; i < d.h * d.w * ncls; i += TGT_THREADS) heat[i] = 0.f;
+  __syncthreads();
+  // head-local class of each row (0: not this head's), rank among this head's rows in row order (center_head.py:200-210)
+  for (int start = 0; start < m; start += TGT_THREADS) {
+    const int i = start + tid;
+    int local = 0;
+    if (i < m) {
+      const float c = g[i * bw + bw - 1];
+      const int gc = (c >= 1.f && c < (float)PCP_TGT_MAX_CLASSES) ? (int)c : 0;
+      local = hd.class_to_local[gc];
+    }
+    const int fg = local > 0 ? 1 : 0;
+    const unsigned long long bal = __ballot(fg);
+    const int lane = tid & 63, wv = tid >> 6;
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wv; ++w) off += wave_tot[w];
+    if (i < m) {
+      rank_of[i] = fg ? off + before : -1;
+      boxes[i].cls = local - 1;
+    }
+    __syncthreads();
+    if (tid == 0) { int t = 0; for (int w = 0; w < TGT_THREADS / 64; ++w) t += wave_tot[w]; base += t; }
+    __syncthreads();
+  }
+  for (int i = tid; i < m; i += TGT_THREADS) {
+    BoxT bx{0, 0, 0, 0, boxes[i].cls};
+    const int k = rank_of[i];
+    if (k >= 0 && k < d.k) {
+      const float *r = g + i * bw;
+      float cx = (r[0] - d.min_x) / d.voxel_x / d.stride;
+      float cy = (r[1] - d.min_y) / d.voxel_y / d.stride;
+      cx = fminf(fmaxf(cx, 0.f), (float)d.w - 0.5f);
+      cy = fminf(fmaxf(cy, 0.f), (float)d.h - 0.5f);
+      const int ix = (int)cx, iy = (int)cy;
+      const float dx = r[3] / d.voxel_x / d.stride;
+      const float dy = r[4] / d.voxel_y / d.stride;
+      if (dx > 0.f && dy > 0.f) {
+        float rad = gaussian_radius_f32(dx, dy, d.gaussian_overlap);
+        int ri = (rad == rad) ? (int)rad : 0;
+        if (ri < d.min_radius) ri = d.min_radius;
+        bx.valid = 1; bx.x = ix; bx.y = iy; bx.r = ri;
+        inds[k] = iy * d.w + ix;
+        mask[k] = 1;
+        float *t = tbox + (long long)k * tw;
+        t[0] = cx - (float)ix;
+        t[1] = cy - (float)iy;
+        t[2] = r[2];
+        t[3] = logf(r[3]);
+        t[4] = logf(r[4]);
+        t[5] = logf(r[5]);
+        t[6] = cosf(r[6]);
+        t[7] = sinf(r[6]);
+        if (bw == 10) { t[8] = r[7]; t[9] = r[8]; }
+        if (p.with_iou) {
+          // center_head.py:213-242: the prediction at the ground-truth centre's cell, decoded, against the ground-truth box
+          const float *px = hd.head + (((long long)b * d.h + iy) * d.w + ix) * hd.ld;
+          const float pxw = ((float)ix + px[hd.ch_center]) * d.stride * d.voxel_x + d.min_x;
+          const float pyw = ((float)iy + px[hd.ch_center + 1]) * d.stride * d.voxel_y + d.min_y;
+          const float ang = atan2f(px[hd.ch_rot + 1], px[hd.ch_rot]);
+          float ra[4], rb[4];
+          aa_rect(pxw, pyw, expf(px[hd.ch_dim]), expf(px[hd.ch_dim + 1]), ang, ra);
+          aa_rect(r[0], r[1], r[3], r[4], r[6], rb);
+          t[tw - 1] = 2.0f * aa_iou(ra, rb) - 1.f;
+        }
+      }
+    }
+    boxes[i] = bx;
+  }
+  __syncthreads();
+  int *hm = reinterpret_cast<int *>(heat);
+  for (int i = 0; i < m; ++i) {
+    const BoxT bx = boxes[i];
+    if (!bx.valid) continue;
+    const int r = bx.r;
+    const int left = min(bx.x, r), right = min(d.w - bx.x, r + 1);
+    const int top = min(bx.y, r), bottom = min(d.h - bx.y, r + 1);
+    const int ww = left + right, hh = top + bottom;
+    if (ww <= 0 || hh <= 0) continue;
+    const double sigma = (double)(2 * r + 1) / 6.0;
+    const double inv = 1.0 / (2.0 * sigma * sigma);
+    for (int q = tid; q < ww * hh; q += TGT_THREADS) {
+      const int py = q / ww - top, px = q % ww - left;
+      const float v = (float)exp(-(double)(px * px + py * py) * inv);
+      atomicMax(hm + ((long long)(bx.y + py) * d.w + (bx.x + px)) * ncls + bx.cls, __float_as_int(v));
+    }
+  }
+}
+
+// ---- losses of all heads ---------------------------------------------------------------------------------------------------------
+// workspace (double) per head: [LX_BLOCKS][3] focal partials (pos, neg, num_pos) | [1 + 16] mask sum and per-code L1 sums | [2] num_pos, num
+constexpr int LX_BLOCKS = 64;
+constexpr int LX_PER_HEAD = LX_BLOCKS * 3 + 1 + PCP_HEADLOSS_MAX_CODES + 2;
+
+struct LossExtParams {
+  pcp_headloss_ext_t d;
+  pcp_headloss_head_t heads[PCP_DET_MAX_HEADS];
+  int n_heads;
+  float grad_scale;
+};
+
+// grid (LX_BLOCKS + 1, heads): blocks 0 .. LX_BLOCKS-1 reduce the focal terms of their head, block LX_BLOCKS its L1 sums; every block
+// writes its own partial (no atomics), the finalize kernel adds them in block order
+__global__ __launch_bounds__(256) void k_lossx_reduce(LossExtParams p, double *__restrict__ ws) {
+  __shared__ double sh[4];
+  const pcp_headloss_ext_t &d = p.d;
+  const pcp_headloss_head_t &hd = p.heads[blockIdx.y];
+  double *w = ws + (long long)blockIdx.y * LX_PER_HEAD;
+  if (blockIdx.x < LX_BLOCKS) {
+    const long long total = (long long)d.batch * d.h * d.w * hd.num_class;
+    double pos = 0, neg = 0, npos = 0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)LX_BLOCKS * blockDim.x) {
+      const int c = (int)(t % hd.num_class);
+      const long long pix = t / hd.num_class;
+      int inside;
+      const float q = clamped_sigmoid(hd.head[pix * hd.ld + hd.ch_hm + c], &inside);
+      const float gtv = hd.heatmap[t];
+      if (gtv == 1.f) {
+        pos += (double)(logf(q) * (1.f - q) * (1.f - q));
+        npos += 1.0;
+      } else if (gtv < 1.f) {
+        const float wt = (1.f - gtv) * (1.f - gtv);
+        neg += (double)(logf(1.f - q) * q * q * (wt * wt));
+      }
+    }
+    double s = block_sum(pos, sh);
+    if (threadIdx.x == 0) w[blockIdx.x * 3 + 0] = s;
+    s = block_sum(neg, sh);
+    if (threadIdx.x == 0) w[blockIdx.x * 3 + 1] = s;
+    s = block_sum(npos, sh);
+    if (threadIdx.x == 0) w[blockIdx.x * 3 + 2] = s;
+    return;
+  }
+  double *wr = w + LX_BLOCKS * 3;
+  const int total = d.batch * d.k;
+  double s[PCP_HEADLOSS_MAX_CODES], num = 0;
+#pragma unroll
+  for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) s[j] = 0;
+  for (int t = threadIdx.x; t < total; t += blockDim.x) {
+    if (!hd.mask[t]) continue;
+    num += 1.0;
+    const int b = t / d.k;
+    const float *px = hd.head + ((long long)b * d.h * d.w + hd.inds[t]) * hd.ld;
+    const float *tv = hd.target_boxes + (long long)t * hd.tb_width;
+#pragma unroll
+    for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j)
+      if (j < hd.n_codes) s[j] += (double)fabsf(px[hd.reg_ch[j]] - tv[j]);
+  }
+  double r = block_sum(num, sh);
+  if (threadIdx.x == 0) wr[0] = r;
+#pragma unroll
+  for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) {
+    r = block_sum(s[j], sh);
+    if (threadIdx.x == 0) wr[1 + j] = r;
+  }
+}
+
+// one thread per head, then thread 0 adds the heads in order
+__global__ void k_lossx_finalize(LossExtParams p, double *__restrict__ ws, float *__restrict__ losses, float *__restrict__ total) {
+  __shared__ double sums[PCP_DET_MAX_HEADS];
+  const int h = threadIdx.x;
+  if (h < p.n_heads) {
+    const pcp_headloss_ext_t &d = p.d;
+    double *w = ws + (long long)h * LX_PER_HEAD;
+    double pos = 0, neg = 0, npos = 0;
+    for (int i = 0; i < LX_BLOCKS; ++i) { pos += w[i * 3]; neg += w[i * 3 + 1]; npos += w[i * 3 + 2]; }
+    const double *wr = w + LX_BLOCKS * 3;
+    const double hm = (npos == 0.0 ? -neg : -(pos + neg) / npos) * (double)d.cls_weight;
+    const double num = wr[0] < 1.0 ? 1.0 : wr[0];
+    double loc = 0;
+    for (int j = 0; j < p.heads[h].n_codes; ++j) loc += (double)(float)(wr[1 + j] / num) * (double)d.code_weights[j];
+    loc *= (double)d.loc_weight;
+    losses[h * 4 + 0] = (float)hm;
+    losses[h * 4 + 1] = (float)loc;
+    losses[h * 4 + 2] = (float)(hm + loc);
+    losses[h * 4 + 3] = (float)npos;
+    w[LX_PER_HEAD - 2] = npos;
+    w[LX_PER_HEAD - 1] = wr[0];
+    sums[h] = (double)(float)(hm + loc);
+  }
+  __syncthreads();
+  if (h == 0) {
+    float t = 0.f;                                            // the reference adds the float32 per-head losses in head order (:295)
+    for (int i = 0; i < p.n_heads; ++i) t += (float)sums[i];
+    total[0] = t;
+  }
+}
+
+// grid (blocks, heads): k_focal_grad per head
+__global__ __launch_bounds__(256) void k_lossx_focal_grad(LossExtParams p, const double *__restrict__ ws) {
+  const pcp_headloss_ext_t &d = p.d;
+  const pcp_headloss_head_t &hd = p.heads[blockIdx.y];
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long total = (long long)d.batch * d.h * d.w * hd.ld_d;
+  if (t >= total) return;
+  const int ch = (int)(t % hd.ld_d);
+  const long long pix = t / hd.ld_d;
+  float gval = 0.f;
+  const int c = ch - hd.ch_hm;
+  if (c >= 0 && c < hd.num_class) {
+    const double npos = ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 2];
+    const float coef = -d.cls_weight * p.grad_scale / (float)(npos == 0.0 ? 1.0 : npos);
+    int inside;
+    const float q = clamped_sigmoid(hd.head[pix * hd.ld + ch], &inside);
+    const float gtv = hd.heatmap[pix * hd.num_class + c];
+    float dldp = 0.f;
+    if (gtv == 1.f) {
+      if (npos != 0.0) dldp = (1.f - q) * (1.f - q) / q - 2.f * (1.f - q) * logf(q);
+    } else if (gtv < 1.f) {
+      const float wt = (1.f - gtv) * (1.f - gtv);
+      dldp = (wt * wt) * (-(q * q) / (1.f - q) + 2.f * q * logf(1.f - q));
+    }
+    gval = inside ? coef * dldp * q * (1.f - q) : 0.f;
+  }
+  hd.dhead[t] = gval;
+}
+
+// grid (blocks, heads), after k_lossx_focal_grad (the regression channels are zero).  Slots of one frame that share a cell: the first of
+// them adds all their terms in slot order and stores once -- no atomics, one fixed order.
+__global__ __launch_bounds__(256) void k_lossx_reg_grad(LossExtParams p, const double *__restrict__ ws) {
+  const pcp_headloss_ext_t &d = p.d;
+  const pcp_headloss_head_t &hd = p.heads[blockIdx.y];
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= d.batch * d.k || !hd.mask[t]) return;
+  const int b = t / d.k, k0 = t - b * d.k;
+  const int *inds = hd.inds + b * d.k, *mask = hd.mask + b * d.k;
+  const int cell = inds[k0];
+  for (int k = 0; k < k0; ++k)
+    if (mask[k] && inds[k] == cell) return;
+  const double numd = ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 1];
+  const double num = numd < 1.0 ? 1.0 : numd;
+  const long long pix = (long long)b * d.h * d.w + cell;
+  float acc[PCP_HEADLOSS_MAX_CODES];
+#pragma unroll
+  for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) acc[j] = 0.f;
+  for (int k = k0; k < d.k; ++k) {
+    if (!mask[k] || inds[k] != cell) continue;
+    const float *tv = hd.target_boxes + ((long long)b * d.k + k) * hd.tb_width;
+#pragma unroll
+    for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) {
+      if (j >= hd.n_codes) continue;
+      const float diff = hd.head[pix * hd.ld + hd.reg_ch[j]] - tv[j];
+      const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+      if (sg != 0.f) acc[j] += sg * d.loc_weight * d.code_weights[j] * p.grad_scale / (float)num;
+    }
+  }
+  // two codes never share a channel (checked on the host), so these are plain stores
+#pragma unroll
+  for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j)
+    if (j < hd.n_codes) hd.dhead[pix * hd.ld_d + hd.reg_ch[j]] = acc[j];
+}
+
+}  // namespace
+
 extern "C" {
+
+int pcp_centerhead_targets_ext(const pcp_target_t *d, const pcp_target_head_t *heads, int32_t n_heads, const float *gt_boxes,
+                               int32_t max_boxes, int32_t box_width, int32_t with_iou, void *stream) {
+  if (!d || !heads || !gt_boxes || n_heads <= 0 || n_heads > PCP_DET_MAX_HEADS) return PCP_ERR_ARG;
+  if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->k <= 0 || max_boxes < 0) return PCP_ERR_ARG;
+  if (box_width != 8 && box_width != 10) return PCP_ERR_ARG;
+  if (max_boxes > TGT_MAX_BOXES) return PCP_ERR_UNSUPPORTED;
+  TgtExtParams p;
+  p.d = *d;
+  p.bw = box_width;
+  p.with_iou = with_iou ? 1 : 0;
+  p.tw = 8 + (box_width == 10 ? 2 : 0) + p.with_iou;
+  for (int i = 0; i < n_heads; ++i) {
+    const pcp_target_head_t &h = heads[i];
+    if (!h.heatmap || !h.target_boxes || !h.inds || !h.mask || h.num_class <= 0) return PCP_ERR_ARG;
+    if (h.class_to_local[0] != 0) return PCP_ERR_ARG;
+    for (int c = 0; c < PCP_TGT_MAX_CLASSES; ++c)
+      if (h.class_to_local[c] < 0 || h.class_to_local[c] > h.num_class) return PCP_ERR_ARG;
+    if (p.with_iou) {
+      if (!h.head || h.ld <= 0 || h.ch_center < 0 || h.ch_z < 0 || h.ch_dim < 0 || h.ch_rot < 0) return PCP_ERR_ARG;
+      if (h.ch_center + 2 > h.ld || h.ch_z >= h.ld || h.ch_dim + 3 > h.ld || h.ch_rot + 2 > h.ld) return PCP_ERR_ARG;
+    }
+    p.heads[i] = h;
+  }
+  hipLaunchKernelGGL(k_targets_ext, dim3(n_heads * d->batch), dim3(TGT_THREADS), 0, (hipStream_t)stream, p, gt_boxes, max_boxes);
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
+
+size_t pcp_centerhead_loss_ext_workspace_bytes(int32_t n_heads) {
+  return (size_t)(n_heads > 0 ? n_heads : 0) * LX_PER_HEAD * sizeof(double);
+}
+
+int pcp_centerhead_loss_ext(const pcp_headloss_ext_t *d, const pcp_headloss_head_t *heads, int32_t n_heads, float grad_scale,
+                            void *workspace, size_t workspace_bytes, float *losses, float *total, void *stream) {
+  if (!d || !heads || !workspace || !losses || !total || n_heads <= 0 || n_heads > PCP_DET_MAX_HEADS) return PCP_ERR_ARG;
+  if (d->batch <= 0 || d->h <= 0 || d->w <= 0 || d->k <= 0) return PCP_ERR_ARG;
+  if (workspace_bytes < pcp_centerhead_loss_ext_workspace_bytes(n_heads)) return PCP_ERR_WORKSPACE;
+  LossExtParams p;
+  p.d = *d;
+  p.n_heads = n_heads;
+  p.grad_scale = grad_scale;
+  const bool with_grad = heads[0].dhead != nullptr;
+  long long max_total = 0;
+  for (int i = 0; i < n_heads; ++i) {
+    const pcp_headloss_head_t &h = heads[i];
+    if (!h.head || !h.heatmap || !h.target_boxes || !h.inds || !h.mask) return PCP_ERR_ARG;
+    if ((h.dhead != nullptr) != with_grad) return PCP_ERR_ARG;
+    if (h.ld <= 0 || h.num_class <= 0 || h.ch_hm < 0 || h.ch_hm + h.num_class > h.ld) return PCP_ERR_ARG;
+    if (h.n_codes <= 0 || h.n_codes > PCP_HEADLOSS_MAX_CODES || h.tb_width != h.n_codes) return PCP_ERR_ARG;
+    if (with_grad && (h.ld_d <= 0 || h.ch_hm + h.num_class > h.ld_d)) return PCP_ERR_ARG;
+    for (int j = 0; j < h.n_codes; ++j) {
+      if (h.reg_ch[j] < 0 || h.reg_ch[j] >= h.ld || (with_grad && h.reg_ch[j] >= h.ld_d)) return PCP_ERR_ARG;
+      if (h.reg_ch[j] >= h.ch_hm && h.reg_ch[j] < h.ch_hm + h.num_class) return PCP_ERR_ARG;
+      for (int i2 = 0; i2 < j; ++i2)
+        if (h.reg_ch[i2] == h.reg_ch[j]) return PCP_ERR_ARG;
+    }
+    if (with_grad) {
+      const long long t = (long long)d->batch * d->h * d->w * h.ld_d;
+      if (t > max_total) max_total = t;
+    }
+    p.heads[i] = h;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  double *ws = (double *)workspace;
+  hipLaunchKernelGGL(k_lossx_reduce, dim3(LX_BLOCKS + 1, n_heads), dim3(256), 0, s, p, ws);
+  hipLaunchKernelGGL(k_lossx_finalize, dim3(1), dim3(64), 0, s, p, ws, losses, total);
+  if (with_grad) {
+    const int nk = d->batch * d->k;
+    hipLaunchKernelGGL(k_lossx_focal_grad, dim3((unsigned)((max_total + 255) / 256), n_heads), dim3(256), 0, s, p, ws);
+    hipLaunchKernelGGL(k_lossx_reg_grad, dim3((nk + 255) / 256, n_heads), dim3(256), 0, s, p, ws);
+  }
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
 
 int pcp_centerhead_targets(const pcp_target_t *d, const float *gt_boxes, int32_t max_boxes, float *heatmap, float *target_boxes,
                            int32_t *inds, int32_t *mask, void *stream) {

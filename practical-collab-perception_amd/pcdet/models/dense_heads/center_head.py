@@ -50,6 +50,30 @@ class SeparateHead(nn.Module):
             self.__setattr__(cur_name, fc)
 
 
+def class_rewrite_is_inert(class_names, class_names_each_head):
+    """The reference's assign_targets writes every selected row's class back into gt_boxes IN PLACE as the index inside the head
+    (temp_box[-1] = cur_class_names.index(name) + 1, reference :203-204), so later heads read rewritten classes: a value v names
+    class_names[v - 1] to them.  The rewrite changes nothing iff no later head holds class_names[v - 1] for a v that an earlier head can
+    write (v = 1 .. its number of classes); the device kernel reads gt_boxes only, which is the same thing exactly then."""
+    for i, names in enumerate(class_names_each_head):
+        for v in range(1, len(names) + 1):
+            if v - 1 >= len(class_names):
+                continue
+            alias = class_names[v - 1]
+            if any(alias in later for later in class_names_each_head[i + 1:]):
+                return False
+    return True
+
+
+def check_class_rewrite_is_inert(class_names, class_names_each_head):
+    if not class_rewrite_is_inert(class_names, class_names_each_head):
+        raise NotImplementedError(
+            'CLASS_NAMES_EACH_HEAD=%s: the reference rewrites the class column of gt_boxes in place per head (center_head.py:203-204), and '
+            'with this layout a later head would select rows by the rewritten value (a head writes 1 .. its class count, which a later '
+            'head reads as CLASS_NAMES[v - 1]).  The target kernel reads gt_boxes only, so it would not assign what the reference assigns; '
+            'order the heads so that no later head holds one of the first classes of CLASS_NAMES' % (class_names_each_head,))
+
+
 class CenterHead(PackedModule):
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range, voxel_size,
                  predict_boxes_when_training=True):
@@ -251,18 +275,41 @@ class CenterHead(PackedModule):
         return data_dict
 
     # ---- training (reference :104-300, 377-392) -------------------------------------------------------------------------
-    def _head_channels(self):
-        names = self.head_names[0]
-        outs = [self.heads_list[0].sep_head_dict[n]['out_channels'] for n in names]
+    def _head_channels(self, idx=0):
+        names = self.head_names[idx]
+        outs = [self.heads_list[idx].sep_head_dict[n]['out_channels'] for n in names]
         offs = np.concatenate([[0], np.cumsum(outs)]).astype(int)
         off = {n: int(o) for n, o in zip(names, offs[:-1])}
         order = list(self.separate_head_cfg.HEAD_ORDER)
         reg = []
         for n in order:
             reg += [off[n] + j for j in range(outs[names.index(n)])]
-        if len(reg) != 8 or 'hm' not in off:
-            raise NotImplementedError('loss kernel covers the 8 regression codes center/center_z/dim/rot + hm (all five configs)')
+        if 'hm' not in off:
+            raise NotImplementedError('the loss kernels need the hm branch')
         return off, outs, reg, names
+
+    def _ext_train(self, gt_width):
+        """the one-head, 8-code head on 8-column boxes (the five V2X-Sim configs) keeps pcp_centerhead_targets / pcp_centerhead_loss;
+        several heads, vel / iou codes or velocity columns run the _ext entry points"""
+        return len(self.heads_list) != 1 or len(self._head_channels(0)[2]) != 8 or gt_width != 8
+
+    def _check_code_widths(self, gt_width):
+        """column j of the HEAD_ORDER concatenation pairs with column j of target_boxes (reference :286-292) and with code_weights[j]:
+        settle the widths before anything is launched"""
+        from pcp_amd import lib
+        from pcp_amd import train_ops as tops
+        tw = tops.centerhead_target_width(gt_width, 'iou' in self.separate_head_cfg.HEAD_ORDER)
+        n_weights = len(self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS['code_weights'])
+        for idx in range(len(self.heads_list)):
+            n_codes = len(self._head_channels(idx)[2])
+            if n_codes != tw:
+                raise ValueError('head %d: HEAD_ORDER=%s concatenates %d prediction channels, but gt_boxes of width %d give target_boxes of '
+                                 '%d columns' % (idx, list(self.separate_head_cfg.HEAD_ORDER), n_codes, gt_width, tw))
+            if n_codes != n_weights:
+                raise ValueError('head %d: LOSS_WEIGHTS.code_weights has %d entries but HEAD_ORDER concatenates %d prediction channels'
+                                 % (idx, n_weights, n_codes))
+            if n_codes > lib.HEADLOSS_MAX_CODES:
+                raise ValueError('%d regression codes, the loss kernel takes at most %d' % (n_codes, lib.HEADLOSS_MAX_CODES))
 
     def _forward_train(self, data_dict):
         from pcp_amd import lib
@@ -271,22 +318,28 @@ class CenterHead(PackedModule):
         from ..train_path import HeadTrain
         if self.predict_boxes_when_training:
             raise NotImplementedError('predict_boxes_when_training needs a RoI head (not on the PointPillars path)')
+        gt = data_dict['gt_boxes']
+        if gt.shape[-1] not in (8, 10):
+            raise NotImplementedError('gt_boxes rows have 8 columns, or 10 with velocity (got %d)' % gt.shape[-1])
+        ext = self._ext_train(gt.shape[-1])
+        if ext:
+            check_class_rewrite_is_inert(self.class_names, self.class_names_each_head)
+            self._check_code_widths(gt.shape[-1])
         if getattr(self, '_pcp_train', None) is None:
             self._pcp_train = HeadTrain(self)
         self.invalidate_packed()
         x = ops.as_nhwc(data_dict['spatial_features_2d'])
+        if gt.dtype != torch.float32 or not gt.is_contiguous():
+            gt = gt.float().contiguous()
+        ta = self.model_cfg.TARGET_ASSIGNER_CONFIG
+        if ext:
+            return self._forward_train_ext(data_dict, x, gt, ta)
         buf = self._pcp_train.forward(Act(x))
         B, H, W, ld = buf.shape
         off, outs, reg, names = self._head_channels()
         view = ops.nchw_view(buf)
         offs = np.concatenate([[0], np.cumsum(outs)]).astype(int)
         self.forward_ret_dict['pred_dicts'] = [{n: view[:, int(offs[i]):int(offs[i + 1])] for i, n in enumerate(names)}]
-        ta = self.model_cfg.TARGET_ASSIGNER_CONFIG
-        gt = data_dict['gt_boxes']
-        if gt.dtype != torch.float32 or not gt.is_contiguous():
-            gt = gt.float().contiguous()
-        if gt.shape[-1] != 8:
-            raise NotImplementedError('gt_boxes with velocity columns are not used by the V2X-Sim configs')
         ncls = outs[names.index('hm')]
         tdesc = lib.Target(B, H, W, ncls, int(ta.NUM_MAX_OBJS), float(ta.FEATURE_MAP_STRIDE), float(np.float32(self.voxel_size[0])),
                            float(np.float32(self.voxel_size[1])), float(self.point_cloud_range[0]), float(self.point_cloud_range[1]),
@@ -298,15 +351,52 @@ class CenterHead(PackedModule):
         train_tape(data_dict).append(('dense_head', self._backward_from_loss))
         return data_dict
 
+    def _forward_train_ext(self, data_dict, x, gt, ta):
+        """several heads / vel / iou (reference :168-268): head convs first (the IoU target reads them), then ONE targets launch"""
+        from pcp_amd import lib
+        from pcp_amd import train_ops as tops
+        from pcp_amd.train_layers import Act
+        bufs = self._pcp_train.forward_heads(Act(x))
+        B, H, W, _ = bufs[0].shape
+        with_iou = 'iou' in self.separate_head_cfg.HEAD_ORDER
+        n_global = len(self.class_names) + 1
+        heads, pred_dicts = [], []
+        for idx, buf in enumerate(bufs):
+            off, outs, reg, names = self._head_channels(idx)
+            offs = np.concatenate([[0], np.cumsum(outs)]).astype(int)
+            view = ops.nchw_view(buf)
+            pred_dicts.append({n: view[:, int(offs[i]):int(offs[i + 1])] for i, n in enumerate(names)})
+            table = [0] * n_global
+            for local, name in enumerate(self.class_names_each_head[idx]):
+                table[self.class_names.index(name) + 1] = local + 1
+            h = dict(num_class=outs[names.index('hm')], class_to_local=table, off=off, reg=reg)
+            if with_iou:
+                for need in ('center', 'dim', 'rot'):
+                    assert need in off, 'the IoU target decodes the %s branch' % need
+                h.update(head=buf, ch_center=off['center'], ch_z=off.get('center_z', 0), ch_dim=off['dim'], ch_rot=off['rot'])
+            heads.append(h)
+        self.forward_ret_dict['pred_dicts'] = pred_dicts
+        tdesc = lib.Target(B, H, W, 0, int(ta.NUM_MAX_OBJS), float(ta.FEATURE_MAP_STRIDE), float(np.float32(self.voxel_size[0])),
+                           float(np.float32(self.voxel_size[1])), float(self.point_cloud_range[0]), float(self.point_cloud_range[1]),
+                           float(ta.GAUSSIAN_OVERLAP), int(ta.MIN_RADIUS))
+        targets = tops.centerhead_targets_ext(gt, tdesc, heads, with_iou=with_iou)
+        self.forward_ret_dict['target_dicts'] = {'heatmaps': [ops.nchw_view(t[0]) for t in targets], 'target_boxes': [t[1] for t in targets],
+                                                 'inds': [t[2].long() for t in targets], 'masks': [t[3].long() for t in targets]}
+        self._train_state = dict(ext=True, bufs=bufs, heads=heads, targets=targets)
+        train_tape(data_dict).append(('dense_head', self._backward_from_loss))
+        return data_dict
+
     def get_loss(self, read_back=True):
         """focal + L1 losses AND dL/d(head maps) in one pass (the gradient is consumed by loss.backward()).
         read_back=False: the tb_dict values stay device scalars (CenterPoint.eager_backward reads them after queuing the backward)."""
         from pcp_amd import lib
         from pcp_amd import train_ops as tops
         st = self._train_state
+        lw = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
+        if st.get('ext'):
+            return self._get_loss_ext(st, lw, read_back)
         buf = st['buf']
         B, H, W, ld = buf.shape
-        lw = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
         d = lib.HeadLoss()
         d.batch, d.h, d.w, d.ld, d.ld_d = B, H, W, ld, ld
         d.num_class, d.ch_hm = st['ncls'], st['off']['hm']
@@ -322,5 +412,35 @@ class CenterHead(PackedModule):
         tb_dict = {'hm_loss_head_0': vals[0], 'loc_loss_head_0': vals[1], 'rpn_loss': vals[2]}
         return losses[2], tb_dict
 
+    def _get_loss_ext(self, st, lw, read_back):
+        """reference :274-300 for every head in one call; one host read (the (H, 4) losses and the total share one tensor)"""
+        from pcp_amd import lib
+        from pcp_amd import train_ops as tops
+        B, H, W, _ = st['bufs'][0].shape
+        weights = [float(v) for v in lw['code_weights']]                 # widths were settled in _check_code_widths
+        d = lib.HeadLossExt()
+        d.batch, d.h, d.w, d.k = B, H, W, int(self.model_cfg.TARGET_ASSIGNER_CONFIG.NUM_MAX_OBJS)
+        d.cls_weight, d.loc_weight = float(lw['cls_weight']), float(lw['loc_weight'])
+        for j, v in enumerate(weights):
+            d.code_weights[j] = v
+        heads = [dict(head=buf, heat=t[0], tb=t[1], inds=t[2], mask=t[3], ch_hm=h['off']['hm'], num_class=h['num_class'], reg_ch=h['reg'])
+                 for buf, h, t in zip(st['bufs'], st['heads'], st['targets'])]
+        losses, total, dheads = tops.centerhead_loss_ext(d, heads, with_grad=True)
+        st['dheads'] = dheads
+        n = len(heads)
+        if read_back:
+            flat = torch.cat([losses.reshape(-1), total]).tolist()
+            vals, tot = [flat[4 * i:4 * i + 4] for i in range(n)], flat[4 * n]
+        else:
+            vals, tot = losses, total[0]
+        tb_dict = {}
+        for i in range(n):
+            tb_dict['hm_loss_head_%d' % i] = vals[i][0]
+            tb_dict['loc_loss_head_%d' % i] = vals[i][1]
+        tb_dict['rpn_loss'] = tot
+        return total[0], tb_dict
+
     def _backward_from_loss(self, _unused):
+        if self._train_state.get('ext'):
+            return self._pcp_train.backward_heads(self._train_state['dheads'])
         return self._pcp_train.backward(self._train_state['dhead'])

@@ -294,22 +294,18 @@ class FusionTrain:
 # CenterHead
 # ---------------------------------------------------------------------------------------------------------------------
 
-class HeadTrain:
-    def __init__(self, head):
-        self.m = head
-        if len(head.heads_list) != 1:
-            raise NotImplementedError('training kernels cover one detection head (all five configs)')
-        sh = head.shared_conv
-        self.shared = ConvBNAct(sh[0], sh[1], relu=True, name='shared_conv')
-        self.names = head.head_names[0]
-        h = head.heads_list[0]
+class _HeadBranches:
+    """the branches of ONE SeparateHead behind the shared conv: stage 1 (every branch's conv+BN+ReLU), stage 2 (the grouped final convs)"""
+
+    def __init__(self, h, names, c, tag=''):
+        self.names = names
         self.seqs = [getattr(h, n) for n in self.names]
         if not all(len(s) == 2 for s in self.seqs):
             raise NotImplementedError('training kernels cover NUM_HM_CONV = num_conv = 2 (all five configs)')
-        self.stage1 = [ConvBNAct(s[0][0], s[0][1], relu=True, name='%s.0' % n) for s, n in zip(self.seqs, self.names)]
+        self.stage1 = [ConvBNAct(s[0][0], s[0][1], relu=True, name='%s%s.0' % (tag, n)) for s, n in zip(self.seqs, self.names)]
         self.outs = [s[1].weight.shape[0] for s in self.seqs]
         self.offs = [int(v) for v in np.concatenate([[0], np.cumsum(self.outs)])]
-        self.c = sh[0].weight.shape[0]
+        self.c = c
         self.ld = max(16, (self.offs[-1] + 3) // 4 * 4)
         self._step = -1
         self.saved = None
@@ -335,9 +331,8 @@ class HeadTrain:
         self._step = tl.StepClock.step
         return self._forms
 
-    def forward(self, x):
-        """x: Act (B, H, W, 384).  Returns the raw head-map buffer (B, H, W, ld)."""
-        s = self.shared.forward(x)
+    def forward(self, s):
+        """s: Act, the shared activation.  Returns the raw head-map buffer (B, H, W, ld)."""
         B, H, W, _ = s.t.shape
         dev = s.t.device
         n, c = len(self.seqs), self.c
@@ -347,11 +342,11 @@ class HeadTrain:
         f = self._stage2_forms()
         buf = torch.zeros((B, H, W, self.ld), dtype=torch.float32, device=dev)
         ops.conv3x3_grouped_small(mid, f['grouped'][0], f['grouped'][1], self.offs, buf)
-        self.saved = dict(mid=mid, s=s)
+        self.saved = dict(mid=mid, shape=tuple(s.t.shape))
         return buf
 
     def backward(self, dhead):
-        """dhead: (B, H, W, ld) gradient of the raw maps.  Returns Act gradient of the head input (B, H, W, 384)."""
+        """dhead: (B, H, W, ld) gradient of the raw maps.  Returns the float32 gradient of the shared activation (B, H, W, c)."""
         sv = self.saved
         n, c = len(self.seqs), self.c
         dev = dhead.device
@@ -373,9 +368,46 @@ class HeadTrain:
         dmid = ops.conv3x3(dhead, w, b, self.ld, n * c, cp, stride=1, relu=False)
         for i, layer in enumerate(self.stage1):
             layer.backward(Act(dmid, c * i, c), need_dx=False)                  # BN+ReLU backward in place, wgrad
-        ds = _empty(tuple(sv['s'].t.shape), dev)
+        ds = _empty(sv['shape'], dev)
         ConvBNAct._run3x3(f['bw1'], dmid, n * c, c, 1, ds, 0, 0)
+        return ds
+
+
+class HeadTrain:
+    """shared conv -> one _HeadBranches per SeparateHead (center_head.py:75-96, 377-392).  One head (the five V2X-Sim configs): forward
+    returns its buffer and backward takes its gradient; several heads (the nuScenes head): lists, and the heads' gradients of the shared
+    activation are added in head order before the shared conv's backward."""
+
+    def __init__(self, head):
+        self.m = head
+        sh = head.shared_conv
+        self.shared = ConvBNAct(sh[0], sh[1], relu=True, name='shared_conv')
+        self.c = sh[0].weight.shape[0]
+        single = len(head.heads_list) == 1
+        self.heads = [_HeadBranches(h, names, self.c, tag='' if single else 'head%d.' % i)
+                      for i, (h, names) in enumerate(zip(head.heads_list, head.head_names))]
+        self.names, self.outs, self.offs, self.ld = self.heads[0].names, self.heads[0].outs, self.heads[0].offs, self.heads[0].ld
+
+    def forward_heads(self, x):
+        """x: Act (B, H, W, 384).  Returns the raw head-map buffers [(B, H, W, ld_h)]; the shared conv runs once."""
+        s = self.shared.forward(x)
+        return [h.forward(s) for h in self.heads]
+
+    def backward_heads(self, dheads):
+        """dheads: [(B, H, W, ld_h)] gradients of the raw maps.  Returns Act gradient of the head input (B, H, W, 384)."""
+        ds = None
+        for h, dh in zip(self.heads, dheads):
+            g = h.backward(dh)
+            ds = g if ds is None else ds.add_(g)
         return self.shared.backward(Act(ds))
+
+    def forward(self, x):
+        assert len(self.heads) == 1
+        return self.forward_heads(x)[0]
+
+    def backward(self, dhead):
+        assert len(self.heads) == 1
+        return self.backward_heads([dhead])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -116,6 +116,29 @@ class HeadLoss(ctypes.Structure):
                 ('reg_ch', c_i32 * 8), ('k', c_i32), ('cls_weight', c_f), ('loc_weight', c_f), ('code_weights', c_f * 8)]
 
 
+DET_MAX_HEADS = 8            # PCP_DET_MAX_HEADS: heads per call of the _ext entry points
+TGT_MAX_CLASSES = 32
+HEADLOSS_MAX_CODES = 16
+
+
+class TargetHead(ctypes.Structure):
+    """pcp_target_head_t: one head of pcp_centerhead_targets_ext"""
+    _fields_ = [('num_class', c_i32), ('class_to_local', c_i32 * TGT_MAX_CLASSES), ('heatmap', vp), ('target_boxes', vp), ('inds', vp),
+                ('mask', vp), ('head', vp), ('ld', c_i32), ('ch_center', c_i32), ('ch_z', c_i32), ('ch_dim', c_i32), ('ch_rot', c_i32)]
+
+
+class HeadLossHead(ctypes.Structure):
+    """pcp_headloss_head_t: one head of pcp_centerhead_loss_ext"""
+    _fields_ = [('head', vp), ('dhead', vp), ('heatmap', vp), ('target_boxes', vp), ('inds', vp), ('mask', vp), ('ld', c_i32),
+                ('ld_d', c_i32), ('ch_hm', c_i32), ('num_class', c_i32), ('n_codes', c_i32), ('reg_ch', c_i32 * HEADLOSS_MAX_CODES),
+                ('tb_width', c_i32)]
+
+
+class HeadLossExt(ctypes.Structure):
+    _fields_ = [('batch', c_i32), ('h', c_i32), ('w', c_i32), ('k', c_i32), ('cls_weight', c_f), ('loc_weight', c_f),
+                ('code_weights', c_f * HEADLOSS_MAX_CODES)]
+
+
 class AnchorAssign(ctypes.Structure):
     _fields_ = [('batch', c_i32), ('h', c_i32), ('w', c_i32), ('anchors_per_loc', c_i32), ('num_class', c_i32), ('num_groups', c_i32),
                 ('slot_group', c_i32 * 32), ('group_class', c_i32 * 8), ('matched', c_f * 8), ('unmatched', c_f * 8)]
@@ -255,6 +278,9 @@ SYMBOLS.update({
     'pcp_centerhead_targets': (c_i32, [ctypes.POINTER(Target), vp, c_i32, vp, vp, vp, vp, vp]),
     'pcp_loss_workspace_bytes': (c_sz, []),
     'pcp_centerhead_loss': (c_i32, [ctypes.POINTER(HeadLoss), vp, vp, vp, vp, vp, c_f, vp, vp, vp, vp]),
+    'pcp_centerhead_targets_ext': (c_i32, [ctypes.POINTER(Target), ctypes.POINTER(TargetHead), c_i32, vp, c_i32, c_i32, c_i32, vp]),
+    'pcp_centerhead_loss_ext_workspace_bytes': (c_sz, [c_i32]),
+    'pcp_centerhead_loss_ext': (c_i32, [ctypes.POINTER(HeadLossExt), ctypes.POINTER(HeadLossHead), c_i32, c_f, vp, c_sz, vp, vp, vp]),
     'pcp_anchor_assign_workspace_bytes': (c_sz, [ctypes.POINTER(AnchorAssign), c_i32]),
     'pcp_anchor_assign_targets': (c_i32, [ctypes.POINTER(AnchorAssign), vp, vp, c_i32, vp, c_sz, vp, vp, vp, vp]),
     'pcp_anchor_loss_workspace_bytes': (c_sz, [c_i32]),

@@ -418,6 +418,99 @@ def centerhead_loss(head, desc, heat, tb, inds, mask, dhead=None, grad_scale=1.0
     return losses
 
 
+def centerhead_target_width(box_width, with_iou):
+    """row width of target_boxes for gt rows of box_width columns: 8 codes, + 2 velocity columns, + 1 IoU column"""
+    if box_width not in (8, 10):
+        raise ValueError('gt_boxes rows have 8 columns, or 10 with velocity (got %d)' % box_width)
+    return 8 + (2 if box_width == 10 else 0) + (1 if with_iou else 0)
+
+
+def centerhead_targets_ext(gt_boxes, desc, heads, with_iou=False):
+    """pcp_centerhead_targets_ext: every (frame, head) in ONE launch.  gt_boxes (B, M, 8 | 10) float32 CUDA, read only.  desc: lib.Target
+    (its num_class is not read).  heads: list of dict(num_class, class_to_local (list indexed by the class column, [0] = 0) and, when
+    with_iou, head (B,H,W,ld) raw maps + ch_center / ch_z / ch_dim / ch_rot).  Returns per head (heatmap (B,H,W,ncls), target_boxes (B,K,T),
+    inds (B,K) i32, mask (B,K) i32)."""
+    _need_cuda(gt_boxes)
+    L = _lib.load()
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.dim() == 3 and gt_boxes.is_contiguous()
+    assert 0 < len(heads) <= _lib.DET_MAX_HEADS, 'pcp_centerhead_targets_ext takes 1 .. %d heads' % _lib.DET_MAX_HEADS
+    B, M, bw = gt_boxes.shape
+    assert B == desc.batch
+    tw = centerhead_target_width(bw, with_iou)
+    dev = gt_boxes.device
+    arr = (_lib.TargetHead * len(heads))()
+    out = []
+    for i, h in enumerate(heads):
+        table = [int(v) for v in h['class_to_local']]
+        if len(table) > _lib.TGT_MAX_CLASSES:
+            raise ValueError('pcp_centerhead_targets_ext takes class ids below %d' % _lib.TGT_MAX_CLASSES)
+        ncls = int(h['num_class'])
+        heat = torch.empty((B, desc.h, desc.w, ncls), dtype=torch.float32, device=dev)
+        tb = torch.empty((B, desc.k, tw), dtype=torch.float32, device=dev)
+        inds = torch.empty((B, desc.k), dtype=torch.int32, device=dev)
+        mask = torch.empty((B, desc.k), dtype=torch.int32, device=dev)
+        arr[i].num_class = ncls
+        for c, v in enumerate(table):
+            arr[i].class_to_local[c] = v
+        arr[i].heatmap, arr[i].target_boxes, arr[i].inds, arr[i].mask = _p(heat).value, _p(tb).value, _p(inds).value, _p(mask).value
+        if with_iou:
+            buf = h['head']
+            _need_cuda(buf)
+            assert buf.dtype == torch.float32 and buf.is_contiguous() and tuple(buf.shape[:3]) == (B, desc.h, desc.w)
+            arr[i].head, arr[i].ld = _p(buf).value, buf.shape[3]
+            arr[i].ch_center, arr[i].ch_z, arr[i].ch_dim, arr[i].ch_rot = (int(h['ch_center']), int(h['ch_z']), int(h['ch_dim']),
+                                                                          int(h['ch_rot']))
+        out.append((heat, tb, inds, mask))
+    check(L.pcp_centerhead_targets_ext(ctypes.byref(desc), arr, len(heads), _p(gt_boxes), M, bw, 1 if with_iou else 0, _stream()),
+          'pcp_centerhead_targets_ext')
+    return out
+
+
+_LOSS_EXT_WS = {}
+
+
+def centerhead_loss_ext(desc, heads, with_grad=True, grad_scale=1.0):
+    """pcp_centerhead_loss_ext: all heads in four launches.  desc: lib.HeadLossExt.  heads: list of dict(head (B,H,W,ld) raw maps, heat, tb,
+    inds, mask, ch_hm, num_class, reg_ch (channels in HEAD_ORDER concatenation order)).  A target_boxes width other than len(reg_ch) is a
+    ValueError (column j pairs with code j).  Returns (losses (H, 4) [hm, loc, hm + loc, num_pos], total (1,), [dhead per head] | None)."""
+    assert 0 < len(heads) <= _lib.DET_MAX_HEADS, 'pcp_centerhead_loss_ext takes 1 .. %d heads' % _lib.DET_MAX_HEADS
+    for i, h in enumerate(heads):
+        n = len(h['reg_ch'])
+        if n > _lib.HEADLOSS_MAX_CODES:
+            raise ValueError('head %d: %d regression codes, the loss kernel takes at most %d' % (i, n, _lib.HEADLOSS_MAX_CODES))
+        if h['tb'].shape[-1] != n:
+            raise ValueError('head %d: target_boxes has %d columns but HEAD_ORDER concatenates %d prediction channels'
+                             % (i, h['tb'].shape[-1], n))
+    L = _lib.load()
+    dev = heads[0]['head'].device
+    arr = (_lib.HeadLossHead * len(heads))()
+    dheads = []
+    for i, h in enumerate(heads):
+        buf = h['head']
+        _need_cuda(buf, h['heat'], h['tb'], h['inds'], h['mask'])
+        assert buf.dtype == torch.float32 and buf.is_contiguous() and tuple(buf.shape[:3]) == (desc.batch, desc.h, desc.w)
+        assert h['tb'].is_contiguous() and h['heat'].is_contiguous() and h['inds'].dtype == torch.int32 and h['mask'].dtype == torch.int32
+        dh = torch.empty_like(buf) if with_grad else None
+        dheads.append(dh)
+        arr[i].head, arr[i].dhead, arr[i].heatmap, arr[i].target_boxes = _p(buf).value, _p(dh).value, _p(h['heat']).value, _p(h['tb']).value
+        arr[i].inds, arr[i].mask = _p(h['inds']).value, _p(h['mask']).value
+        arr[i].ld = arr[i].ld_d = buf.shape[3]
+        arr[i].ch_hm, arr[i].num_class = int(h['ch_hm']), int(h['num_class'])
+        arr[i].n_codes = arr[i].tb_width = len(h['reg_ch'])
+        for j, ch in enumerate(h['reg_ch']):
+            arr[i].reg_ch[j] = int(ch)
+    need = L.pcp_centerhead_loss_ext_workspace_bytes(len(heads))
+    ws = _LOSS_EXT_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = torch.zeros(L.pcp_centerhead_loss_ext_workspace_bytes(_lib.DET_MAX_HEADS), dtype=torch.uint8, device=dev)
+        _LOSS_EXT_WS[dev] = ws
+    out = torch.empty(len(heads) * 4 + 1, dtype=torch.float32, device=dev)
+    losses, total = out[:len(heads) * 4].view(len(heads), 4), out[len(heads) * 4:]
+    check(L.pcp_centerhead_loss_ext(ctypes.byref(desc), arr, len(heads), float(grad_scale), _p(ws), ws.numel(), _p(losses), _p(total),
+                                    _stream()), 'pcp_centerhead_loss_ext')
+    return losses, total, (dheads if with_grad else None)
+
+
 _ANCHOR_WS = {}
 
 
