@@ -69,11 +69,7 @@ class _PackedBottleneck:
         self.planes = blk.conv3.out_channels
         wa, ba = _fold(blk.conv1_a, blk.bn1_a, out_axis=0)
         wb, bb = _fold(blk.conv1_b, blk.bn1_b, out_axis=0)
-        self.conv1 = PackedConv()
-        c1 = self.conv1
-        c1.kind, c1.relu, c1.stride, c1.cin, c1.cout = 'plain', True, 1, blk.conv1_a.in_channels, 2 * self.gw
-        c1.w, c1.b, c1.cout_pad = pack.pack_plain(torch.cat([wa, wb], 0), torch.cat([ba, bb], 0))
-        c1.wino = c1.b3 = c1.w4 = c1.w4f = c1.w4h = c1.w4c = c1.mp = None
+        self.conv1 = PackedConv('plain', blk.conv1_a.in_channels, 2 * self.gw, True, pack.pack_plain(torch.cat([wa, wb], 0), torch.cat([ba, bb], 0)))
         self.k1 = pack_conv_module(blk.k1[0], blk.k1[1], relu=True)
         self.k2 = pack_conv_module(blk.scconv.k2[1], blk.scconv.k2[2], relu=False)
         self.k3 = pack_conv_module(blk.scconv.k3[0], blk.scconv.k3[1], relu=False)

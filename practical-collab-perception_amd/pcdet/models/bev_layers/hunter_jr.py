@@ -71,11 +71,7 @@ def _pack_linear(linear, bn, relu):
                             conv_bias=linear.bias.detach().float() if linear.bias is not None else None)
     else:
         b = linear.bias.detach().float() if linear.bias is not None else torch.zeros(w.shape[0], device=w.device)
-    pc = PackedConv()
-    pc.kind, pc.relu, pc.stride, pc.wino = 'plain', relu, 1, None
-    pc.cin, pc.cout = w.shape[1], w.shape[0]
-    pc.w, pc.b, pc.cout_pad = pack.pack_plain(w, b)
-    return pc
+    return PackedConv('plain', w.shape[1], w.shape[0], relu, pack.pack_plain(w, b))
 
 
 class HunterJr(PackedModule):
@@ -108,10 +104,7 @@ class HunterJr(PackedModule):
         mlp = [_pack_linear(lf[i], lf[i + 1], relu=True) for i in range(0, len(lf), 3)]
         heads_w = torch.cat([ph.seg[0].weight, ph.reg_flow3d[0].weight, ph.instance_embedding[0].weight], 0).detach().float()
         heads_b = torch.cat([ph.seg[0].bias, ph.reg_flow3d[0].bias, ph.instance_embedding[0].bias], 0).detach().float()
-        heads = PackedConv()
-        heads.kind, heads.relu, heads.stride, heads.wino = 'plain', False, 1, None
-        heads.cin, heads.cout = heads_w.shape[1], heads_w.shape[0]
-        heads.w, heads.b, heads.cout_pad = pack.pack_plain(heads_w, heads_b)
+        heads = PackedConv('plain', heads_w.shape[1], heads_w.shape[0], False, pack.pack_plain(heads_w, heads_b))
         fused = None
         if len(lf) == 6 and heads_w.shape == (8, 384) and lf[0].weight.shape == (32, 384):
             # plain row-major folded weights for the fused point-head kernel

@@ -290,22 +290,31 @@ def _chan_ptr(t, ch_off):
     return ctypes.c_void_p(t.data_ptr() + t.element_size() * ch_off)
 
 
-def conv3x3(x, packed, bias, cin, cout, cout_pad, stride=1, relu=True, out=None, in_ch_off=0, out_ch_off=0):
-    """x: (B, H, W, ld_in) float32 NHWC.  out: (B, Ho, Wo, ld_out) or None (allocated with ld_out = cout)."""
+def _conv3x3_front(what, x, packed, bias, cin, cout, cout_pad, stride, relu, out, in_ch_off, out_ch_off):
+    """the checks every 3x3 conv wrapper makes (device, float32 maps, shapes), the output allocation and the descriptor: (library, descriptor, out)"""
     _need_cuda(x, packed, bias, out)
-    _need_f32('pcp_conv3x3', x, out)
+    _need_f32(what, x, out)
     L = _lib.load()
     B, H, W, ld_in = x.shape
-    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     if out is None:
         out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)
     assert out.shape[:3] == (B, Ho, Wo) and x.is_contiguous() and out.is_contiguous()
     assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    assert bias.numel() >= cout_pad, 'bias must hold cout_pad values (the epilogue reads it 16 bytes at a time)'
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, stride, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(packed), _p(bias), _chan_ptr(out, out_ch_off), _stream()),
-          'pcp_conv3x3')
+    return L, Conv3x3(B, H, W, cin, cout, cout_pad, stride, ld_in, out.shape[3], 1 if relu else 0), out
+
+
+def _conv3x3_launch(symbol, x, packed, bias, cin, cout, cout_pad, stride, relu, out, in_ch_off, out_ch_off):
+    """one launch of the C entry point `symbol` (all of them share pcp_conv3x3's signature)"""
+    L, d, out = _conv3x3_front(symbol, x, packed, bias, cin, cout, cout_pad, stride, relu, out, in_ch_off, out_ch_off)
+    check(getattr(L, symbol)(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(packed), _p(bias), _chan_ptr(out, out_ch_off), _stream()), symbol)
     return out
+
+
+def conv3x3(x, packed, bias, cin, cout, cout_pad, stride=1, relu=True, out=None, in_ch_off=0, out_ch_off=0):
+    """x: (B, H, W, ld_in) float32 NHWC.  out: (B, Ho, Wo, ld_out) or None (allocated with ld_out = cout)."""
+    assert bias.numel() >= cout_pad, 'bias must hold cout_pad values (the epilogue reads it 16 bytes at a time)'
+    return _conv3x3_launch('pcp_conv3x3', x, packed, bias, cin, cout, cout_pad, stride, relu, out, in_ch_off, out_ch_off)
 
 
 def sparse_conv3x3_s2(pillar_features, vox, w_packed, bias, cout, relu=True, out=None, out_dtype=torch.float32):
@@ -329,82 +338,31 @@ def sparse_conv3x3_s2(pillar_features, vox, w_packed, bias, cout, relu=True, out
 
 def conv3x3_winograd(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0):
     """stride-1 3x3 conv through the fused Winograd F(2x2,3x3) kernel; same tensor contract as conv3x3."""
-    _need_cuda(x, u_packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3_winograd(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(u_packed), _p(bias), _chan_ptr(out, out_ch_off),
-                                 _stream()), 'pcp_conv3x3_winograd')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_winograd', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
 
 
 def conv3x3_winograd_ws(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0):
     """stride-1 3x3 conv through the wave-stationary fused Winograd F(2x2,3x3) kernel (csrc/wino_ws.hip; weights from
     pack.pack_conv3x3_winograd_ws); same tensor contract as conv3x3.  cin % 32 == 0, cout_pad % 64 == 0."""
-    _need_cuda(x, u_packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3_winograd_ws(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(u_packed), _p(bias), _chan_ptr(out, out_ch_off),
-                                    _stream()), 'pcp_conv3x3_winograd_ws')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_winograd_ws', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
 
 
 def conv3x3_winograd4f(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0):
     """stride-1 3x3 conv through the FUSED Winograd F(4x4,3x3) kernel (csrc/wino4f.hip; weights from pack.pack_conv3x3_winograd4f); same
     tensor contract as conv3x3.  cin % 8 == 0, cout_pad % 64 == 0."""
-    _need_cuda(x, u_packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3_winograd4f(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(u_packed), _p(bias), _chan_ptr(out, out_ch_off),
-                                   _stream()), 'pcp_conv3x3_winograd4f')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_winograd4f', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
 
 
 def conv3x3_winograd4h(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0):
     """stride-1 3x3 conv through the fused F(4x4,3x3) kernel with two four-wave workgroups per CU (csrc/wino4h.hip; weights from
     pack.pack_conv3x3_winograd4h); same tensor contract as conv3x3_winograd4f."""
-    _need_cuda(x, u_packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3_winograd4h(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(u_packed), _p(bias), _chan_ptr(out, out_ch_off),
-                                   _stream()), 'pcp_conv3x3_winograd4h')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_winograd4h', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
 
 
 def conv3x3_winograd4c(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=None, in_ch_off=0, out_ch_off=0):
     """stride-1 3x3 conv through the fused F(4x4,3x3) kernel whose waves split the output channels (csrc/wino4c.hip: the output transform
     in registers; weights from pack.pack_conv3x3_winograd4c); same tensor contract and the same bits as conv3x3_winograd4h."""
-    _need_cuda(x, u_packed, bias, out)
-    _need_f32('pcp_conv3x3_winograd4c', x, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
-    check(L.pcp_conv3x3_winograd4c(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(u_packed), _p(bias), _chan_ptr(out, out_ch_off),
-                                   _stream()), 'pcp_conv3x3_winograd4c')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_winograd4c', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
 
 
 _W4_WORKSPACE = {}
@@ -430,14 +388,7 @@ def conv3x3_winograd4(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=Non
     """stride-1 3x3 conv of a wide layer through Winograd F(4x4,3x3) (transform, 36 batched MFMA GEMMs, transform); same tensor
     contract as conv3x3.  stage_times: optional list; when given the call is synchronous and appends
     (input_ms, gemm_ms, output_ms, gemm_flops) measured with HIP events on the launch stream."""
-    _need_cuda(x, u_packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    if out is None:
-        out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, H, W) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, 1, ld_in, out.shape[3], 1 if relu else 0)
+    L, d, out = _conv3x3_front('pcp_conv3x3_winograd4', x, u_packed, bias, cin, cout, cout_pad, 1, relu, out, in_ch_off, out_ch_off)
     nbytes = ctypes.c_size_t(0)
     check(L.pcp_conv3x3_winograd4_workspace_bytes(ctypes.byref(d), ctypes.byref(nbytes)), 'pcp_conv3x3_winograd4_workspace_bytes')
     ws = _w4_workspace(x.device, nbytes.value)
@@ -456,19 +407,8 @@ def conv3x3_winograd4(x, u_packed, bias, cin, cout, cout_pad, relu=True, out=Non
 def conv3x3_bf16x3(x, packed, bias, cin, cout, cout_pad, stride=1, relu=True, out=None, in_ch_off=0, out_ch_off=0, plain=False):
     """opt-in split-bf16 arithmetic (see include/pcp_hip.h); same tensor contract as conv3x3.  plain=True: single bf16 products
     (pcp_conv3x3_bf16, the mixed-precision training mode)"""
-    _need_cuda(x, packed, bias, out)
-    L = _lib.load()
-    B, H, W, ld_in = x.shape
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None:
-        out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, Ho, Wo) and x.is_contiguous() and out.is_contiguous()
-    assert in_ch_off + cin <= ld_in and out_ch_off + cout <= out.shape[3]
-    d = Conv3x3(B, H, W, cin, cout, cout_pad, stride, ld_in, out.shape[3], 1 if relu else 0)
-    fn = L.pcp_conv3x3_bf16 if plain else L.pcp_conv3x3_bf16x3
-    check(fn(ctypes.byref(d), _chan_ptr(x, in_ch_off), _p(packed), _p(bias), _chan_ptr(out, out_ch_off), _stream()),
-          'pcp_conv3x3_bf16' if plain else 'pcp_conv3x3_bf16x3')
-    return out
+    return _conv3x3_launch('pcp_conv3x3_bf16' if plain else 'pcp_conv3x3_bf16x3', x, packed, bias, cin, cout, cout_pad, stride, relu, out,
+                           in_ch_off, out_ch_off)
 
 
 def conv3x3_grouped_small(x, weights, bias, offsets, out):

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import lib, ops, pack
 from . import train_ops as tops
+from .conv_dispatch import bf16x3_items, choose_fused_f4, conv_algo, fused_f4_shape, winograd_items
 
 
 B3_MIN_WORKGROUPS = 256        # the bf16 / bf16x3 conv kernels are used where a launch fills the chip (tests lower it)
@@ -26,31 +27,23 @@ B3_MIN_WORKGROUPS = 256        # the bf16 / bf16x3 conv kernels are used where a
 
 def fused_f4_choice(B, H, W, cin, cout):
     """which fused Winograd F(4x4,3x3) kernel a stride-1 3x3 conv cin -> cout on a (B, H, W) map goes to in the training step: None | '4f' |
-    '4h'.  The rule of the inference dispatch (pcdet/models/convnet.py::PackedConv._use_winograd4f / _prefer_winograd4h): k_wino4h up to 128
-    input channels or where k_wino4f's 16 x 32-pixel items leave CUs idle, k_wino4f for the wider layers, neither below one item per CU
-    slot.  PCP_CONV_ALGO = winograd4f | winograd4h forces a kernel (tests), direct | winograd | bf16* switch both off."""
-    algo = os.environ.get('PCP_CONV_ALGO', 'auto')
-    if cin % 8 or cout % 4 or cout < 48 or algo in ('direct', 'winograd', 'winograd4', 'bf16x3', 'bf16'):
+    '4h'.  The rule of the inference dispatch (conv_dispatch.choose_fused_f4): k_wino4h up to 128 input channels or where k_wino4f's
+    16 x 32-pixel items leave CUs idle, k_wino4f for the wider layers, neither below one item per CU slot.  PCP_CONV_ALGO = winograd4f |
+    winograd4h forces a kernel (tests), direct | winograd | bf16* switch both off.  The keyword arguments are where this rule differs from
+    inference (each explained at choose_fused_f4)."""
+    algo = conv_algo()
+    if not fused_f4_shape(cin, cout, 1, algo):
         return None
-    if algo == 'winograd4f':
-        return '4f'
-    if algo == 'winograd4h':
-        return '4h'
-    nb = pack.round_up(cout, 64) // 64
-    w4h = B * ((H + 15) // 16) * ((W + 15) // 16) * nb
-    w4f = B * ((H + 15) // 16) * ((W + 31) // 32) * nb
-    if w4h >= 256 and (cin <= 128 or w4f < 256):
-        return '4h'
-    if cin <= 448 and w4f >= 256 and (w4f % 256 == 0 or w4f >= 512) and not (H * W <= 64 * 64 and cin <= 128):
-        return '4f'
-    return None
+    name = choose_fused_f4(algo, cin, pack.round_up(cout, 64), False, B, H, W, kernel_limits=False, knows_4c=False, wino4h_overrides=False,
+                           cap_needs_w4=False, half_before_cap=True)
+    return {'winograd4f': '4f', 'winograd4h': '4h'}.get(name)
 
 
 def mp_mode():
     """PCP_CONV_ALGO=bf16: the mixed-precision training loop (include/pcp_hip_mp.h) -- the 3x3 layers store their activations and
     gradients as bf16 and run forward / data-gradient / weight-gradient on the bf16 matrix cores; master weights, BatchNorm, losses
     and the optimizer stay fp32"""
-    return os.environ.get('PCP_CONV_ALGO', 'auto') == 'bf16'
+    return conv_algo() == 'bf16'
 
 
 def as_f32(t, off=0, c=None):
@@ -182,8 +175,9 @@ class ConvBNAct:
         cache = getattr(self.conv, '_pcp_train_pack', None)
         if cache is None:
             cache = self.conv._pcp_train_pack = dict(step=-1)
-        if bhw is not None and self.kind == '3x3' and cache.get('f4_key') != (tuple(bhw), os.environ.get('PCP_CONV_ALGO', 'auto')):
-            cache['f4_key'] = (tuple(bhw), os.environ.get('PCP_CONV_ALGO', 'auto'))
+        f4_key = (tuple(bhw), conv_algo()) if bhw is not None and self.kind == '3x3' else None
+        if f4_key is not None and cache.get('f4_key') != f4_key:
+            cache['f4_key'] = f4_key
             f4_new = (fused_f4_choice(*bhw, self.cin, self.cout) if self.stride == 1 else None, fused_f4_choice(*bhw, self.cout, self.cin))
             if f4_new != cache.get('f4'):
                 # another fused-F(4x4) form is needed (another batch / map shape, e.g. the last partial batch): take the slow path once so
@@ -254,7 +248,7 @@ class ConvBNAct:
                     bufs['fw_w'] = torch.empty((self.cin // 8, 16, pack.round_up(self.cout, 64), 8), dtype=torch.float32, device=dev)
                 if self.cout % pack.WINO_CK == 0 and self.cin >= 48:
                     bufs['bw_w'] = torch.empty((self.cout // 8, 16, pack.round_up(self.cin, 64), 8), dtype=torch.float32, device=dev)
-                if os.environ.get('PCP_CONV_ALGO', 'auto') in ('bf16x3', 'bf16'):  # opt-in split / plain bf16 arithmetic (conv_bf16x3.hip)
+                if conv_algo() in ('bf16x3', 'bf16'):  # opt-in split / plain bf16 arithmetic (conv_bf16x3.hip)
                     if self.cin % 16 == 0 and self.cout >= 48:
                         bufs['fw_3'] = torch.empty((self.cin // 16) * pack.round_up(self.cout, 64) * 9 * 16 * 2, dtype=torch.int16, device=dev)
                     if self.cout % 16 == 0 and self.cin >= 48:
@@ -339,11 +333,9 @@ class ConvBNAct:
     @staticmethod
     def _run3x3(forms, x, cin, cout, stride, out, in_off, out_off):
         B, H, W, _ = x.shape
-        algo = os.environ.get('PCP_CONV_ALGO', 'auto')                  # auto | direct | winograd | bf16x3 | bf16 (same switch as inference)
+        algo = conv_algo()                                              # auto | direct | winograd | bf16x3 | bf16 (same switch as inference)
         if algo in ('bf16x3', 'bf16') and 'b3' in forms:
-            Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-            th = 16 if stride == 1 else 8
-            if B * ((Ho + th - 1) // th) * ((Wo + 15) // 16) * (forms['b3'][2] // 64) >= B3_MIN_WORKGROUPS:
+            if bf16x3_items(B, H, W, stride) * (forms['b3'][2] // 64) >= B3_MIN_WORKGROUPS:
                 w3, b3, cp3 = forms['b3']
                 return ops.conv3x3_bf16x3(x, w3, b3, cin, cout, cp3, stride=stride, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off,
                                           plain=(algo == 'bf16'))
@@ -352,7 +344,7 @@ class ConvBNAct:
             kind, u, ub, ucp = forms['f4']
             run = ops.conv3x3_winograd4h if kind == '4h' else ops.conv3x3_winograd4f
             return run(x, u, ub, cin, cout, ucp, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off)
-        big = B * ((H + 7) // 8) * ((W + 15) // 16) * (forms['wino'][2] // 64) >= 256 if 'wino' in forms else False
+        big = winograd_items(B, H, W) * (forms['wino'][2] // 64) >= 256 if 'wino' in forms else False
         if stride == 1 and 'wino' in forms and algo != 'direct' and (big or algo == 'winograd'):
             u, ub, ucp = forms['wino']
             return ops.conv3x3_winograd(x, u, ub, cin, cout, ucp, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off)

@@ -22,6 +22,7 @@ sys.path.insert(0, PKG)
 from pcdet.config import EasyDict, cfg_from_yaml_file  # noqa: E402
 from pcdet.models import DatasetInfo, build_network  # noqa: E402
 from pcp_amd import lib, ops, synth  # noqa: E402
+from pcp_amd.conv_dispatch import conv_algo  # noqa: E402
 
 YAML = os.path.join(HERE, 'cfgs', 'nuscenes_models', 'pointpillar_jr_nomap.yaml')
 
@@ -114,7 +115,7 @@ def main():
     args = ap.parse_args()
     model = build_model()
     res = {'metric': 'pointpillar_jr_nomap', 'points_per_frame': args.points, 'cloud': 'synth.nusc_cloud ring, seeded',
-           'conv_algo': os.environ.get('PCP_CONV_ALGO', 'auto')}
+           'conv_algo': conv_algo()}
     clouds = [synth.nusc_cloud(b, args.points, dist='ring') for b in range(4)]
     for B in (1, 4):
         pts = synth.collate(clouds[:B])

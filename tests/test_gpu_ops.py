@@ -966,6 +966,7 @@ def test_auto_dispatch_falls_back_when_the_fused_f4_kernel_refuses(monkeypatch):
     those: the wrappers raise)"""
     import torch.nn as nn
     from pcdet.models import convnet
+    from pcp_amd import conv_dispatch
     ops = _ops()
     d = dev()
     torch.manual_seed(5)
@@ -975,21 +976,105 @@ def test_auto_dispatch_falls_back_when_the_fused_f4_kernel_refuses(monkeypatch):
         v = getattr(pc, attr)
         setattr(pc, attr, tuple(t.to(d) if torch.is_tensor(t) else t for t in v) if isinstance(v, tuple) else v.to(d))
     x = torch.from_numpy(_rand(281, (8, 128, 128, 72))).to(d)                     # 8 x 8 x 4 = 256 workgroups: auto picks the fused kernel
-    assert pc._use_winograd4f(x, None, 0, 4)
-    assert pc._prefer_winograd4h(x)                                                # 64 input channels, 512 half-size items: k_wino4h
+    forms = convnet.Forms(*[f and f[2] for f in (pc.wino, pc.b3, pc.w4, pc.w4f, pc.mp)])
+
+    def choice():
+        return conv_dispatch.choose_conv3x3(conv_dispatch.conv_algo(), 64, 64, 1, forms, 8, 128, 128, 72, 4)
+    assert choice() == 'winograd4c'                                                # 64 input channels, 512 half-size items: k_wino4h's grid
     want = pc.run(x, in_ch_off=4)                                                  # fused F(4x4), two workgroups per CU (k_wino4c)
-    monkeypatch.setattr(convnet, 'WINOGRAD4H', '0')
-    assert pc._use_winograd4f(x, None, 0, 4) and not pc._prefer_winograd4h(x)
+    monkeypatch.setattr(conv_dispatch, 'WINOGRAD4H', '0')
+    assert choice() == 'winograd4f'
     want8 = pc.run(x, in_ch_off=4)                                                 # fused F(4x4), one eight-wave workgroup per CU
     np.testing.assert_allclose(want8.cpu().numpy(), want.cpu().numpy(), rtol=0, atol=2e-4)
-    monkeypatch.setattr(convnet, 'WINOGRAD4H', 'auto')
-    monkeypatch.setattr(convnet, 'WINOGRAD4F_MAX_INPUT_BYTES', 1 << 20)
-    assert not pc._use_winograd4f(x, None, 0, 4)
+    monkeypatch.setattr(conv_dispatch, 'WINOGRAD4H', 'auto')
+    monkeypatch.setattr(conv_dispatch, 'WINOGRAD4F_MAX_INPUT_BYTES', 1 << 20)
+    assert choice() == 'winograd'
     got = pc.run(x, in_ch_off=4)                                                   # F(2x2): no exception
     torch.cuda.synchronize()
     ref = F.relu(F.conv2d(x[..., 4:68].permute(0, 3, 1, 2).cpu(), conv.weight.detach(), None, padding=1))
     np.testing.assert_allclose(got.permute(0, 3, 1, 2).cpu().numpy(), ref.numpy(), rtol=2e-4, atol=2e-4)
     np.testing.assert_allclose(want.permute(0, 3, 1, 2).cpu().numpy(), ref.numpy(), rtol=2e-4, atol=2e-4)
+
+
+_CONV_WRAPPERS = {'direct': 'conv3x3', 'winograd': 'conv3x3_winograd', 'winograd4': 'conv3x3_winograd4', 'winograd4f': 'conv3x3_winograd4f',
+                  'winograd4h': 'conv3x3_winograd4h', 'winograd4c': 'conv3x3_winograd4c', 'bf16x3': 'conv3x3_bf16x3'}
+_FORCED = {}
+
+
+def _forced_case(h, w):
+    """the 128 -> 256 layer (the smallest that gets every form packed), its input and torch-CPU conv2d on it, computed once"""
+    if (h, w) not in _FORCED:
+        import torch.nn as nn
+        conv = nn.Conv2d(128, 256, 3, padding=1, bias=True)
+        with torch.no_grad():
+            conv.weight.copy_(torch.from_numpy(_rand(311, (256, 128, 3, 3), -0.05, 0.05)))
+            conv.bias.copy_(torch.from_numpy(_rand(312, (256,), -0.2, 0.2)))
+        x = torch.from_numpy(_rand(313, (1, 128, h, w)))
+        with torch.no_grad():
+            want = F.relu(conv(x))
+            want64 = F.relu(F.conv2d(x.double(), conv.weight.double(), conv.bias.double(), padding=1))
+        _FORCED[(h, w)] = (conv, x, want, want64)
+    return _FORCED[(h, w)]
+
+
+@pytest.mark.parametrize('algo', sorted(_CONV_WRAPPERS))
+@pytest.mark.parametrize('h,w', [(16, 16), (17, 33)])
+def test_forced_kernel_is_the_one_the_rule_names_and_matches_torch_cpu(algo, h, w, monkeypatch):
+    """every forced value of PCP_CONV_ALGO on one layer: PackedConv.run launches the pcp_amd.ops function conv_dispatch.choose_conv3x3 names
+    (the forced kernel), and the output meets the bar of that kernel's own test above.  17 x 33 has ragged tile edges in both directions,
+    for the 16 x 16- and the 16 x 32-pixel items.  PCP_CONV_ALGO=bf16 is not here: its branch ('mp') runs train_ops.mp_conv3x3, no function
+    of pcp_amd.ops, on bf16 maps (tests/test_gpu_mp.py)"""
+    from pcdet.models import convnet
+    from pcp_amd import conv_dispatch
+    ops = _ops()
+    d = dev()
+    conv, x, want, want64 = _forced_case(h, w)
+    monkeypatch.setenv('PCP_CONV_ALGO', algo)
+    monkeypatch.setattr(conv_dispatch, 'B3_MIN_WORKGROUPS', 1)                    # a one-frame launch never fills the chip
+    conv.cuda()
+    try:
+        pc = convnet.pack_conv_module(conv, None, relu=True)
+    finally:
+        conv.cpu()
+    ran = []
+    for n in set(_CONV_WRAPPERS.values()) | {'conv3x3_winograd_ws', 'pointwise'}:
+        monkeypatch.setattr(ops, n, (lambda n_, f_: lambda *a, **k: (ran.append(n_), f_(*a, **k))[1])(n, getattr(ops, n)))
+    got = pc.run(ops.as_nhwc(x.to(d)))
+    torch.cuda.synchronize()
+    forms = convnet.Forms(*[f and f[2] for f in (pc.wino, pc.b3, pc.w4, pc.w4f, pc.mp)])
+    name = conv_dispatch.choose_conv3x3(algo, 128, 256, 1, forms, 1, h, w, 128)
+    assert name == algo and ran == [_CONV_WRAPPERS[name]], (name, ran)
+    got = got.permute(0, 3, 1, 2).cpu()
+    if algo == 'direct':
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=1e-4, atol=1e-4)
+    elif algo == 'winograd':
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=2e-4, atol=2e-4)
+    elif algo == 'winograd4':
+        assert float((got.double() - want64).abs().max()) <= 2e-4 * float(want64.abs().max())
+    elif algo == 'bf16x3':
+        assert float((got - want).abs().max()) / float(want.abs().max()) < 1e-4
+    else:
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=2e-4, atol=2e-4 * max(1.0, float(want.abs().max())))
+
+
+@pytest.mark.parametrize('wrapper', sorted(_CONV_WRAPPERS.values()) + ['conv3x3_winograd_ws'])
+def test_conv3x3_wrappers_refuse_maps_that_are_not_float32(wrapper, monkeypatch):
+    """the fp32 kernels would read a bf16 map past its end: every 3x3 wrapper raises on a bf16 input and on a bf16 output buffer, before
+    anything is launched (a launch asks for the stream: that call is made to fail here)"""
+    ops = _ops()
+    from pcp_amd import lib
+    d = dev()
+
+    def no_launch():
+        raise AssertionError('%s went on to launch' % wrapper)
+    monkeypatch.setattr(ops, '_stream', no_launch)
+    wts, bias = torch.zeros(1 << 16, device=d), torch.zeros(64, device=d)
+    x = torch.zeros((1, 16, 16, 8), device=d)
+    run = getattr(ops, wrapper)
+    with pytest.raises(lib.PcpError):
+        run(x.to(torch.bfloat16), wts, bias, 8, 8, 64)
+    with pytest.raises(lib.PcpError):
+        run(x, wts, bias, 8, 8, 64, out=torch.zeros((1, 16, 16, 8), dtype=torch.bfloat16, device=d))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

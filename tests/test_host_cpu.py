@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import pack_eval
-from helpers import load_golden
+from helpers import GOLDEN, load_golden
 from pcp_amd import pack, synth
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -196,7 +196,7 @@ def test_shipped_yaml_configs_build_all_five_models():
 def test_shipped_yaml_state_dicts_equal_the_references(yaml_name, golden):
     """every shipped YAML builds a model whose state-dict keys and shapes are EXACTLY those of the reference model built from the
     reference's YAML of the same name (recorded as data in the golden fixtures): reference checkpoints load with strict=True"""
-    from helpers import load_golden
+    from helpers import GOLDEN, load_golden
     from pcdet.config import EasyDict, cfg_from_yaml_file
     from pcdet.models import DatasetInfo, build_network
     cfg = cfg_from_yaml_file(os.path.join(REPO, 'practical-collab-perception_amd', 'tools', 'cfgs', 'v2x_sim_models', yaml_name), EasyDict())
@@ -221,7 +221,7 @@ def test_shipped_yaml_sections_equal_the_references(yaml_name, golden, opt_golde
     """the resolved MODEL (and OPTIMIZATION) section of every shipped YAML against the reference's resolved section of the YAML of the same
     name (stored as data with the golden fixtures): equal key by key except the build's own include keys, keys the build adds with the
     reference's default, and the overrides the fixture generator applied (temp checkpoints, mini-geometry range, lowered score threshold)"""
-    from helpers import load_golden
+    from helpers import GOLDEN, load_golden
     from pcdet.config import EasyDict, cfg_from_yaml_file
     cfg = cfg_from_yaml_file(os.path.join(REPO, 'practical-collab-perception_amd', 'tools', 'cfgs', 'v2x_sim_models', yaml_name), EasyDict())
 
@@ -323,15 +323,27 @@ def test_winograd4h_weight_order_is_the_documented_permutation_and_dispatch_rule
         kq, c, e, ks = lane >> 4, lane & 15, j >> 1, j & 1
         assert pc4[s, g, q, lane, j] == pf[s, 2 * q + e, 16 * g + c, 4 * ks + kq]
     pc = convnet.pack_conv_module(nn.Conv2d(128, 128, 3, padding=1, bias=False), None, relu=True)
-    assert pc._prefer_winograd4h(torch.empty((20, 64, 64, 128), device='meta'))          # 640 items: the layer F(2x2) used to keep
-    assert pc._use_winograd4f(torch.empty((20, 64, 64, 128), device='meta'), None, 0, 0)
-    assert not pc._prefer_winograd4h(torch.empty((4, 64, 64, 128), device='meta'))       # 128 items: does not cover the chip
+    assert _choice(pc, (20, 64, 64, 128)) == 'winograd4c'                                 # 640 half-size items: the layer F(2x2) used to keep
+    assert _choice(pc, (4, 64, 64, 128)) == 'winograd'                                    # 128 items: does not cover the chip
     wide = convnet.pack_conv_module(nn.Conv2d(384, 128, 3, padding=1, bias=False), None, relu=True)
-    assert not wide._prefer_winograd4h(torch.empty((4, 128, 128, 384), device='meta'))   # cin > 128: the eight-wave kernel
+    assert _choice(wide, (4, 128, 128, 384)) == 'winograd4f'                              # cin > 128: the eight-wave kernel
     monkeypatch.setenv('PCP_CONV_ALGO', 'winograd4h')
-    assert wide._prefer_winograd4h(torch.empty((4, 128, 128, 384), device='meta'))
+    assert _choice(wide, (4, 128, 128, 384)) == 'winograd4h'
     monkeypatch.setenv('PCP_CONV_ALGO', 'winograd4f')
-    assert not pc._prefer_winograd4h(torch.empty((20, 64, 64, 128), device='meta'))
+    assert _choice(pc, (20, 64, 64, 128)) == 'winograd4f'
+
+
+def _choice(pc, shape, in_ch_off=0):
+    """the kernel conv_dispatch.choose_conv3x3 names for the packed layer on a map of `shape` (the launch allocates its output)"""
+    from pcdet.models import convnet
+    from pcp_amd import conv_dispatch
+    B, H, W, ld = shape
+    forms = convnet.Forms(*[f and f[2] for f in (pc.wino, pc.b3, pc.w4, pc.w4f, pc.mp)])
+    return conv_dispatch.choose_conv3x3(conv_dispatch.conv_algo(), pc.cin, pc.cout, pc.stride, forms, B, H, W, ld, in_ch_off)
+
+
+def _fused_f4(pc, shape, in_ch_off=0):
+    return _choice(pc, shape, in_ch_off) in ('winograd4f', 'winograd4h', 'winograd4c')
 
 
 def test_auto_dispatch_respects_the_fused_f4_kernels_own_limits(monkeypatch):
@@ -339,21 +351,48 @@ def test_auto_dispatch_respects_the_fused_f4_kernels_own_limits(monkeypatch):
     (32-bit buffer-descriptor offsets); auto dispatch must fall through to the other kernels outside those limits instead of raising"""
     import torch.nn as nn
     from pcdet.models import convnet
+    from pcp_amd import conv_dispatch
     conv = nn.Conv2d(64, 64, 3, padding=1, bias=False)
     pc = convnet.pack_conv_module(conv, nn.BatchNorm2d(64).eval(), relu=True)
     assert pc.w4f is not None
-    x = torch.empty((4, 256, 256, 64), device='meta')
-    assert pc._use_winograd4f(x, None, 0, 0)
-    assert not pc._use_winograd4f(x, None, 0, 2)                        # input window not 16-byte aligned
-    assert not pc._use_winograd4f(torch.empty((4, 256, 256, 66), device='meta'), None, 0, 0)
-    monkeypatch.setattr(convnet, 'WINOGRAD4F_MAX_INPUT_BYTES', x.numel() * 4 - 1)
-    assert not pc._use_winograd4f(x, None, 0, 0)                        # over the byte limit: F(2x2) / direct take the layer
+    x = (4, 256, 256, 64)
+    assert _fused_f4(pc, x)
+    assert not _fused_f4(pc, x, 2)                                      # input window not 16-byte aligned
+    assert not _fused_f4(pc, (4, 256, 256, 66))
+    monkeypatch.setattr(conv_dispatch, 'WINOGRAD4F_MAX_INPUT_BYTES', 4 * 256 * 256 * 64 * 4 - 1)
+    assert not _fused_f4(pc, x)                                         # over the byte limit: F(2x2) / direct take the layer
     monkeypatch.undo()
-    big = torch.empty((130, 256, 256, 64), device='meta')               # the stacked car-maker pass at B = 26 frames: > 2 GiB
-    assert big.numel() * 4 > 0x7fffffff and not pc._use_winograd4f(big, None, 0, 0)
+    big = (130, 256, 256, 64)                                           # the stacked car-maker pass at B = 26 frames: > 2 GiB
+    assert 130 * 256 * 256 * 64 * 4 > 0x7fffffff and not _fused_f4(pc, big)
     # layers auto dispatch never sends to the fused kernel do not get its (4x sized) weight form packed
     wide = convnet.pack_conv_module(nn.Conv2d(768, 768, 3, padding=1, bias=False), None, relu=False)
     assert wide.w4 is not None and wide.w4f is None
+
+
+def test_conv_dispatch_table_is_the_recorded_one():
+    """tests/golden/conv_dispatch_table.json was recorded at the commit before pcp_amd/conv_dispatch.py existed (the file names it), by
+    tests/golden/make_conv_dispatch_table.py through PackedConv.run and train_layers.fused_f4_choice with the ops functions stubbed out.  The
+    same recorder on this code must give the same kernel, packed form, cout_pad and channel offset on every row, and the same fused-F(4x4)
+    choice of the training step.  On the CPU the bf16-loop form is never packed (packing it needs a CUDA weight), so no row reaches the 'mp'
+    branch; the bf16 training tests (tests/test_gpu_mp.py, test_gpu_train_ops.py) cover it on the GPU."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('make_conv_dispatch_table', os.path.join(GOLDEN, 'make_conv_dispatch_table.py'))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(rec.TABLE) as f:
+        doc = json.load(f)
+    assert doc['launches'] == [r[0] for r in rec.launches(64, 64, 1)] and doc['fused_f4_launches'] == ['B%d %dx%d' % l for l in rec.f4_launches()]
+    want, got = rec.decode(doc['dispatch']), rec.record_dispatch()
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], (key, [(doc['launches'][i], w, g) for i, (w, g) in enumerate(zip(want[key], got[key])) if w != g])
+    assert {c.split('/')[0] for c in doc['dispatch']['codes']} == {'conv3x3', 'conv3x3_winograd', 'conv3x3_winograd4', 'conv3x3_winograd4f',
+                                                                 'conv3x3_winograd4h', 'conv3x3_winograd4c', 'conv3x3_bf16x3', 'pointwise'}
+    want4, got4 = doc['fused_f4_choice'], rec.record_fused_f4()
+    assert sorted(got4) == sorted(want4)
+    for key in sorted(want4):
+        assert got4[key] == want4[key], key
 
 
 def test_auto_resume_validates_a_checkpoint_before_anything_is_loaded(tmp_path):
