@@ -51,7 +51,9 @@ enum {
   PCP_OPT_MP_DIAG = 5,          /* pcp_mp_conv3x3: timing-only diagnostic builds of the kernel body (built-in 0) */
   PCP_OPT_VOX_AGGREGATE = 6,    /* pcp_voxelize / pcp_pillarise_rows: 1 = count a workgroup's rows in an LDS hash table first, one global atomic per distinct
                                    (workgroup, cell) pair (built-in); 0 = one global atomic per row (rounds 1 - 5) */
-  PCP_OPT_COUNT = 7
+  PCP_OPT_CONV_S2_FORM = 7,     /* pcp_conv3x3, stride 2, cout_pad % 64 == 0: 1 = the 8 x 8-pixel x 64-channel form of k_conv3x3, 2 = the wide form
+                                   k_conv3x3_s2w (bit-identical; built-in: the wide form) */
+  PCP_OPT_COUNT = 8
 };
 int pcp_set_option(int32_t option, int64_t value);
 int64_t pcp_get_option(int32_t option);          /* the override, or -1 while the built-in rule applies (also for an unknown option) */

@@ -49,6 +49,7 @@ struct Conv3Params {
   int relu;
   int tiles_x, tiles_y, n_tiles;
   int vec_out;          // output rows 16-byte aligned: 16-byte stores
+  unsigned in_bytes;    // k_conv3x3_s2w: bytes from `in` to the end of the last pixel's cin channels (buffer descriptor range)
 };
 
 template <int S, int TH, int TW, int BN, int WAVES_M, int WAVES_N>
@@ -218,6 +219,192 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_conv3x3(Conv3Params p) {
           if (co + 2 < p.cout) orow[co + 2] = v.z;
           if (co + 3 < p.cout) orow[co + 3] = v.w;
         }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stride 2, wide form: the arithmetic of k_conv3x3<2, ...> (every output sums slices ascending, taps 0..8, g = 0, 1, the four channel pairs
+// of a g on one accumulator: the same bits) with fewer non-MFMA instructions per MFMA:
+//   * a wave owns 64 pixels x 32 channels (two accumulators): one weight fragment and two patch fragments feed eight MFMAs;
+//   * the weight fragment of lane (r, h) is 16 contiguous bytes of row n0 + r of [cout_pad][16]: it comes from global memory / L2 into a
+//     register ring W2_RING fragments ahead of use and never passes through LDS;
+//   * the patch is double-buffered in LDS (the registers hold the slice after the staged one), ONE barrier per slice;
+//   * the patch loads go through a buffer descriptor, pixels outside the image get an offset past its end and read 0: the number of
+//     loads in flight does not depend on the tile;
+//   * LDS image: pixel (py, px) of the patch is 64-byte row P = py * PITCH + (px & 1) * PE + (px >> 1) (odd and even columns apart, so
+//     the stride-2 gather of a tap reads consecutive rows) and its 16-byte slot s sits at s ^ ((P >> 2) + (py >> KSH)) & 3: every
+//     16-lane group of a ds_read_b128 covers the sixteen slots of a bank row once (the 80-byte rows of k_conv3x3 are 3-way at stride 2).
+// TH x TW = 8 x 8 with BN = 128 (four waves side by side over the channels: the patch is staged once per 128 output channels) where
+// cout_pad % 128 == 0, 8 x 16 with BN = 64 (2 x 2 waves) otherwise.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int W2_RING = 6;          // divides the 18 fragments of a slice: the ring slots are compile-time
+
+template <int TH, int TW, int BN, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(CONV_THREADS, 2) void k_conv3x3_s2w(Conv3Params p) {
+  constexpr int BM = TH * TW;
+  constexpr int PH = (TH - 1) * 2 + 3, PW = (TW - 1) * 2 + 3;
+  constexpr int PE = TW + 1;                              // rows of the even columns 0, 2 .. 2 TW in front of the odd ones
+  constexpr int PITCH = TW == 8 ? 18 : 36;                // rows per patch line (2 TW + 1 used)
+  constexpr int KSH = TW == 8 ? 1 : 0;
+  constexpr int BUF = PH * PITCH * CK;                    // floats per patch buffer
+  constexpr int MI = 2;
+  static_assert(TW == 8 || TW == 16, "swizzle constants are worked out for these two");
+  static_assert(WAVES_M * WAVES_N * 64 == CONV_THREADS && BM == WAVES_M * 64 && BN == WAVES_N * 32, "a wave owns 64 pixels x 32 channels");
+  static_assert(18 % W2_RING == 0, "ring slots are static");
+  constexpr int A_F4 = PH * PW * (CK / 4);
+  constexpr int A_PER = (A_F4 + CONV_THREADS - 1) / CONV_THREADS;
+  static_assert(A_PER * CONV_THREADS - A_F4 <= A_F4, "surplus threads repeat an item");
+
+  __shared__ __attribute__((aligned(16))) float lds[2 * BUF];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+
+  int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int nt = lid % p.n_tiles;
+  int sp = lid / p.n_tiles;
+  const int tile_x = sp % p.tiles_x;
+  sp /= p.tiles_x;
+  const int tile_y = sp % p.tiles_y;
+  const int b = sp / p.tiles_y;
+  const int oy0 = tile_y * TH, ox0 = tile_x * TW;
+  const int n0 = nt * BN;
+  const int iy0 = oy0 * 2 - 1, ix0 = ox0 * 2 - 1;
+
+  // ---- patch staging: static load count, out-of-image pixels read 0 through the descriptor's range check ---------------------------------
+  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in), 0, p.in_bytes, 0x00020000);
+  unsigned a_goff[A_PER];
+  int a_dst[A_PER];
+#pragma unroll
+  for (int i = 0; i < A_PER; i++) {
+    int idx = tid + i * CONV_THREADS;
+    if (idx >= A_F4) idx -= A_F4;                          // surplus threads repeat an item
+    const int pix = idx >> 2, q = idx & 3;
+    const int py = pix / PW, px = pix % PW;
+    const int iy = iy0 + py, ix = ix0 + px;
+    const int P = py * PITCH + (px & 1) * PE + (px >> 1);
+    a_dst[i] = P * CK + ((q ^ (((P >> 2) + (py >> KSH)) & 3)) << 2);
+    a_goff[i] = 0x80000000u;                               // past the end of the buffer -> 0
+    if (iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w)
+      a_goff[i] = (unsigned)((((long long)(b * p.in_h + iy) * p.in_w + ix) * p.ld_in + q * 4) * 4);
+  }
+  const int n_slices = p.cin / CK;
+  const int last = n_slices - 1;
+  f32x4 a_reg[A_PER];
+  auto patch_load = [&](int slice) {
+    const int soff = min(slice, last) * (CK * 4);
+#pragma unroll
+    for (int i = 0; i < A_PER; i++)
+      a_reg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)a_goff[i], soff, 0));
+  };
+  auto patch_store = [&](int buf) {
+    float *dst = lds + buf * BUF;
+#pragma unroll
+    for (int i = 0; i < A_PER; i++) *reinterpret_cast<f32x4 *>(dst + a_dst[i]) = a_reg[i];
+  };
+
+  // ---- weight fragments: lane (r, h) reads channels 8 g + 4 h .. + 3 of row n0 + wn * 32 + r, tap by tap, from global memory ----------------
+  const float *w_lane = p.w + (long long)(n0 + wn * 32 + r) * CK + 4 * h;
+  const long long w_tap = (long long)p.cout_pad * CK;                       // floats between taps; 9 taps per slice
+  auto w_load = [&](int slice, int t) {                                      // t = tap * 2 + g
+    return *reinterpret_cast<const f32x4 *>(w_lane + ((long long)min(slice, last) * 9 + (t >> 1)) * w_tap + (t & 1) * 8);
+  };
+
+  // ---- patch fragment addresses (floats) of g = 0; g = 1 is the slot two further: address ^ 8 ---------------------------------------------
+  int a_off[MI][9];
+#pragma unroll
+  for (int i = 0; i < MI; i++) {
+    const int m = wm * 64 + i * 32 + r;
+    const int ty = m / TW, tx = m % TW;
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+      const int ky = tap / 3, kx = tap % 3;
+      const int py = 2 * ty + ky;
+      const int P = py * PITCH + (kx & 1) * PE + tx + (kx >> 1);
+      a_off[i][tap] = P * CK + ((h ^ (((P >> 2) + (py >> KSH)) & 3)) << 2);
+    }
+  }
+
+  f32x16 acc[MI];
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[i][e] = 0.f;
+
+  // One slice = 18 fenced blocks (the compiler otherwise sinks every load to just in front of its use): block t requests the patch
+  // fragments of block t + 1 and the weight fragment W2_RING - 1 blocks ahead, then runs its eight MFMAs.
+  const auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
+  f32x4 wr[W2_RING];
+  f32x4 af[2][MI];
+  patch_load(0);
+#pragma unroll
+  for (int t = 0; t < W2_RING; t++) wr[t] = w_load(0, t);
+  patch_store(0);
+  patch_load(1);
+  __syncthreads();
+  for (int slice = 0; slice < n_slices; slice++) {
+    const float *As = lds + (slice & 1) * BUF;
+    // the other buffer was last read in slice - 1, in front of the barrier that ended it.  After the last slice this stages a repeat
+    // of it that nobody reads: the loop stays free of branches
+    patch_store((slice + 1) & 1);
+    patch_load(slice + 2);
+#pragma unroll
+    for (int i = 0; i < MI; i++) af[0][i] = *reinterpret_cast<const f32x4 *>(As + a_off[i][0]);
+    fence();
+#pragma unroll
+    for (int t = 0; t < 18; t++) {
+      if (t + 1 < 18) {
+#pragma unroll
+        for (int i = 0; i < MI; i++)
+          af[(t + 1) & 1][i] = *reinterpret_cast<const f32x4 *>(As + (a_off[i][(t + 1) >> 1] ^ (((t + 1) & 1) * 8)));
+      }
+      if (t > 0) wr[(t - 1) % W2_RING] = w_load(slice + (t - 1 + W2_RING >= 18 ? 1 : 0), (t - 1 + W2_RING) % 18);
+      fence();
+      const f32x4 bf = wr[t % W2_RING];
+      const f32x4 a0 = af[t & 1][0], a1 = af[t & 1][1];
+      acc[0] = mfma32(bf.x, a0.x, acc[0]);
+      acc[1] = mfma32(bf.x, a1.x, acc[1]);
+      acc[0] = mfma32(bf.y, a0.y, acc[0]);
+      acc[1] = mfma32(bf.y, a1.y, acc[1]);
+      acc[0] = mfma32(bf.z, a0.z, acc[0]);
+      acc[1] = mfma32(bf.z, a1.z, acc[1]);
+      acc[0] = mfma32(bf.w, a0.w, acc[0]);
+      acc[1] = mfma32(bf.w, a1.w, acc[1]);
+      fence();
+    }
+    wr[17 % W2_RING] = w_load(slice + 1, (17 + W2_RING) % 18);
+    __syncthreads();
+  }
+
+  // ---- epilogue, as k_conv3x3: lane (r, h) holds channels nb + 8 q + 4 h + (0..3) of pixel wm * 64 + i * 32 + r in accumulator quad q -----
+  const int nb = n0 + wn * 32;
+#pragma unroll
+  for (int i = 0; i < MI; i++) {
+    const int m = wm * 64 + i * 32 + r;
+    const int oy = oy0 + m / TW, ox = ox0 + m % TW;
+    if (oy >= p.out_h || ox >= p.out_w) continue;
+    float *orow = p.out + ((long long)(b * p.out_h + oy) * p.out_w + ox) * p.ld_out;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int co = nb + 8 * q + 4 * h;
+      if (co >= p.cout) continue;
+      const f32x4 bias = *reinterpret_cast<const f32x4 *>(p.bias + co);          // padded to cout_pad
+      f32x4 v = f32x4{acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]} + bias;
+      if (p.relu) {
+        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      }
+      if (co + 3 < p.cout && p.vec_out) {
+        *reinterpret_cast<f32x4 *>(orow + co) = v;
+      } else {
+        orow[co] = v.x;
+        if (co + 1 < p.cout) orow[co + 1] = v.y;
+        if (co + 2 < p.cout) orow[co + 2] = v.z;
+        if (co + 3 < p.cout) orow[co + 3] = v.w;
       }
     }
   }
@@ -440,9 +627,36 @@ int launch_conv3(const pcp_conv3x3_t *d, const float *in, const float *w, const 
   p.tiles_y = (p.out_h + TH - 1) / TH;
   p.n_tiles = d->cout_pad / BN;
   p.vec_out = (d->ld_out % 4 == 0 && (((uintptr_t)out) & 15) == 0) ? 1 : 0;
+  p.in_bytes = 0;
   long long blocks = (long long)d->batch * p.tiles_x * p.tiles_y * p.n_tiles;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return PCP_ERR_ARG;
   hipLaunchKernelGGL((k_conv3x3<S, TH, TW, BN, WM, WN>), dim3((unsigned)blocks), dim3(CONV_THREADS), 0, st, p);
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
+
+// bytes the stride-2 wide form addresses through its buffer descriptor; it needs them below 2 GiB (32-bit offsets, 0x80000000 = "outside")
+long long conv3_in_bytes(const pcp_conv3x3_t *d) {
+  return (((long long)d->batch * d->in_h * d->in_w - 1) * d->ld_in + d->cin) * 4;
+}
+
+template <int TH, int TW, int BN, int WM, int WN>
+int launch_conv3_s2w(const pcp_conv3x3_t *d, const float *in, const float *w, const float *bias, float *out, hipStream_t st) {
+  Conv3Params p;
+  p.in = in; p.w = w; p.bias = bias; p.out = out;
+  p.batch = d->batch; p.in_h = d->in_h; p.in_w = d->in_w;
+  p.out_h = (d->in_h - 1) / 2 + 1;
+  p.out_w = (d->in_w - 1) / 2 + 1;
+  p.cin = d->cin; p.cout = d->cout; p.cout_pad = d->cout_pad;
+  p.ld_in = d->ld_in; p.ld_out = d->ld_out; p.relu = d->relu;
+  p.tiles_x = (p.out_w + TW - 1) / TW;
+  p.tiles_y = (p.out_h + TH - 1) / TH;
+  p.n_tiles = d->cout_pad / BN;
+  p.vec_out = (d->ld_out % 4 == 0 && (((uintptr_t)out) & 15) == 0) ? 1 : 0;
+  p.in_bytes = (unsigned)conv3_in_bytes(d);
+  long long blocks = (long long)d->batch * p.tiles_x * p.tiles_y * p.n_tiles;
+  if (blocks <= 0 || blocks > 0x7fffffffLL) return PCP_ERR_ARG;
+  hipLaunchKernelGGL((k_conv3x3_s2w<TH, TW, BN, WM, WN>), dim3((unsigned)blocks), dim3(CONV_THREADS), 0, st, p);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }
@@ -472,7 +686,19 @@ extern "C" int pcp_conv3x3(const pcp_conv3x3_t *d, const float *in, const float 
     if (d->cout_pad % 64 == 0) return launch_conv3<1, 8, 16, 64, 2, 2>(d, in, w_packed, bias, out, st);
     return launch_conv3<1, 8, 16, 32, 4, 1>(d, in, w_packed, bias, out, st);
   } else if (d->stride == 2) {
-    if (d->cout_pad % 64 == 0) return launch_conv3<2, 8, 8, 64, 2, 2>(d, in, w_packed, bias, out, st);
+    if (d->cout_pad % 64 == 0) {
+      // PCP_OPT_CONV_S2_FORM: 1 = k_conv3x3<2, 8, 8, 64, 2, 2>, 2 = k_conv3x3_s2w (same bits), unset = the wide form wherever its buffer
+      // descriptor can address the input
+      const long long form = pcp_option(PCP_OPT_CONV_S2_FORM, 0);
+      if (form != 0 && form != 1 && form != 2) return PCP_ERR_ARG;
+      const bool fits = conv3_in_bytes(d) <= 0x7fffffffLL;
+      if (form == 2 && !fits) return PCP_ERR_UNSUPPORTED;
+      if (form != 1 && fits) {
+        if (d->cout_pad % 128 == 0) return launch_conv3_s2w<8, 8, 128, 1, 4>(d, in, w_packed, bias, out, st);
+        return launch_conv3_s2w<8, 16, 64, 2, 2>(d, in, w_packed, bias, out, st);
+      }
+      return launch_conv3<2, 8, 8, 64, 2, 2>(d, in, w_packed, bias, out, st);
+    }
     return launch_conv3<2, 8, 16, 32, 4, 1>(d, in, w_packed, bias, out, st);
   }
   return PCP_ERR_UNSUPPORTED;

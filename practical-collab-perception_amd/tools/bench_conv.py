@@ -1,6 +1,10 @@
 """Micro-benchmark of the 3x3 convolution kernels on the layer shapes of the five configs (B frames per launch):
 direct implicit GEMM (pcp_conv3x3) vs fused Winograd F(2x2,3x3) (pcp_conv3x3_winograd).  Prints algorithmic TFLOP/s
-(2*B*H*W*Cout*9*Cin / time) for both; used to choose the per-layer algorithm in pcdet/models/convnet.py."""
+(2*B*H*W*Cout*9*Cin / time) for both; used to choose the per-layer algorithm in pcdet/models/convnet.py.
+
+  python tools/bench_conv.py [B [layer]]        the stride-1 table
+  python tools/bench_conv.py s2 [repeats [iters]]     the stride-2 direct kernel on the shapes of the DiscoNet step: the 8 x 8-pixel form
+                                                (option conv_s2_form = 1) and the wide form (2) interleaved in one process"""
 import sys
 from pathlib import Path
 
@@ -18,6 +22,11 @@ LAYERS = [  # (name, cin, cout, H, W)
 ]
 
 
+S2_LAYERS = [  # (B, H = W of the input, cin, cout, launches per DiscoNet step)
+    (20, 256, 64, 128, 1), (4, 512, 64, 64, 2), (4, 256, 64, 128, 3), (20, 128, 128, 128, 1), (4, 128, 128, 256, 2), (4, 128, 128, 128, 1),
+]
+
+
 def timeit(fn, iters=10):
     fn()
     torch.cuda.synchronize()
@@ -30,7 +39,44 @@ def timeit(fn, iters=10):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
+def main_s2(repeats, iters=20):
+    """old and new form alternate inside every repeat; a form's figure is the median of its repeats, its spread their max - min"""
+    from pcp_amd import lib
+    d = torch.device('cuda:0')
+    print('%-28s %10s %8s %8s | %10s %8s %8s | %6s  %s' % ('B HxW (input) cin->cout', 'old us', 'spread', 'TF', 'wide us', 'spread', 'TF', 'x', 'wide wins'))
+    step = [0.0, 0.0]
+    for B, H, cin, cout, per_step in S2_LAYERS:
+        x = torch.randn((B, H, H, cin), device=d)
+        w = torch.randn((cout, cin, 3, 3)) * 0.05
+        pd, bd, cpd = pack.pack_conv3x3(w, torch.zeros(cout))
+        pd, bd = pd.to(d), bd.to(d)
+        out = torch.empty((B, H // 2, H // 2, cout), device=d)
+        flops = 2.0 * B * (H // 2) * (H // 2) * cpd * 9 * cin                  # executed
+        t = {1: [], 2: []}
+        outs = {}
+        for form in (1, 2):                                                      # clocks and caches warm before the first repeat counts
+            lib.set_option('conv_s2_form', form)
+            timeit(lambda: ops.conv3x3(x, pd, bd, cin, cout, cpd, stride=2, out=out), iters=iters)
+        for _ in range(repeats):
+            for form in (1, 2):
+                lib.set_option('conv_s2_form', form)
+                t[form].append(timeit(lambda: ops.conv3x3(x, pd, bd, cin, cout, cpd, stride=2, out=out), iters=iters))
+                outs[form] = out.clone()
+        lib.set_option('conv_s2_form', None)
+        assert torch.equal(outs[1], outs[2]), 'the two forms differ'
+        med = {f: sorted(v)[len(v) // 2] for f, v in t.items()}
+        spread = {f: max(v) - min(v) for f, v in t.items()}
+        step[0] += per_step * med[1]
+        step[1] += per_step * med[2]
+        print('%-28s %10.1f %8.1f %8.1f | %10.1f %8.1f %8.1f | %6.3f  %s' % (
+            '%d %dx%d %d->%d' % (B, H, H, cin, cout), med[1] * 1e6, spread[1] * 1e6, flops / med[1] / 1e12, med[2] * 1e6,
+            spread[2] * 1e6, flops / med[2] / 1e12, med[1] / med[2], 'yes' if med[1] - med[2] > spread[1] else 'no'))
+    print('per DiscoNet step: old %.3f ms, wide %.3f ms' % (step[0] * 1e3, step[1] * 1e3))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 's2':
+        return main_s2(int(sys.argv[2]) if len(sys.argv) > 2 else 7, int(sys.argv[3]) if len(sys.argv) > 3 else 20)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     only = int(sys.argv[2]) if len(sys.argv) > 2 else -1            # layer index (for rocprof --pmc runs)
     d = torch.device('cuda:0')

@@ -31,7 +31,7 @@ def source_sha(label):
 # substring of the rocprof kernel name -> bench.py label key
 KEYS = [('k_conv3x3_wino<1>', 'k_conv3x3_wino<1>'), ('k_conv3x3_wino<2>', 'k_conv3x3_wino<2>'), ('k_wino4f', 'k_wino4f'), ('k_wino4h', 'k_wino4h'), ('k_wino4c', 'k_wino4c'), ('k_wino_ws', 'k_wino_ws'),
         ('k_w4_gemm', 'k_w4_gemm'), ('k_w4_input', 'k_w4_input'), ('k_w4_output', 'k_w4_output'),
-        ('k_conv3x3<1,', 'k_conv3x3_direct<s1>'), ('k_conv3x3<2,', 'k_conv3x3_direct<s2>'),
+        ('k_conv3x3<1,', 'k_conv3x3_direct<s1>'), ('k_conv3x3<2,', 'k_conv3x3_direct<s2>'), ('k_conv3x3_s2w<', 'k_conv3x3_direct<s2>'),
         ('k_pointwise<0', 'k_pointwise<plain>'), ('k_pointwise<1', 'k_pointwise<conv_k2s2>'), ('k_pointwise<2', 'k_pointwise<convT_k2s2>'),
         ('k_pfn_rows', 'k_pfn_rows'), ('k_pfn<', 'k_pfn'), ('k_point_cells', 'k_point_cells'), ('k_cell_finish', 'k_cell_finish'), ('k_point_place', 'k_point_place'),
         ('k_stc_scatter', 'k_stc_scatter'), ('k_sparse_conv_s2', 'k_sparse_conv_s2'), ('k_point_head', 'k_point_head'), ('k_head_grouped', 'k_head_grouped')]
