@@ -417,6 +417,33 @@ typedef struct pcp_pack_job {
 int pcp_pack_conv3x3_group_blocks(const pcp_pack_job_t *job);
 int pcp_pack_conv3x3_group(const pcp_pack_job_t *jobs_device, int32_t n_jobs, int32_t total_blocks, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * SC backbone, training half (workspace/sc_conv.py:14-44,91-119 under autograd): what the conv / BatchNorm entry points above do
+ * not cover of an SCBottleneck.  Conventions of pcp_avgpool_nhwc / pcp_sc_gate (pcp_hip.h): NHWC float32 channel windows, c / ld
+ * multiples of 4, 16-byte aligned pointers.  No atomics: every output element is written by one thread, sums run in a fixed order.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* backward of nn.AvgPool2d(r, r): dx[b, y, x] (+)= dpooled[b, y / r, x / r] / (r * r) for y < (h / r) * r and x < (w / r) * r; the
+ * remainder rows / columns the pool dropped get 0 (accumulate: are left as they are).  dpooled (B, h / r, w / r), dx (B, h, w). */
+int pcp_avgpool_nhwc_backward(const float *dpooled, int32_t ld_dpooled, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t r, float *dx,
+                              int32_t ld_dx, int32_t accumulate, void *stream);
+
+/* backward of pcp_sc_gate's out = t * g, g = sigmoid(x + up(s)):
+ *   dt = dout * g;  dz = dout * t * (1 - g) * g;  dx (+)= dz (dx NULL: skipped, dz IS the gradient of x);
+ *   ds[b, sy, sx] = sum of dz over exactly the pixels the forward's nearest rule sends to (sy, sx), rows then columns ascending.
+ * Two launches: one thread per pixel, then one thread per s element walking its own pixel range (the inverse of the nearest index,
+ * found with the same float32 scale product).  dt may alias dout; dz (B, h, w, ld_dz) is a buffer of its own. */
+int pcp_sc_gate_backward(const float *dout, int32_t ld_dout, const float *t, int32_t ld_t, const float *x, int32_t ld_x, const float *s,
+                         int32_t ld_s, int32_t sh, int32_t sw, float *dt, int32_t ld_dt, float *dz, int32_t ld_dz, float *dx, int32_t ld_dx,
+                         int32_t accumulate_dx, float *ds, int32_t ld_ds, int32_t batch, int32_t h, int32_t w, int32_t c, void *stream);
+
+/* the bottleneck's residual in front of its last ReLU: out = relu(z + res) (out may alias z), and its backward
+ * dz = dout * [out > 0] (dz may alias dout), also copied to dz2 when that is not NULL (the residual branch and the in-place
+ * BatchNorm backward of the conv branch each need their own). */
+int pcp_add_relu(const float *z, int32_t ld_z, const float *res, int32_t ld_res, float *out, int32_t ld_out, int64_t rows, int32_t c,
+                 void *stream);
+int pcp_add_relu_backward(const float *dout, int32_t ld_dout, const float *out, int32_t ld_out, float *dz, int32_t ld_dz, float *dz2,
+                          int32_t ld_dz2, int64_t rows, int32_t c, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

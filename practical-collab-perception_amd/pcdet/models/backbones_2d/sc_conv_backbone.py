@@ -12,6 +12,11 @@ SCBottleneck on NHWC buffers, BatchNorm folded into every conv:
   k4 + ReLU                      -> 3x3 conv, written into window 1 of the cat buffer
   relu(conv3(cat) + x)           -> 1x1 launch with the residual added before the activation
 The ConvTranspose of main_pass and conv_skip write the two windows of conv_out's input: there is no torch.cat anywhere.
+
+train() mode (GPU only): pcdet/models/train_path.py SCBackboneTrain runs the same graph layer by layer with batch-statistics BatchNorm
+(ConvBNAct: conv1_a and conv1_b stay two layers, each with its own BatchNorm, writing the two windows of [a | b]), keeps the un-gated k3
+output, and records its backward on the tape: pcp_add_relu_backward, the conv / BatchNorm gradients, pcp_sc_gate_backward and
+pcp_avgpool_nhwc_backward, with every gradient fan-in added in a fixed order (no atomics: a step repeats bit for bit).
 """
 from functools import partial
 
@@ -21,7 +26,7 @@ import torch.nn as nn
 from pcp_amd import lib, ops, pack
 
 from ..convnet import PackedConv, _fold, pack_conv_module
-from ..packed import PackedModule, require_eval_hip
+from ..packed import PackedModule, train_tape
 
 POOLING_R = 4          # SCBottleneck.pooling_r
 
@@ -103,12 +108,25 @@ class _SCBackboneBase(PackedModule):
                     skip=seq_convs(self.conv_skip), main0=seq_convs(mp[0]), main_blocks=[_PackedBottleneck(b) for b in mp[1:4]],
                     up=pack_conv_module(mp[4], mp[5], relu=True), out=seq_convs(self.conv_out))
 
+    def _forward_train(self, data_dict):
+        from pcp_amd.train_layers import Act
+        from ..train_path import SCBackboneTrain
+        if getattr(self, '_pcp_train', None) is None:
+            self._pcp_train = SCBackboneTrain(self)
+        self._pcp_train.check_input(data_dict['spatial_features'])          # NotImplementedError / ValueError before any launch
+        self.invalidate_packed()
+        out = self._pcp_train.forward(Act(ops.as_nhwc(data_dict['spatial_features'])))
+        data_dict['spatial_features_2d'] = ops.nchw_view(out.t)
+        train_tape(data_dict).append(('backbone_2d', self._pcp_train.backward))
+        return data_dict
+
     def forward(self, data_dict):
-        require_eval_hip(self, type(self).__name__)
-        pk = self.packed()
         if data_dict['spatial_features'] is None:
             raise RuntimeError('%s needs the dense canvas: the VFE skipped it (sparse_first_layer); unset sparse_first_layer'
                                % type(self).__name__)
+        if self.training:
+            return self._forward_train(data_dict)
+        pk = self.packed()
         x = ops.as_nhwc(data_dict['spatial_features'])
         x = pk['stem0'].run(x)
         for blk in pk['stem_blocks']:

@@ -52,8 +52,8 @@ class PackedModule(nn.Module):
 def require_eval_hip(module, what):
     if module.training:
         raise NotImplementedError(
-            '%s: this module has no training kernels (the HIP training path covers config 5: DynPillarVFE, PointPillarScatter, '
-            'BaseBEVBackbone, V2XMidFusionDisco, CenterHead) -- call model.eval()' % what)
+            '%s: this module has no training kernels (the HIP training path covers DynPillarVFE, PointPillarScatter, BaseBEVBackbone, '
+            'SCConvBackbone2dStride4 / Stride1, V2XMidFusionDisco, CenterHead) -- call model.eval()' % what)
 
 
 def train_tape(batch_dict):

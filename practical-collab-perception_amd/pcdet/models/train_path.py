@@ -191,6 +191,137 @@ class BackboneTrain:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# SC backbone (SCConvBackbone2dStride4 / Stride1 of the nuScenes PointPillar-Jr models, workspace/sc_conv.py:14-208)
+# ---------------------------------------------------------------------------------------------------------------------
+
+class _SCBottleneckTrain:
+    """one SCBottleneck (sc_conv.py:47-119) forward and backward.  Every map between the layers is float32: the pool, the gate and the
+    residual kernels are fp32 only, so in the bf16 loop the 3x3 layers are asked for fp32 activations and fp32 data gradients."""
+
+    def __init__(self, blk, name):
+        from .backbones_2d.sc_conv_backbone import POOLING_R
+        self.r = POOLING_R
+        self.gw = blk.conv1_a.out_channels
+        self.planes = blk.conv3.out_channels
+        sc = blk.scconv
+        self.conv1_a = ConvBNAct(blk.conv1_a, blk.bn1_a, relu=True, name=name + '.conv1_a')
+        self.conv1_b = ConvBNAct(blk.conv1_b, blk.bn1_b, relu=True, name=name + '.conv1_b')
+        self.k1 = ConvBNAct(blk.k1[0], blk.k1[1], relu=True, name=name + '.k1')
+        self.k2 = ConvBNAct(sc.k2[1], sc.k2[2], relu=False, name=name + '.scconv.k2')
+        self.k3 = ConvBNAct(sc.k3[0], sc.k3[1], relu=False, name=name + '.scconv.k3')
+        self.k4 = ConvBNAct(sc.k4[0], sc.k4[1], relu=True, name=name + '.scconv.k4')
+        self.conv3 = ConvBNAct(blk.conv3, blk.bn3, relu=False, name=name + '.conv3')
+        self.saved = None
+
+    def forward(self, x):
+        """x: Act, a float32 (B, H, W, planes) map.  Returns Act relu(bn3(conv3([k1 | k4])) + x)."""
+        gw, f32 = self.gw, torch.float32
+        B, H, W, _ = x.t.shape
+        dev = x.t.device
+        ab = _empty((B, H, W, 2 * gw), dev)                                            # [a | b]: two BatchNorms, two windows of one buffer
+        a = self.conv1_a.forward(x, out=Act(ab, 0, gw))
+        b = self.conv1_b.forward(x, out=Act(ab, gw, gw))
+        cat = _empty((B, H, W, 2 * gw), dev)
+        self.k1.forward(a, out=Act(cat, 0, gw))
+        pooled = ops.avgpool_nhwc(ab, self.r, in_ch_off=gw, c=gw)
+        s = self.k2.forward(Act(pooled), out_dtype=f32)
+        t = self.k3.forward(b, out_dtype=f32)
+        gated = _empty((B, H, W, gw), dev)
+        ops.sc_gate(t.t, ab, s.t, gw, out=gated, x_ch_off=gw)                          # not in place: the backward needs the un-gated t
+        self.k4.forward(Act(gated), out=Act(cat, gw, gw))
+        z = self.conv3.forward(Act(cat))
+        tops.add_relu(z.t, x.t, self.planes, res_ch_off=x.off)                         # in place over bn3's output
+        self.saved = dict(ab=ab, s=s.t, t=t.t, out=z.t)
+        return z
+
+    def backward(self, dout):
+        """dout: Act, a float32 buffer of its own (overwritten).  Returns Act gradient of the block input."""
+        sv = self.saved
+        gw, f32 = self.gw, torch.float32
+        dev = dout.t.device
+        dx = _empty(tuple(dout.t.shape[:3]) + (self.planes,), dev)                     # the residual branch's copy of the masked gradient
+        tops.add_relu_backward(dout.t, sv['out'], self.planes, dz2=dx, dout_ch_off=dout.off)
+        dcat = self.conv3.backward(dout)
+        da = self.k1.backward(Act(dcat.t, 0, gw), dx_dtype=f32)
+        dgated = self.k4.backward(Act(dcat.t, gw, gw), dx_dtype=f32)
+        # gradient of b, always in this order: the gate's, k3's data gradient, the pool backward of k2's data gradient
+        dt, db, ds = tops.sc_gate_backward(dgated.t, sv['t'], sv['ab'], sv['s'], gw, x_ch_off=gw)
+        dk3 = self.k3.backward(Act(dt), dx_dtype=f32)
+        tops.accumulate(db, dk3.t, gw)
+        dpooled = self.k2.backward(Act(ds), dx_dtype=f32)
+        tops.avgpool_nhwc_backward(dpooled.t, self.r, db, gw, accumulate=True)
+        # gradient of the block input: the masked residual gradient, conv1_a's, conv1_b's
+        tops.accumulate(dx, self.conv1_a.backward(da).t, self.planes)
+        tops.accumulate(dx, self.conv1_b.backward(Act(db)).t, self.planes)
+        return Act(dx)
+
+
+class SCBackboneTrain:
+    """stem -> (conv_skip | main_pass) -> conv_out of both SC backbones, forward and backward"""
+
+    def __init__(self, bb):
+        self.m = bb
+        stem, mp = list(bb.stem), list(bb.main_pass)
+        self.stem0 = ConvBNAct(stem[0][0], stem[0][1], relu=True, name='stem.0')
+        self.stem_blocks = [_SCBottleneckTrain(b, 'stem.%d' % (i + 1)) for i, b in enumerate(stem[1:])]
+        self.skip = ConvBNAct(bb.conv_skip[0], bb.conv_skip[1], relu=True, name='conv_skip')
+        self.main0 = ConvBNAct(mp[0][0], mp[0][1], relu=True, name='main_pass.0')
+        self.main_blocks = [_SCBottleneckTrain(b, 'main_pass.%d' % (i + 1)) for i, b in enumerate(mp[1:4])]
+        self.up = ConvBNAct(mp[4], mp[5], relu=True, name='main_pass.4')
+        self.out = ConvBNAct(bb.conv_out[0], bb.conv_out[1], relu=True, name='conv_out')     # its BatchNorm keeps its own eps / momentum
+
+    def check_input(self, sf):
+        """the refusals, before any launch.  sf: the (B, C, H, W) canvas."""
+        from .backbones_2d.sc_conv_backbone import POOLING_R
+        name = type(self.m).__name__
+        if sf is None or not sf.is_cuda:
+            raise NotImplementedError('%s: the HIP training path has no CPU form (the canvas is on %s) -- move the model and the batch to the '
+                                      'GPU, or call model.eval()' % (name, 'no device' if sf is None else sf.device))
+        s0 = self.stem0.stride
+        if sf.shape[2] % s0 or sf.shape[3] % s0:
+            raise ValueError('%s: a %dx%d canvas is not a multiple of the stem stride %d (the stride-%d training kernels take even maps)'
+                             % (name, sf.shape[2], sf.shape[3], s0, s0))
+        # the layers' own sizes: stem.0, then main_pass.0
+        _b, sh, sw = self.stem0.out_shape(Act(sf.permute(0, 2, 3, 1)))
+        _b, mh, mw = self.main0.out_shape(Act(sf.new_empty((sf.shape[0], sh, sw, 0))))
+        if min(mh, mw) < POOLING_R:
+            raise NotImplementedError('%s: the main-pass map is %dx%d, below POOLING_R = %d: the pooled map of its bottlenecks would be empty'
+                                      % (name, mh, mw, POOLING_R))
+        if 2 * mh != sh or 2 * mw != sw:
+            raise ValueError('%s: the up-sampled main pass (%dx%d) does not match the stem map (%dx%d); the grid needs even stem sizes'
+                             % (name, 2 * mh, 2 * mw, sh, sw))
+
+    def forward(self, x):
+        """x: Act of the canvas.  Returns Act of conv_out's map."""
+        f32 = torch.float32
+        x = self.stem0.forward(x, out_dtype=f32)
+        for blk in self.stem_blocks:
+            x = blk.forward(x)
+        B, H, W, _ = x.t.shape
+        merged = _empty((B, H, W, self.up.cout + self.skip.cout), x.t.device)         # cat([main, skip]): skip is window 1
+        self.skip.forward(x, out=Act(merged, self.up.cout, self.skip.cout))
+        y = self.main0.forward(x, out_dtype=f32)
+        for blk in self.main_blocks:
+            y = blk.forward(y)
+        self.up.forward(y, out=Act(merged, 0, self.up.cout))
+        return self.out.forward(Act(merged))
+
+    def backward(self, dout):
+        """dout: Act, gradient of conv_out's map.  Returns Act gradient of the canvas."""
+        f32 = torch.float32
+        dm = self.out.backward(dout, dx_dtype=f32)
+        g = self.up.backward(Act(dm.t, 0, self.up.cout))
+        for blk in reversed(self.main_blocks):
+            g = blk.backward(g)
+        # gradient of the stem output: conv_skip's data gradient, then main_pass.0's
+        dx = self.skip.backward(Act(dm.t, self.up.cout, self.skip.cout))
+        tops.accumulate(dx.t, self.main0.backward(g, dx_dtype=f32).t, dx.c)
+        for blk in reversed(self.stem_blocks):
+            dx = blk.backward(dx)
+        return self.stem0.backward(dx)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # DiscoNet mid fusion
 # ---------------------------------------------------------------------------------------------------------------------
 

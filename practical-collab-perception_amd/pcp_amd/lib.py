@@ -317,6 +317,11 @@ SYMBOLS.update({
     'pcp_pack_conv3x3_group_blocks': (c_i32, [vp]),
     'pcp_pack_conv3x3_group': (c_i32, [vp, c_i32, c_i32, vp]),
     'pcp_adam_step': (c_i32, [vp, vp, vp, vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_f, vp, c_f, vp]),
+    'pcp_avgpool_nhwc_backward': (c_i32, [vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp]),
+    'pcp_sc_gate_backward': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, vp, c_i32, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, c_i32, c_i32, vp, c_i32,
+                                     c_i32, c_i32, c_i32, c_i32, vp]),
+    'pcp_add_relu': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, c_i64, c_i32, vp]),
+    'pcp_add_relu_backward': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, vp, c_i32, c_i64, c_i32, vp]),
 })
 
 # include/pcp_hip_mp.h (mixed-precision training loop, config 5)

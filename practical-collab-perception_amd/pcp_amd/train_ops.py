@@ -6,7 +6,7 @@ import torch
 
 from . import lib as _lib
 from .lib import Conv3x3, RowMap, check
-from .ops import _chan_ptr, _need_cuda, _p, _stream
+from .ops import _chan_ptr, _need_cuda, _need_f32, _p, _stream
 
 
 class Scratch:
@@ -887,3 +887,79 @@ def filter_gt_boxes(gt_boxes, pc_range):
     rng = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
     check(L.pcp_filter_gt_boxes(_p(gt_boxes), B, M, rng, _p(out), _stream()), 'pcp_filter_gt_boxes')
     return out
+
+
+# ---- SC backbone (csrc/scconv.hip, training half): fp32 only, NHWC channel windows of c channels --------------------------------------
+
+def _sc_windows(what, c, *pairs):
+    ts = [t for t, _off in pairs if t is not None]
+    _need_cuda(*ts)
+    _need_f32(what, *ts)
+    for t, off in pairs:
+        if t is not None:
+            assert t.is_contiguous() and off >= 0 and off + c <= t.shape[-1], (what, tuple(t.shape), off, c)
+
+
+def avgpool_nhwc_backward(dpooled, r, dx, c, accumulate=False, dpooled_ch_off=0, dx_ch_off=0):
+    """backward of ops.avgpool_nhwc: dx (B, H, W, ld) window (+)= dpooled (B, H // r, W // r, ld) window / r^2; the dropped remainder rows and
+    columns are zeroed (left alone when accumulating)"""
+    _sc_windows('pcp_avgpool_nhwc_backward', c, (dpooled, dpooled_ch_off), (dx, dx_ch_off))
+    B, H, W, ld = dx.shape
+    assert tuple(dpooled.shape[:3]) == (B, H // r, W // r)
+    check(_lib.load().pcp_avgpool_nhwc_backward(_chan_ptr(dpooled, dpooled_ch_off), dpooled.shape[-1], B, H, W, int(c), int(r),
+                                                _chan_ptr(dx, dx_ch_off), ld, 1 if accumulate else 0, _stream()), 'pcp_avgpool_nhwc_backward')
+    return dx
+
+
+def sc_gate_backward(dout, t, x, s, c, dt=None, dz=None, dx=None, accumulate_dx=False, ds=None, dout_ch_off=0, t_ch_off=0, x_ch_off=0,
+                     s_ch_off=0, dt_ch_off=0, dz_ch_off=0, dx_ch_off=0, ds_ch_off=0):
+    """backward of ops.sc_gate (out = t * sigmoid(x + up(s))).  Returns (dt, dz, ds): dt None -> in place over dout's window; dz is the
+    gradient of x (a buffer of its own, allocated when None).  dx / accumulate_dx: the entry point's optional second destination, to which dz
+    is also written or added; _SCBottleneckTrain does not use it (it starts the gradient of b from dz itself), only the kernel tests do."""
+    B, H, W, _ = dout.shape
+    dev = dout.device
+    if dt is None:
+        dt, dt_ch_off = dout, dout_ch_off
+    if dz is None:
+        dz = torch.empty((B, H, W, c), dtype=torch.float32, device=dev)
+    if ds is None:
+        ds = torch.empty((B, s.shape[1], s.shape[2], c), dtype=torch.float32, device=dev)
+    _sc_windows('pcp_sc_gate_backward', c, (dout, dout_ch_off), (t, t_ch_off), (x, x_ch_off), (s, s_ch_off), (dt, dt_ch_off), (dz, dz_ch_off),
+                (dx, dx_ch_off), (ds, ds_ch_off))
+    for m in (t, x, dt, dz) + ((dx,) if dx is not None else ()):
+        assert tuple(m.shape[:3]) == (B, H, W)
+    assert s.shape[0] == B and tuple(ds.shape[:3]) == tuple(s.shape[:3])
+    check(_lib.load().pcp_sc_gate_backward(_chan_ptr(dout, dout_ch_off), dout.shape[-1], _chan_ptr(t, t_ch_off), t.shape[-1],
+                                           _chan_ptr(x, x_ch_off), x.shape[-1], _chan_ptr(s, s_ch_off), s.shape[-1], s.shape[1], s.shape[2],
+                                           _chan_ptr(dt, dt_ch_off), dt.shape[-1], _chan_ptr(dz, dz_ch_off), dz.shape[-1],
+                                           _chan_ptr(dx, dx_ch_off) if dx is not None else ctypes.c_void_p(0),
+                                           dx.shape[-1] if dx is not None else 0, 1 if accumulate_dx else 0, _chan_ptr(ds, ds_ch_off),
+                                           ds.shape[-1], B, H, W, int(c), _stream()), 'pcp_sc_gate_backward')
+    return dt, dz, ds
+
+
+def add_relu(z, res, c, out=None, z_ch_off=0, res_ch_off=0, out_ch_off=0):
+    """out = relu(z + res) on (..., ld) windows of c channels; out None: in place over z"""
+    if out is None:
+        out, out_ch_off = z, z_ch_off
+    _sc_windows('pcp_add_relu', c, (z, z_ch_off), (res, res_ch_off), (out, out_ch_off))
+    rows = z.numel() // z.shape[-1]
+    assert res.numel() // res.shape[-1] == rows and out.numel() // out.shape[-1] == rows
+    check(_lib.load().pcp_add_relu(_chan_ptr(z, z_ch_off), z.shape[-1], _chan_ptr(res, res_ch_off), res.shape[-1], _chan_ptr(out, out_ch_off),
+                                   out.shape[-1], rows, int(c), _stream()), 'pcp_add_relu')
+    return out
+
+
+def add_relu_backward(dout, out, c, dz=None, dz2=None, dout_ch_off=0, out_ch_off=0, dz_ch_off=0, dz2_ch_off=0):
+    """dz = dout * (out > 0); dz None: in place over dout.  dz2: an optional second copy."""
+    if dz is None:
+        dz, dz_ch_off = dout, dout_ch_off
+    _sc_windows('pcp_add_relu_backward', c, (dout, dout_ch_off), (out, out_ch_off), (dz, dz_ch_off), (dz2, dz2_ch_off))
+    rows = dout.numel() // dout.shape[-1]
+    for m in (out, dz) + ((dz2,) if dz2 is not None else ()):
+        assert m.numel() // m.shape[-1] == rows
+    check(_lib.load().pcp_add_relu_backward(_chan_ptr(dout, dout_ch_off), dout.shape[-1], _chan_ptr(out, out_ch_off), out.shape[-1],
+                                            _chan_ptr(dz, dz_ch_off), dz.shape[-1],
+                                            _chan_ptr(dz2, dz2_ch_off) if dz2 is not None else ctypes.c_void_p(0),
+                                            dz2.shape[-1] if dz2 is not None else 0, rows, int(c), _stream()), 'pcp_add_relu_backward')
+    return dz
