@@ -194,15 +194,23 @@ int pcp_masked_smooth_l1_rows(const float *fused, int32_t ld_f, const float *tea
  * the Linear layers run on pcp_pointwise, their gradients on pcp_pointwise / pcp_pointwise_wgrad, BatchNorm on pcp_bn_*.
  * Replaces dynamic_pillar_vfe.py:110-126 (features), :35-46 (scatter_max + concat) and their autograd (scatter_max backward
  * routes to one arg-max row per (pillar, channel); ties -> first row in bucket order), pointpillar_scatter.py:14-37.
- *   features      fbuf (N', FW) = [raw(num_raw), f_cluster(3), f_center(3), 0...], FW = 16 if num_raw + 6 <= 16 else 32 (num_raw 3, 4, 5, 11);
- *                 slot_pillar (N',) int32 pillar rank of each slot
+ *   features      fbuf (N', FW) = [raw(num_raw), f_cluster(3), f_center(3), 0...], FW = 16 if num_raw + 6 <= 16 else 32;
+ *                 slot_pillar (N',) int32 pillar rank of each slot.  Widths 3, 4, 5 and 11 have a kernel of their own; every other
+ *                 width runs pcp_pfn_train_features_w
+ *   features_w    the same rows (the same bits) for ANY raw width PCP_PFN_TRAIN_MIN_RAW <= num_raw <= PCP_PFN_TRAIN_MAX_RAW, the width a
+ *                 run-time argument: row_stride >= 1 + num_raw floats (the cloud may carry columns the PFN does not read), fw = 16 or 32
+ *                 with num_raw + 6 <= fw; anything else is PCP_ERR_ARG and nothing is launched
  *   mid           in1 (N', 64) = [relu(x0 * scale0 + shift0), per-pillar max of it]; arg0 (P, 32) int32 arg-max slot
  *   out           pillar_features (P, 64) (may be NULL), arg1 (P, 64), canvas (B, ny, nx, 64) rows (may be NULL)
  *   route_out     dz1 (kept_rows, 64) = 0 except dz1[arg1[p, c], c] = dcanvas[cell(p), c]  (or dpillar[p, c]; exactly one non-NULL)
  *   route_mid     da0 (N', 32) = din1[:, :32] + [slot == arg0] * sum over the pillar of din1[:, 32:]
  * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_PFN_TRAIN_MIN_RAW 3
+#define PCP_PFN_TRAIN_MAX_RAW 26 /* 26 + 6 = the 32 floats of the wider feature row */
 int pcp_pfn_train_features(const float *points, int64_t n, int32_t row_stride, int32_t num_raw, const pcp_grid_t *grid,
                            const void *vox_workspace, float *fbuf, int32_t *slot_pillar, void *stream);
+int pcp_pfn_train_features_w(const float *points, int64_t n, int32_t row_stride, int32_t num_raw, int32_t fw, const pcp_grid_t *grid,
+                             const void *vox_workspace, float *fbuf, int32_t *slot_pillar, void *stream);
 int pcp_pfn_train_mid(const pcp_grid_t *grid, const void *vox_workspace, int64_t n, const float *x0, const float *scale0,
                       const float *shift0, float *in1, int32_t *arg0, void *stream);
 int pcp_pfn_train_out(const pcp_grid_t *grid, const void *vox_workspace, int64_t n, const float *x1, const float *scale1,

@@ -100,6 +100,74 @@ __global__ __launch_bounds__(PT_THREADS) void k_pfnt_feat(FeatParams p) {
   }
 }
 
+// Any raw width (3 <= num_raw <= 26; the 10 columns the HD-map PillarFeatureNet reads out of a 12-column cloud): the arithmetic of k_pfnt_feat,
+// operation for operation, with the width and the padded row length as run-time arguments.  The raw columns of a row sit at float offset
+// stride * row + 1 (stride 13 for the 12-column cloud), aligned to 4 bytes and no more, so they are read with plain 4-byte SCALAR loads (one
+// lane per row; the lines of a row stay in L1 / L2 between the mean pass and this one) -- not staged through LDS: a row is touched twice and
+// the kernel is a small share of an iteration.  The stores stay 16 bytes wide: each quad of the row is put together in registers (the six
+// derived values chosen by compare-and-select, no run-time indexed array, so nothing goes to scratch) and written as one float4.
+__global__ __launch_bounds__(PT_THREADS) void k_pfnt_feat_w(FeatParams p, int num_raw, int fw) {
+  __shared__ int pl_start[PT_PILLARS + 1];
+  __shared__ long long sum_fx[PT_PILLARS][3];
+  __shared__ float mean[PT_PILLARS][3];
+  const int P = p.counters[0];
+  const int r0 = blockIdx.x * PT_PILLARS;
+  if (r0 >= P) return;
+  const int np = min(PT_PILLARS, P - r0);
+  const int tid = threadIdx.x;
+  for (int i = tid; i <= np; i += PT_THREADS) pl_start[i] = p.pillar_start[r0 + i];
+  for (int i = tid; i < PT_PILLARS * 3; i += PT_THREADS) (&sum_fx[0][0])[i] = 0;
+  __syncthreads();
+  const int s0 = pl_start[0], s1 = pl_start[np];
+  // 2^-24 fixed point sums: integer LDS atomics, so the order the lanes arrive in does not matter
+  for (int s = s0 + tid; s < s1; s += PT_THREADS) {
+    const float *row = p.points + (long long)p.bucket_order[s] * p.stride;
+    const int pl = find_pillar(pl_start, np, s);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const long long q = __double2ll_rn((double)row[1 + a] * 16777216.0);
+      atomicAdd(reinterpret_cast<unsigned long long *>(&sum_fx[pl][a]), (unsigned long long)q);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < np * 3; i += PT_THREADS) {
+    const int pl = i / 3, a = i % 3;
+    const int cnt = pl_start[pl + 1] - pl_start[pl];
+    mean[pl][a] = (float)(((double)sum_fx[pl][a] * (1.0 / 16777216.0)) / (double)cnt);
+  }
+  __syncthreads();
+  const int plane = p.g.nx * p.g.ny;
+  const float x_off = __fadd_rn(p.g.voxel_x * 0.5f, p.g.min_x);
+  const float y_off = __fadd_rn(p.g.voxel_y * 0.5f, p.g.min_y);
+  const float z_off = __fadd_rn(p.g.voxel_z * 0.5f, p.g.min_z);
+  for (int s = s0 + tid; s < s1; s += PT_THREADS) {
+    const int pl = find_pillar(pl_start, np, s);
+    const float *row = p.points + (long long)p.bucket_order[s] * p.stride;
+    const float x = row[1], y = row[2], z = row[3];
+    const int rem = p.pillar_cell[r0 + pl] % plane;
+    const float cx = (float)(rem / p.g.ny), cy = (float)(rem % p.g.ny);
+    const float d0 = __fsub_rn(x, mean[pl][0]);
+    const float d1 = __fsub_rn(y, mean[pl][1]);
+    const float d2 = __fsub_rn(z, mean[pl][2]);
+    const float d3 = __fsub_rn(x, __fadd_rn(__fmul_rn(cx, p.g.voxel_x), x_off));
+    const float d4 = __fsub_rn(y, __fadd_rn(__fmul_rn(cy, p.g.voxel_y), y_off));
+    const float d5 = __fsub_rn(z, z_off);
+    float4 *o = reinterpret_cast<float4 *>(p.fbuf + (long long)s * fw);
+    for (int q = 0; q < fw / 4; q++) {
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int k = 4 * q + j, d = k - num_raw;
+        float t = d == 0 ? d0 : d == 1 ? d1 : d == 2 ? d2 : d == 3 ? d3 : d == 4 ? d4 : d == 5 ? d5 : 0.f;   // d > 5: the zero padding
+        if (d < 0) t = row[1 + k];                                                                            // k < num_raw <= stride - 1
+        v[j] = t;
+      }
+      o[q] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    p.slot_pillar[s] = r0 + pl;
+  }
+}
+
 // The PillarFeatureNet variants no config of the reference uses (WITH_DISTANCE, USE_ABSLOTE_XYZ False, any raw width): the same feature
 // rows with the composition decided at run time (dynamic_pillar_vfe.py:117-126).  `fw` floats per row, zero padded.
 struct FeatAnyParams {
@@ -530,15 +598,37 @@ inline int pillar_blocks(int64_t max_pillars, int lanes_per_pillar) {
 
 extern "C" {
 
+static void fill_feat_params(FeatParams &p, const float *points, int32_t row_stride, const pcp_grid_t *grid, const WsView &v, float *fbuf,
+                             int32_t *slot_pillar) {
+  p.points = points; p.stride = row_stride; p.g = *grid;
+  p.bucket_order = v.bucket_order; p.pillar_cell = v.pillar_cell; p.pillar_start = v.pillar_start; p.counters = v.counters;
+  p.fbuf = fbuf; p.slot_pillar = slot_pillar;
+}
+
+int pcp_pfn_train_features_w(const float *points, int64_t n, int32_t row_stride, int32_t num_raw, int32_t fw, const pcp_grid_t *grid,
+                             const void *vox_workspace, float *fbuf, int32_t *slot_pillar, void *stream) {
+  if (!points || !grid || !vox_workspace || !fbuf || !slot_pillar || n < 0) return PCP_ERR_ARG;
+  if (num_raw < PCP_PFN_TRAIN_MIN_RAW || num_raw > PCP_PFN_TRAIN_MAX_RAW || row_stride < 1 + num_raw) return PCP_ERR_ARG;
+  if ((fw != 16 && fw != 32) || num_raw + 6 > fw) return PCP_ERR_ARG;
+  if (n == 0) return PCP_OK;
+  const WsView v = view_ws(vox_workspace, grid, n);
+  FeatParams p;
+  fill_feat_params(p, points, row_stride, grid, v, fbuf, slot_pillar);
+  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
+  const int64_t max_pillars = n < cells ? n : cells;
+  const int blocks = (int)((max_pillars + PT_PILLARS - 1) / PT_PILLARS);
+  hipLaunchKernelGGL(k_pfnt_feat_w, dim3(blocks), dim3(PT_THREADS), 0, (hipStream_t)stream, p, (int)num_raw, (int)fw);
+  PCP_CHECK_LAUNCH();
+  return PCP_OK;
+}
+
 int pcp_pfn_train_features(const float *points, int64_t n, int32_t row_stride, int32_t num_raw, const pcp_grid_t *grid,
                            const void *vox_workspace, float *fbuf, int32_t *slot_pillar, void *stream) {
   if (!points || !grid || !vox_workspace || !fbuf || !slot_pillar || n < 0 || row_stride < 1 + num_raw || num_raw < 3) return PCP_ERR_ARG;
   if (n == 0) return PCP_OK;
   const WsView v = view_ws(vox_workspace, grid, n);
   FeatParams p;
-  p.points = points; p.stride = row_stride; p.g = *grid;
-  p.bucket_order = v.bucket_order; p.pillar_cell = v.pillar_cell; p.pillar_start = v.pillar_start; p.counters = v.counters;
-  p.fbuf = fbuf; p.slot_pillar = slot_pillar;
+  fill_feat_params(p, points, row_stride, grid, v, fbuf, slot_pillar);
   const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
   const int64_t max_pillars = n < cells ? n : cells;
   const int blocks = (int)((max_pillars + PT_PILLARS - 1) / PT_PILLARS);
@@ -548,7 +638,8 @@ int pcp_pfn_train_features(const float *points, int64_t n, int32_t row_stride, i
     case 4: hipLaunchKernelGGL(k_pfnt_feat<4>, dim3(blocks), dim3(PT_THREADS), 0, s, p); break;
     case 5: hipLaunchKernelGGL(k_pfnt_feat<5>, dim3(blocks), dim3(PT_THREADS), 0, s, p); break;
     case 11: hipLaunchKernelGGL(k_pfnt_feat<11>, dim3(blocks), dim3(PT_THREADS), 0, s, p); break;
-    default: return PCP_ERR_UNSUPPORTED;
+    default:                                  // any other width: the run-time kernel (PCP_ERR_ARG above PCP_PFN_TRAIN_MAX_RAW columns)
+      return pcp_pfn_train_features_w(points, n, row_stride, num_raw, num_raw + 6 <= 16 ? 16 : 32, grid, vox_workspace, fbuf, slot_pillar, stream);
   }
   PCP_CHECK_LAUNCH();
   return PCP_OK;

@@ -35,6 +35,7 @@ class PFNLayerV2(nn.Module):
         return w.float(), b.detach().float()
 
 
+TRAIN_MIN_RAW, TRAIN_MAX_RAW = 3, 26  # raw widths pcp_pfn_train_features takes (PCP_PFN_TRAIN_MIN_RAW / _MAX_RAW, include/pcp_hip_train.h)
 SPARSE_MAX_FILL = 0.35        # points per cell below which the first backbone layer runs from the pillar list (pipeline mode)
 
 
@@ -54,6 +55,11 @@ class DynamicPillarVFE(VFETemplate):
         # (_forward_layers: pcp_pfn_features + pcp_pointwise + pcp_segment_max per PFNLayerV2)
         self.fused = (self.use_absolute_xyz and not self.with_distance and self.num_filters == [64, 64]
                       and num_point_features in (3, 4, 5, 11))
+        # the training PFN (train_path.VFETrain) takes the same composition at ANY raw width its 16 / 32-float feature rows hold (the 10
+        # columns pointpillar_jr_withmap reads among them).  `fused` is deliberately not widened with it: it also picks the inference
+        # kernel, and a width outside its four keeps running _forward_layers in eval
+        self.train_fused = (self.use_absolute_xyz and not self.with_distance and bool(self.use_norm) and self.num_filters == [64, 64]
+                            and TRAIN_MIN_RAW <= num_point_features <= TRAIN_MAX_RAW)
         if num_point_features < 3:
             raise NotImplementedError('a point row holds at least x, y, z')
         dims = [in_dim] + self.num_filters
@@ -78,7 +84,11 @@ class DynamicPillarVFE(VFETemplate):
         self._workspace = None
 
     def _forward_train(self, batch_dict):
-        if not self.fused:
+        if not self.train_fused:
+            if (self.use_absolute_xyz and not self.with_distance and self.use_norm and self.num_filters == [64, 64]
+                    and self.num_raw_point_features > TRAIN_MAX_RAW):
+                raise NotImplementedError('the HIP training path takes at most %d raw point features (a feature row holds 32 floats: the raw '
+                                          'columns and 6 derived ones); this VFE reads %d' % (TRAIN_MAX_RAW, self.num_raw_point_features))
             raise NotImplementedError('the HIP training path covers the PillarFeatureNet of the five configs (USE_ABSLOTE_XYZ, no '
                                       'WITH_DISTANCE, NUM_FILTERS [64, 64]); this variant has inference kernels only')
         from ...train_path import VFETrain

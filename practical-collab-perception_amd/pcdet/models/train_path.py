@@ -49,7 +49,7 @@ class VFETrain:
         w0 = l0.linear.weight.detach()                       # (32, F)
         dev = w0.device
         F = w0.shape[1]
-        fw = 16 if F <= 16 else 32                              # feature rows are padded to 16 / 32 floats (pcp_pfn_train_features)
+        fw = 16 if F <= 16 else 32                              # feature rows are padded to 16 / 32 floats (pcp_pfn_train_features): F <= 32
         w0p = torch.zeros((32, fw), dtype=torch.float32, device=dev)
         w0p[:, :F] = w0
         w1 = l1.linear.weight.detach()                       # (64, 64)

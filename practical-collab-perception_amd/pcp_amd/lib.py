@@ -303,6 +303,7 @@ SYMBOLS.update({
     'pcp_distill_loss': (c_i32, [vp, c_i32, vp, c_i32, c_i64, c_i32, c_f, c_f, vp, vp, vp, c_i32, c_i32, vp]),
     'pcp_masked_smooth_l1_rows': (c_i32, [vp, c_i32, vp, c_i32, c_i64, c_i32, c_f, vp, vp, vp]),
     'pcp_pfn_train_features': (c_i32, [vp, c_i64, c_i32, c_i32, ctypes.POINTER(Grid), vp, vp, vp, vp]),
+    'pcp_pfn_train_features_w': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, ctypes.POINTER(Grid), vp, vp, vp, vp]),
     'pcp_pfn_train_mid': (c_i32, [ctypes.POINTER(Grid), vp, c_i64, vp, vp, vp, vp, vp, vp]),
     'pcp_pfn_train_out': (c_i32, [ctypes.POINTER(Grid), vp, c_i64, vp, vp, vp, vp, vp, vp, vp]),
     'pcp_pfn_train_route_out_grad': (c_i32, [ctypes.POINTER(Grid), vp, c_i64, c_i64, vp, vp, vp, vp, vp]),

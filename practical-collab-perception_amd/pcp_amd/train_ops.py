@@ -583,10 +583,22 @@ def masked_smooth_l1_rows(fused, teacher, c, thresh=1e-3):
 # PFN (train mode)
 # ---------------------------------------------------------------------------------------------------------------------
 
+PFN_TRAIN_MIN_RAW, PFN_TRAIN_MAX_RAW = 3, 26        # PCP_PFN_TRAIN_MIN_RAW / _MAX_RAW of include/pcp_hip_train.h
+
+
 def pfn_train_features(points, vox, num_raw, fbuf, slot_pillar):
+    """widths 3, 4, 5, 11 on their own kernels, any other through pcp_pfn_train_features_w"""
     L = _lib.load()
     check(L.pcp_pfn_train_features(_p(points), vox.n, vox.row_stride, num_raw, ctypes.byref(vox.grid), _p(vox.workspace), _p(fbuf),
                                    _p(slot_pillar), _stream()), 'pcp_pfn_train_features')
+
+
+def pfn_train_features_w(points, vox, num_raw, fbuf, slot_pillar):
+    """the same rows for any raw width PFN_TRAIN_MIN_RAW .. PFN_TRAIN_MAX_RAW (the width is a run-time argument of the kernel); the row
+    length is fbuf's: 16 or 32 floats"""
+    L = _lib.load()
+    check(L.pcp_pfn_train_features_w(_p(points), vox.n, vox.row_stride, num_raw, fbuf.shape[1], ctypes.byref(vox.grid), _p(vox.workspace),
+                                     _p(fbuf), _p(slot_pillar), _stream()), 'pcp_pfn_train_features_w')
 
 
 def pfn_train_mid(vox, x0, vec0, in1, arg0):
