@@ -71,11 +71,7 @@ __device__ __forceinline__ f32x16 mfma32p(float a, float b, f32x16 c) { return _
 
 // The kernel is latency bound (a 64-pillar workgroup holds ~120 points = two chunks behind a chain of dependent global loads): ONE x tile
 // and an extra barrier per chunk keep the LDS at 39 KB, i.e. four workgroups per CU instead of three -- 267 -> 233 us on 1.44 M points.
-#ifdef PFN_DOUBLE_BUF
-constexpr int PFN_NBUF = 2, PFN_WGS = 3;
-#else
 constexpr int PFN_NBUF = 1, PFN_WGS = 4;
-#endif
 
 #ifdef PFN_STAMP
 __device__ unsigned long long pfn_dbg[32];
@@ -130,7 +126,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
 #pragma unroll
     for (int k = 0; k < NUM_RAW; k++) rawc[k] = row[1 + k];             // slot past the end: row 0, never used
   }
-#ifndef PFN_OLD_SWEEP1
   // xyz of slot s0 + tid for the mean sweep: requested now, with everything else that does not depend on the LDS set-up (the sweep used to
   // start its own bucket_order -> row chain behind two barriers: one more dependent global round trip on the workgroup's critical path)
   float xyz1[3] = {0.f, 0.f, 0.f};
@@ -143,7 +138,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
       xyz1[2] = row[3];
     }
   }
-#endif
   if (tid <= np) pl_start[tid] = ps_reg;
   for (int i = tid; i < PILLARS_PER_BLOCK * 3; i += PFN_THREADS) (&sum_fx[0][0])[i] = 0;
   for (int i = tid; i < PILLARS_PER_BLOCK * XLD; i += PFN_THREADS) xmax0[i] = 0.f;
@@ -187,17 +181,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
 
   PFN_STAMP_AT(2);
   // ---- sweep 1: per-pillar xyz sums in 2^-24 fixed point (integer adds commute -> deterministic) ---------------------------
-#ifdef PFN_OLD_SWEEP1
-  for (int s = s0 + tid; s < s1; s += PFN_THREADS) {
-    const float *row = p.points + (long long)p.bucket_order[s] * p.stride;
-    int pl = pillar_of(s);
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      long long q = __double2ll_rn((double)row[1 + a] * 16777216.0);
-      atomicAdd(reinterpret_cast<unsigned long long *>(&sum_fx[pl][a]), (unsigned long long)q);
-    }
-  }
-#else
   if (s0 + tid < s1) {
     const int pl = pillar_of(s0 + tid);
 #pragma unroll
@@ -215,7 +198,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
       atomicAdd(reinterpret_cast<unsigned long long *>(&sum_fx[pl][a]), (unsigned long long)q);
     }
   }
-#endif
   __syncthreads();
   for (int i = tid; i < np * 3; i += PFN_THREADS) {
     int pl = i / 3, a = i % 3;
@@ -282,13 +264,11 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; e++) acc[e] = 0.f;
-#ifndef PFN_OLD_EPILOGUE
     // the pillar of each of this lane's 16 accumulator rows: requested before the MFMAs, so the running-max updates behind them issue back
     // to back instead of one LDS round trip per row (stamps: 3 k cycles per chunk for 16 atomics)
     int ppl_e[16];
 #pragma unroll
     for (int e = 0; e < 16; e++) ppl_e[e] = pl_s[buf][rt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h];
-#endif
     const float *xa = &xs[buf][(rt * 32 + r) * XLD + 4 * h];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -300,14 +280,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
     }
     if (base == s0) PFN_STAMP_AT(7);
     const int o = ct * 32 + r;
-#ifdef PFN_OLD_EPILOGUE
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const int prow = rt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      const int ppl = pl_s[buf][prow];
-      if (ppl >= 0) atomicMax(&dmax[ppl][o], fkey(acc[e]));
-    }
-#else
     {
       // rows of one pillar are consecutive in this lane's row order: fold a run into ONE update (1.9 points per pillar: ~half the atomics)
       unsigned run = 0u;
@@ -326,7 +298,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
       }
       if (run_pl >= 0) atomicMax(&dmax[run_pl][o], run);
     }
-#endif
 #pragma unroll
     for (int k = 0; k < NUM_RAW; k++) rawc[k] = rawn[k];
     bo_n = bo_nn;
@@ -341,32 +312,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
   // ---- epilogue: out = relu(b1 + xmax0 . W1[:, 32:]^T + dmax) for rows = pillars rt2*32 .. +31 --------------------------------
   const int o = ct * 32 + r;
   const float bias = p.b1[o];
-#ifdef PFN_OLD_EPILOGUE
-  for (int rt2 = rt; rt2 * 32 < np; rt2 += 2) {
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.f;
-    const float *xa = &xmax0[(rt2 * 32 + r) * XLD + 4 * h];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const f32x4 a = *reinterpret_cast<const f32x4 *>(xa + 8 * j);
-      acc = mfma32p(a.x, wm[j].x, acc);
-      acc = mfma32p(a.y, wm[j].y, acc);
-      acc = mfma32p(a.z, wm[j].z, acc);
-      acc = mfma32p(a.w, wm[j].w, acc);
-    }
-    PFN_STAMP_AT(14);
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const int pl = rt2 * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      if (pl < np) {
-        const float v = fmaxf((bias + acc[e]) + fkey_inv(dmax[pl][o]), 0.0f);
-        if (p.pillar_features) p.pillar_features[(long long)(r0 + pl) * C1 + o] = v;
-        if (p.canvas) p.canvas[row_off[pl] + o] = v;
-      }
-    }
-  }
-#else
   // the finished value replaces its own dmax word (one owner per (pillar, channel)); after a barrier every pillar row leaves as 16-byte
   // stores: a wave instruction writes four whole 256-byte canvas rows (the first version stored 128-byte half rows a dword per lane, with
   // an LDS round trip in front of each: 11 - 15 k cycles of a 50 k workgroup)
@@ -400,7 +345,6 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
     if (p.pillar_features) *reinterpret_cast<f32x4 *>(p.pillar_features + (long long)(r0 + pl) * C1 + 4 * q) = v;
     if (p.canvas) *reinterpret_cast<f32x4 *>(p.canvas + row_off[pl] + 4 * q) = v;
   }
-#endif
   PFN_STAMP_AT(11);
 }
 

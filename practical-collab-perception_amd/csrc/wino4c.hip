@@ -18,115 +18,18 @@
 //   a slice = nine fenced blocks of four positions (eight MFMAs: k step 0 of the four, then k step 1 -- dependent MFMAs are four apart)
 //   LDS: 69 KB per workgroup (raw x2, V x2).
 //
-// Same arithmetic as k_wino4c (same products, same k order); only the output transform's summation runs per lane instead of per thread pair
-// -- identical operations in identical order, so the outputs are bit-identical to k_wino4c's (tests/test_gpu_ops.py).
-#include "pcp_common.h"
-#include <cstdlib>
+// Same arithmetic as k_wino4h (same products, same k order); only the output transform's summation runs per lane instead of per thread pair
+// -- identical operations in identical order, so the outputs are bit-identical to k_wino4h's (tests/test_gpu_ops.py).  What the two kernels
+// share -- item geometry, launch parameters, the 6-point transforms, the prologue's input transform -- is in wino4_common.h; the raw-patch
+// staging is the same text in both files.  One build form: the only compile-time switch left in the fused F(4x4) files is the stamp build
+// of k_wino4h and k_wino4f (DESIGN_HISTORY.md records what the removed schedules and timing-only builds measured).
+#include "wino4_common.h"
 #include <type_traits>
-
-#ifdef H4_STAMP
-__device__ unsigned long long c4_dbg[8192 * 8];               // [workgroup][stamp] (diagnostic build only)
-#define H4_STAMP_AT(slot)                                                                        \
-  do {                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    if (tid == 0 && blockIdx.x < 8192) {                                                         \
-      unsigned long long t_;                                                                     \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-      c4_dbg[blockIdx.x * 8 + (slot)] = t_;                                                      \
-    }                                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-  } while (0)
-// per-wave slice stamps of ONE workgroup (blockIdx.x == H4_STAMP_WG): [wave][slice][0: step start, 1..9: after block, 10: LDS drained, 11: after the barrier]
-__device__ unsigned long long c4_dbg2[4 * 64 * 12];
-#ifndef H4_STAMP_WG
-#define H4_STAMP_WG 1500
-#endif
-#define H4_STAMP2(slice, k)                                                                      \
-  do {                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    if (blockIdx.x == H4_STAMP_WG && lane == 0 && (slice) < 64) {                                \
-      unsigned long long t_;                                                                     \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-      c4_dbg2[(wave * 64 + (slice)) * 12 + (k)] = t_;                                            \
-    }                                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-  } while (0)
-#else
-#define H4_STAMP_AT(slot)
-#define H4_STAMP2(slice, k)
-#endif
 
 namespace {
 
-constexpr int H4_THREADS = 256;
-constexpr int H4_CK = 8;                                  // input channels per slice
-constexpr int H4_RP = 20;                                 // raw plane row pitch (floats)
-constexpr int H4_RAW_H = 18, H4_RAW_W = 18;               // 16 x 16 output pixels + halo
-constexpr int H4_RAW_PIX = H4_RAW_H * H4_RAW_W;
-constexpr int H4_PLANE = H4_RAW_H * H4_RP;                // 360 = 40 (mod 64)
-constexpr int H4_RAW_FLOATS = H4_CK * H4_PLANE;           // 2880
-constexpr int H4_VP = 160;                                // V position pitch: [8 k][16 tiles] + 32 (3 * VP = 32 mod 64: the two lane halves of
-                                                          // the column pass store to disjoint banks)
-constexpr int H4_V_FLOATS = 36 * H4_VP;                   // 5760
-constexpr int H4_MAIN_FLOATS = 2 * H4_RAW_FLOATS + 2 * H4_V_FLOATS;      // 17280
 constexpr int H4_LDS_FLOATS = H4_MAIN_FLOATS;              // 69 KB: no accumulator image (the output transform runs in registers)
-constexpr int H4_RAW_ITEMS = H4_RAW_PIX * 2;              // float4 items per slice (648)
-constexpr int H4_RAW_PER = (H4_RAW_ITEMS + H4_THREADS - 1) / H4_THREADS;   // 3
-constexpr int H4_WBN = 64;
-#ifndef H4_URING
-#define H4_URING 4                    // positions the U fragments are requested ahead (3: +0.5 % time, 2: +2 %)
-#endif
-#ifndef H4_VRING
-#define H4_VRING 2                    // BLOCKS (of four positions) the V fragments are read ahead: 3 spills seven registers into the loop (-7 % .. +37 % time)
-#endif
-#if !defined(H4_LATE_BARRIER) && !defined(H4_EARLY_BARRIER)
-#define H4_EARLY_BARRIER 1             // the slice barrier in front of the last position (-0.5 .. -1 % against the barrier at the end of the step;
-#endif                                 // -DH4_LATE_BARRIER keeps that form, which also carries the per-block stamps of the diagnostic build)
-
-struct H4Params {
-  const float *in;
-  const float *u;       // [cin/8][cout_pad/16][18 position pairs][64 lanes][4]
-  const float *bias;
-  float *out;
-  int batch, h, w;
-  int cin, cout, cout_pad;
-  int ld_in, ld_out;
-  int relu;
-  int tiles_x, tiles_y, n_spatial;
-  unsigned in_bytes, u_bytes;
-};
-
-__device__ __forceinline__ int xcd_remap_h4(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-// B^T x for the 6-point transform (points 0, +-1, +-2, inf).  Contraction is spelt out (no compiler-chosen fma grouping): k_wino4h and both
-// forms of k_wino4c run exactly these operations, so their outputs agree bit for bit.
-__device__ __forceinline__ void h4_bt6(const float d0, const float d1, const float d2, const float d3, const float d4, const float d5,
-                                       float (&t)[6]) {
-#pragma clang fp contract(off)
-  const float p = __builtin_fmaf(-4.f, d2, d4), q = __builtin_fmaf(-4.f, d1, d3);
-  const float r = d4 - d2, s = 2.f * (d3 - d1);
-  t[0] = __builtin_fmaf(4.f, d0, __builtin_fmaf(-5.f, d2, d4));
-  t[1] = p + q;
-  t[2] = p - q;
-  t[3] = r + s;
-  t[4] = r - s;
-  t[5] = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-}
-
-// A^T m for float4 lanes: 6 -> 4 (same rule: explicit fma)
-__device__ __forceinline__ void h4_at6v(const f32x4 m0, const f32x4 m1, const f32x4 m2, const f32x4 m3, const f32x4 m4, const f32x4 m5,
-                                        f32x4 (&y)[4]) {
-#pragma clang fp contract(off)
-  const f32x4 s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-  const f32x4 c2 = f32x4{2.f, 2.f, 2.f, 2.f}, c4 = f32x4{4.f, 4.f, 4.f, 4.f}, c8 = f32x4{8.f, 8.f, 8.f, 8.f};
-  y[0] = (m0 + s12) + s34;
-  y[1] = __builtin_elementwise_fma(c2, d34, d12);
-  y[2] = __builtin_elementwise_fma(c4, s34, s12);
-  y[3] = __builtin_elementwise_fma(c8, d34, d12) + m5;
-}
+constexpr int H4_VRING = 2;           // BLOCKS (of four positions) the V fragments are read ahead: 3 spills seven registers into the loop (-7 % .. +37 % time)
 
 // NW = waves per workgroup = 16-channel blocks per item.  NW = 4 (the default): 64-channel items, two workgroups per CU.  NW = 8 (opt-in,
 // see the launcher): 128-channel items, ONE eight-wave workgroup per CU -- the eight waves share one V image, so the input transform and the
@@ -148,25 +51,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5;
 
-  H4_STAMP_AT(0);
-#ifdef H4_STAMP
-  if (tid == 0 && blockIdx.x < 8192)
-    c4_dbg[blockIdx.x * 8 + 7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
-                                 ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);       // HW_ID, XCC_ID
-#endif
-#if defined(H4_PRIO_SLOT)
-  // the two workgroups of a CU sit in wave slots 0 and 1 of every SIMD (HW_ID[3:0]): the odd slot gets the higher issue priority
-  if (__builtin_amdgcn_s_getreg((3 << 11) | 4) & 1) __builtin_amdgcn_s_setprio(2);
-#endif
-  const int lid = xcd_remap_h4(blockIdx.x, gridDim.x);
-#ifdef H4_N_FAST
-  const int n_blocks = p.cout_pad / WBN;     // N tile as the fast index: the workgroups sharing a raw patch run together on one XCD
-  const int nt = lid % n_blocks;
-  int sp = lid / n_blocks;
-#else
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = lid / p.n_spatial;             // N tile is the slow index (weights stay in the XCD's L2)
   int sp = lid % p.n_spatial;
-#endif
   const int tile_x = sp % p.tiles_x;
   sp /= p.tiles_x;
   const int tile_y = sp % p.tiles_y;
@@ -191,9 +78,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   }
   f32x4 rreg[RAW_PER];
   auto raw_load = [&](int slice) {
-#ifdef H4_DIAG_NO_RLOAD
-    if (slice > 2) return;                                   // timing-only build: no raw loads in the main loop (the LDS stores of stale registers stay)
-#endif
     const int soff = slice * (H4_CK * 4);
 #pragma unroll
     for (int i = 0; i < RAW_PER; i++)
@@ -217,33 +101,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   const int t_tile = t_li & 15, t_ch = 2 * (wave & 3) + (t_li >> 4);
   const int t_src = t_ch * H4_PLANE + (4 * (t_tile >> 2) + 3 * h) * H4_RP + 4 * (t_tile & 3);
   const int t_dst = t_ch * 16 + t_tile + (3 * h) * H4_VP;
-  auto transform = [&](int rbuf, int vbuf) {
-    const float *src = rawb + rbuf * H4_RAW_FLOATS + t_src;
-    float *dst = vb + vbuf * H4_V_FLOATS + t_dst;
-    float wr[3][6];
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++) {
-      const f32x4 lo = *reinterpret_cast<const f32x4 *>(src + rr * H4_RP);
-      const float2 hi = *reinterpret_cast<const float2 *>(src + rr * H4_RP + 4);
-      h4_bt6(lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, wr[rr]);
-    }
-    float top[3][3], bot[3][3];
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(wr[rr][c]), __float_as_uint(wr[rr][3 + c]), false, false);
-        top[rr][c] = __uint_as_float(sw[0]);
-        bot[rr][c] = __uint_as_float(sw[1]);
-      }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      float o[6];
-      h4_bt6(top[0][c], top[1][c], top[2][c], bot[0][c], bot[1][c], bot[2][c], o);
-#pragma unroll
-      for (int i = 0; i < 6; i++) dst[(i * 6 + c) * H4_VP] = o[i];
-    }
-  };
+  const H4Transform transform{rawb, vb, t_src, t_dst};
 
   // ---- U fragments from global / L2: per position PAIR one f32x4 per lane = {pos 2q k0, pos 2q k1, pos 2q+1 k0, pos 2q+1 k1} of this
   // wave's 16 output channels --------------------------------------------------------------------------------------------------------------
@@ -255,9 +113,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   const int last = n_slices - 1;
   f32x4 uq[18];
   auto u_load = [&](int slice, int q) {
-#ifdef H4_DIAG_NO_ULOAD
-    if (slice > 0) return;                                   // timing-only build: the first slice's fragments stay in registers
-#endif
     const int so = u_base + min(slice, last) * u_slice + q * (64 * 4 * 4);
     uq[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, u_lane, so, 0));
   };
@@ -267,14 +122,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   for (int i = 0; i < 36; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int v_off = lane;
-#ifdef H4_EARLY_BARRIER
   // loop-carried operands: the first H4_VRING V fragments of the NEXT slice and the raw rows of the transform after it are requested right
   // behind the barrier, which sits in front of the slice's last position -- its eight MFMAs cover the LDS latency the next slice used to
-  // start with
+  // start with (-0.5 .. -1 % against the barrier at the end of the step)
   float vq[H4_VRING][4][2];
   f32x4 lo[3];
   float2 hi[3];
-#endif
 
   // One pipeline step = nine fenced blocks (wino4f's round-3 schedule): block pi = position pi's eight MFMAs + the V read H4_VRING positions
   // ahead + the U fragment URING positions ahead (wrapping into the next slice) + one ninth of the slice's other work.
@@ -282,19 +135,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
     constexpr bool LAST = decltype(last_tag)::value;
     const int cur = s & 1, nxt = cur ^ 1;
     const float *vsrc = vb + cur * H4_V_FLOATS + v_off;
-    const float *tsrc = rawb + nxt * H4_RAW_FLOATS + t_src;
     float *tdst = vb + nxt * H4_V_FLOATS + t_dst;
     float *rdstb = rawb + cur * H4_RAW_FLOATS;
-#ifndef H4_EARLY_BARRIER
-    float vq[H4_VRING][4][2];
-#pragma unroll
-    for (int i = 0; i < H4_VRING; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        vq[i][j][0] = vsrc[(4 * i + j) * H4_VP];
-        vq[i][j][1] = vsrc[(4 * i + j) * H4_VP + 64];
-      }
-#endif
     // block pi = positions 4 pi .. 4 pi + 3: k step 0 of the four, then k step 1 (an accumulator's two MFMAs are four instructions apart)
     auto mm = [&](int pi) {
       const f32x4 ua = uq[2 * pi], ub = uq[2 * pi + 1];
@@ -307,12 +149,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
       acc[4 * pi + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua.w, v[1][1], acc[4 * pi + 1], 0, 0, 0);
       acc[4 * pi + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(ub.y, v[2][1], acc[4 * pi + 2], 0, 0, 0);
       acc[4 * pi + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(ub.w, v[3][1], acc[4 * pi + 3], 0, 0, 0);
-#ifndef H4_DIAG_NO_VREAD
-      if (pi + H4_VRING < 9)
-#else
-      if (false)
-#endif
-      {
+      if (pi + H4_VRING < 9) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           v[j][0] = vsrc[(4 * (pi + H4_VRING) + j) * H4_VP];
@@ -328,9 +165,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
     };
     auto rstore = [&](int i) {
       const f32x4 v = rreg[i];
-#ifdef H4_DIAG_NO_RSTORE
-      if (v.x + v.y + v.z + v.w != 1.2345e30f) return;        // timing-only build: the loads stay (their values are consumed), the LDS stores go
-#endif
       rdstb[rdst[i]] = v.x;
       rdstb[rdst[i] + H4_PLANE] = v.y;
       rdstb[rdst[i] + 2 * H4_PLANE] = v.z;
@@ -338,17 +172,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
     };
     const auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
     fence();
-#ifndef H4_EARLY_BARRIER
-    f32x4 lo[3];
-    float2 hi[3];
-    if (!LAST) {
-#pragma unroll
-      for (int rr = 0; rr < 3; rr++) {
-        lo[rr] = *reinterpret_cast<const f32x4 *>(tsrc + rr * H4_RP);
-        hi[rr] = *reinterpret_cast<const float2 *>(tsrc + rr * H4_RP + 4);
-      }
-    }
-#endif
     float wr[3][6];
     float top[3][3], bot[3][3];
     auto other = [&](int blk) {
@@ -357,36 +180,27 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
       if (blk == 2 && RAW_PER > 2) rstore(RAW_PER > 2 ? 2 : 0);
       if (blk == 3) raw_load(min(s + 3, last));
       if (!tf) return;
-      if (blk == 1) h4_bt6(lo[0].x, lo[0].y, lo[0].z, lo[0].w, hi[0].x, hi[0].y, wr[0]);
-      if (blk == 2) h4_bt6(lo[1].x, lo[1].y, lo[1].z, lo[1].w, hi[1].x, hi[1].y, wr[1]);
-      if (blk == 3) h4_bt6(lo[2].x, lo[2].y, lo[2].z, lo[2].w, hi[2].x, hi[2].y, wr[2]);
+      if (blk == 1) bt6(lo[0].x, lo[0].y, lo[0].z, lo[0].w, hi[0].x, hi[0].y, wr[0]);
+      if (blk == 2) bt6(lo[1].x, lo[1].y, lo[1].z, lo[1].w, hi[1].x, hi[1].y, wr[1]);
+      if (blk == 3) bt6(lo[2].x, lo[2].y, lo[2].z, lo[2].w, hi[2].x, hi[2].y, wr[2]);
       if (blk == 4) {
 #pragma unroll
         for (int rr = 0; rr < 3; rr++)
 #pragma unroll
           for (int c = 0; c < 3; c++) {
-#ifdef H4_DIAG_NO_SWAP
-            top[rr][c] = wr[rr][c];                 // timing-only build: wrong values, no cross-lane exchange
-            bot[rr][c] = wr[rr][3 + c];
-#else
             const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(wr[rr][c]), __float_as_uint(wr[rr][3 + c]), false, false);
             top[rr][c] = __uint_as_float(sw[0]);
             bot[rr][c] = __uint_as_float(sw[1]);
-#endif
           }
       }
       if (blk >= 5 && blk <= 7) {
         const int c = blk - 5;
         float o[6];
-        h4_bt6(top[0][c], top[1][c], top[2][c], bot[0][c], bot[1][c], bot[2][c], o);
-#ifdef H4_DIAG_NO_VSTORE
-        if (o[0] + o[1] + o[2] + o[3] + o[4] + o[5] == 1.2345e30f)      // timing-only build: never true, keeps the arithmetic
-#endif
+        bt6(top[0][c], top[1][c], top[2][c], bot[0][c], bot[1][c], bot[2][c], o);
 #pragma unroll
         for (int i = 0; i < 6; i++) tdst[(i * 6 + c) * H4_VP] = o[i];
       }
     };
-#ifdef H4_EARLY_BARRIER
 #pragma unroll
     for (int blk = 0; blk < 8; blk++) {
       mm(blk);
@@ -428,27 +242,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
     } else {
       mm(8);                                 // no barrier behind the last block: the epilogue touches no LDS
     }
-#else
-    H4_STAMP2(s, 0);
-#pragma unroll
-    for (int blk = 0; blk < 9; blk++) {
-      mm(blk);
-      fence();
-#ifndef H4_DIAG_NO_OTHER
-      if (!LAST) {
-        other(blk);
-        fence();
-      }
-#endif
-      H4_STAMP2(s, 1 + blk);
-    }
-#ifdef H4_STAMP
-    __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): the stamped build separates the LDS drain from the barrier wait
-    H4_STAMP2(s, 10);
-#endif
-    __syncthreads();
-    H4_STAMP2(s, 11);
-#endif
   };
 
   // ---- prologue: raw(0), raw(1) -> LDS; V(0); rreg <- raw(2); first U fragments -----------------------------------------------------------
@@ -475,7 +268,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
   __syncthreads();
   if (tf) transform(0, 0);
   __syncthreads();
-#ifdef H4_EARLY_BARRIER
 #pragma unroll
   for (int i = 0; i < H4_VRING; i++)
 #pragma unroll
@@ -490,22 +282,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
       hi[rr] = *reinterpret_cast<const float2 *>(rawb + H4_RAW_FLOATS + t_src + rr * H4_RP + 4);
     }
   }
-#endif
 
-  H4_STAMP_AT(1);
-#if defined(H4_PRIO_MAIN)
-  __builtin_amdgcn_s_setprio(2);
-#endif
   for (int s = 0; s < last; s++) step_blocks(s, std::false_type{});
-  step_blocks(last, std::true_type{});        // ends with the barrier after which the LDS belongs to the epilogue
-#if defined(H4_PRIO_MAIN)
-  __builtin_amdgcn_s_setprio(0);
-#elif defined(H4_PRIO_EPI)
-  __builtin_amdgcn_s_setprio(2);
-#endif
+  step_blocks(last, std::true_type{});
 
   // ---- epilogue: Y = A^T M A per lane (tile = lane & 15, channel quad = lane >> 4), bias, ReLU, sixteen 16-byte streaming stores ------------
-  H4_STAMP_AT(2);
   {
     const int e_tile = lane & 15, e_kq = lane >> 4;
     const int n = n0 + 16 * wave + 4 * e_kq;
@@ -516,14 +297,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
 #pragma unroll
       for (int j = 0; j < 6; j++) {
         f32x4 y[4];
-        h4_at6v(acc[j], acc[6 + j], acc[12 + j], acc[18 + j], acc[24 + j], acc[30 + j], y);
+        at6v(acc[j], acc[6 + j], acc[12 + j], acc[18 + j], acc[24 + j], acc[30 + j], y);
 #pragma unroll
         for (int r = 0; r < 4; r++) t[r][j] = y[r];
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         f32x4 y[4];
-        h4_at6v(t[r][0], t[r][1], t[r][2], t[r][3], t[r][4], t[r][5], y);
+        at6v(t[r][0], t[r][1], t[r][2], t[r][3], t[r][4], t[r][5], y);
         if (py + r < p.h) {
           float *o = p.out + ((long long)(b * p.h + py + r) * p.w + px) * p.ld_out + n;
 #pragma unroll
@@ -542,25 +323,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wino4c(H4Params p)
       }
     }
   }
-  H4_STAMP_AT(6);
-}
-
-int h4_geom(const pcp_conv3x3_t *d, H4Params *p) {
-  if (!d || d->stride != 1) return PCP_ERR_UNSUPPORTED;
-  if (d->cin <= 0 || d->cin % H4_CK != 0 || d->cout <= 0 || d->cout_pad < d->cout || d->cout_pad % H4_WBN != 0) return PCP_ERR_ARG;
-  if (d->ld_in % 4 != 0 || d->ld_out % 4 != 0 || d->cout % 4 != 0 || d->batch <= 0 || d->in_h <= 0 || d->in_w <= 0) return PCP_ERR_ARG;
-  p->batch = d->batch; p->h = d->in_h; p->w = d->in_w;
-  p->cin = d->cin; p->cout = d->cout; p->cout_pad = d->cout_pad;
-  p->ld_in = d->ld_in; p->ld_out = d->ld_out; p->relu = d->relu;
-  p->tiles_x = (d->in_w + 15) / 16;
-  p->tiles_y = (d->in_h + 15) / 16;
-  p->n_spatial = d->batch * p->tiles_x * p->tiles_y;
-  const long long in_bytes = (long long)d->batch * d->in_h * d->in_w * d->ld_in * 4;
-  const long long u_bytes = (long long)(d->cin / H4_CK) * 36 * d->cout_pad * H4_CK * 4;       // [cin/8][cout_pad/16][18][64][4] floats
-  if (in_bytes > 0x7fffffffLL || u_bytes > 0x7fffffffLL) return PCP_ERR_UNSUPPORTED;
-  p->in_bytes = (unsigned)in_bytes;
-  p->u_bytes = (unsigned)u_bytes;
-  return PCP_OK;
 }
 
 }  // namespace
@@ -586,15 +348,6 @@ extern "C" int pcp_conv3x3_winograd4c(const pcp_conv3x3_t *d, const float *in, c
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }
-
-#ifdef H4_STAMP
-extern "C" int pcp_debug_read_c4(void *dst, size_t bytes) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(c4_dbg), bytes) == hipSuccess ? 0 : 3;
-}
-extern "C" int pcp_debug_read_c4_slices(void *dst, size_t bytes) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(c4_dbg2), bytes) == hipSuccess ? 0 : 3;
-}
-#endif
 
 extern "C" int pcp_conv3x3_winograd4c_plan(const pcp_conv3x3_t *d, double *executed_flops) {
   H4Params p;

@@ -66,22 +66,6 @@ def main():
     print('  CU %d timeline (start, main start, main end, end; slot):' % c0)
     for i in idx[:12]:
         print('    wg %5d  %8d %8d %8d %8d   slot %d' % (i, t[i, 0] - t0, t[i, 1] - t0, t[i, 2] - t0, t[i, 6] - t0, hw[i] & 15))
-    slices(L, cin // 8)
-
-
-def slices(L, n_slices):
-    buf = np.zeros(4 * 64 * 12, dtype=np.uint64)
-    L.pcp_debug_read_h4_slices.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    assert L.pcp_debug_read_h4_slices(buf.ctypes.data, buf.nbytes) == 0
-    t = buf.reshape(4, 64, 12).astype(np.int64)[:, :n_slices]
-    print('  one workgroup, per wave: mean ticks per slice (last slice excluded)')
-    print('  wave   blk0  blk1  blk2  blk3  blk4  blk5  blk6  blk7  blk8  lds-drain  barrier-wait   slice')
-    for w in range(4):
-        d = t[w, :n_slices - 1]
-        rel = (d[:, 1:] - d[:, :1]).mean(axis=0)
-        blocks = np.diff(np.concatenate([[0], rel[:9]]))
-        print('  %4d  ' % w + ' '.join('%5.0f' % v for v in blocks) + '   %7.0f  %10.0f  %8.0f' % (rel[9] - rel[8], rel[10] - rel[9], rel[10]))
-    print('  slice start times of wave 0 (relative):', ' '.join('%d' % (v - t[0, 0, 0]) for v in t[0, :, 0]))
 
 
 if __name__ == '__main__':
