@@ -1,5 +1,12 @@
-// a14 -- HunterJr point head, fused: bilinear sampling of the BEV map at every point -> feature MLP (C -> 32 -> C, Linear+BN+ReLU
-// twice) + residual -> the three point heads (C -> 3 | 3 | 2) in ONE kernel.
+// a14 -- HunterJr point head, fused: bilinear sampling of the BEV map at every point -> feature MLP (C -> H -> C, Linear+BN+ReLU
+// twice) + residual -> the three point heads (C -> 3 | 3 | 2) in ONE kernel.  The hidden width H is a template parameter: 32
+// (POINT_HEAD_HIDDEN_CHANNELS of the V2X-Sim configs) or 64 (the nuScenes corrector).
+//
+// LDS and occupancy (compiler resource remarks, gfx950; the CU has 160 KB):
+//   H = 32   73 224 bytes / workgroup, 96 VGPRs, 2 waves / SIMD   -> 2 workgroups per CU, as __launch_bounds__(256, 2) asks
+//   H = 64   77 320 bytes / workgroup, 106 VGPRs, 2 waves / SIMD  -> 2 workgroups per CU (154 640 bytes of the 160 KB)
+// H = 64 grows only H1s (32 x 68 floats): `red` keeps its 32-column size, phase 2 reduces the four waves' partials in two
+// 32-column halves through it (two more barriers per tile).  A 64-column `red` would take 92 KB and one workgroup per CU.
 //
 // Reference: pcdet/models/bev_layers/hunter_toolbox.py:8-39,94-127 (interpolate_points_feat_from_bev_img) and
 // pcdet/models/bev_layers/hunter_jr.py:78-101 (HunterPointHead.forward).  Unfused this is five launches that stream the
@@ -7,8 +14,9 @@
 // 32 points' features in LDS: sampled rows are written to HBM once (the scatter-mean needs them later), the hidden and final
 // activations never leave the CU, and only (N, 8) head values come out.
 //   phase 1  per-point corner indices / weights, then the 4-row gather + blend -> LDS tile F[32][C] (+ global pf)
-//   phase 2  H1 = relu(F W1^T + b1)      fp32 MFMA, K = C split over the 4 waves, partials reduced through LDS
-//   phase 3  F <- relu(H1 W2^T + b2) + F  fp32 MFMA, 3 column tiles per wave, in place (final features)
+//   phase 2  H1 = relu(F W1^T + b1)      fp32 MFMA, K = C split over the 4 waves (H / 32 accumulators each), partials reduced
+//                                        through LDS, 32 columns at a time
+//   phase 3  F <- relu(H1 W2^T + b2) + F  fp32 MFMA (K = H), 3 column tiles per wave, in place (final features)
 //   phase 4  head8 = F Wh^T + bh         one dot product per thread (VALU)
 // Sampling arithmetic is bitwise that of k_bilinear / the reference (products and sums in its order, no FMA contraction).
 #include "pcp_common.h"
@@ -17,9 +25,8 @@ namespace {
 
 constexpr int PH_BM = 32;           // points per workgroup
 constexpr int PH_C = 384;           // BEV channels (num_bev_features of the five configs)
-constexpr int PH_H = 32;            // hidden width (POINT_HEAD_HIDDEN_CHANNELS: [32])
 constexpr int PH_LDF = PH_C + 4;    // padded row: a ds_read_b128 group's 16 lanes hit distinct slots
-constexpr int PH_LDH = PH_H + 4;
+// the hidden width (POINT_HEAD_HIDDEN_CHANNELS: [32] or [64]) is k_point_head's template parameter PH_H; the H1 row is padded like F's
 constexpr int PH_NOUT = 8;
 
 struct PointHeadParams {
@@ -29,8 +36,8 @@ struct PointHeadParams {
   long long n;
   int stride;
   float min_x, min_y, pix_x, pix_y;
-  const float *w1, *b1;   // [32][C], [32]
-  const float *w2, *b2;   // [C][32], [C]
+  const float *w1, *b1;   // [H][C], [H]
+  const float *w2, *b2;   // [C][H], [C]
   const float *wh, *bh;   // [8][C], [8]
   float *pf;              // (n, ld_pf) sampled features
   int ld_pf;
@@ -55,10 +62,14 @@ __device__ __forceinline__ f32x16 mfma_ph(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
+template <int PH_H>
 __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
+  static_assert(PH_H == 32 || PH_H == 64, "hidden width: one or two 32-column MFMA tiles");
+  constexpr int PH_LDH = PH_H + 4;
+  constexpr int PH_NT = PH_H / 32;           // 32-column tiles of the hidden layer
   __shared__ __attribute__((aligned(16))) float Fs[PH_BM * PH_LDF];
   __shared__ __attribute__((aligned(16))) float H1s[PH_BM * PH_LDH];
-  __shared__ float red[4][PH_BM][PH_H + 1];
+  __shared__ float red[4][PH_BM][32 + 1];    // one 32-column tile of partials per wave, whatever PH_H
   __shared__ long long c_off[PH_BM][4];     // float offsets of the four corner rows (Ia, Ib, Ic, Id)
   __shared__ float c_w[PH_BM][4];
   __shared__ int c_ok[PH_BM];
@@ -150,37 +161,47 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
 #ifndef PH_DIAG_GATHER_ONLY
   // ---- phase 2: H1 partial over this wave's K quarter (96 channels = 12 groups of 8) -----------------------------------------
   {
-    f32x16 acc;
+    f32x16 acc[PH_NT];
 #pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.f;
+    for (int t = 0; t < PH_NT; t++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
     const float *asrc = Fs + r * PH_LDF + wave * 96 + 4 * h;
-    const float *bsrc = p.w1 + r * PH_C + wave * 96 + 4 * h;          // B[k][n = r] = W1[r][k]
+    const float *bsrc = p.w1 + r * PH_C + wave * 96 + 4 * h;          // B[k][n = 32 t + r] = W1[32 t + r][k]
 #pragma unroll 4
     for (int g = 0; g < 12; g++) {
       f32x4 a = *reinterpret_cast<const f32x4 *>(asrc + g * 8);
-      f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + g * 8);
-      acc = mfma_ph(a.x, bq.x, acc);
-      acc = mfma_ph(a.y, bq.y, acc);
-      acc = mfma_ph(a.z, bq.z, acc);
-      acc = mfma_ph(a.w, bq.w, acc);
-    }
 #pragma unroll
-    for (int e = 0; e < 16; e++) red[wave][(e & 3) + 8 * (e >> 2) + 4 * h][r] = acc[e];
-  }
-  __syncthreads();
-  for (int idx = tid; idx < PH_BM * PH_H; idx += 256) {
-    const int m = idx / PH_H, nn = idx % PH_H;
-    float v = red[0][m][nn] + red[1][m][nn] + red[2][m][nn] + red[3][m][nn] + p.b1[nn];
-    H1s[m * PH_LDH + nn] = fmaxf(v, 0.f);
+      for (int t = 0; t < PH_NT; t++) {
+        f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + t * 32 * PH_C + g * 8);
+        acc[t] = mfma_ph(a.x, bq.x, acc[t]);
+        acc[t] = mfma_ph(a.y, bq.y, acc[t]);
+        acc[t] = mfma_ph(a.z, bq.z, acc[t]);
+        acc[t] = mfma_ph(a.w, bq.w, acc[t]);
+      }
+    }
+    // the four waves' partials go through `red` one 32-column tile at a time (PH_H = 64: red is reused, not doubled)
+#pragma unroll
+    for (int t = 0; t < PH_NT; t++) {
+      if (t) __syncthreads();                                          // the previous tile's sums have been read
+#pragma unroll
+      for (int e = 0; e < 16; e++) red[wave][(e & 3) + 8 * (e >> 2) + 4 * h][r] = acc[t][e];
+      __syncthreads();
+      for (int idx = tid; idx < PH_BM * 32; idx += 256) {
+        const int m = idx / 32, nn = idx % 32;
+        float v = red[0][m][nn] + red[1][m][nn] + red[2][m][nn] + red[3][m][nn] + p.b1[t * 32 + nn];
+        H1s[m * PH_LDH + t * 32 + nn] = fmaxf(v, 0.f);
+      }
+    }
   }
   __syncthreads();
 
 #ifndef PH_DIAG_SKIP34
   // ---- phase 3: final = relu(H1 W2^T + b2) + F, three 32-channel column tiles per wave, in place -----------------------------
   {
-    f32x4 a[4];
+    f32x4 a[PH_H / 8];
 #pragma unroll
-    for (int g = 0; g < 4; g++) a[g] = *reinterpret_cast<const f32x4 *>(H1s + r * PH_LDH + g * 8 + 4 * h);
+    for (int g = 0; g < PH_H / 8; g++) a[g] = *reinterpret_cast<const f32x4 *>(H1s + r * PH_LDH + g * 8 + 4 * h);
 #pragma unroll
     for (int j = 0; j < 3; j++) {
       const int ct = wave * 3 + j;
@@ -189,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[e] = 0.f;
 #pragma unroll
-      for (int g = 0; g < 4; g++) {
+      for (int g = 0; g < PH_H / 8; g++) {
         f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + g * 8);
         acc = mfma_ph(a[g].x, bq.x, acc);
         acc = mfma_ph(a[g].y, bq.y, acc);
@@ -317,7 +338,7 @@ static int point_head_launch(const float *bev, int32_t batch, int32_t h, int32_t
                              float *head, const int32_t *order, const int32_t *order_count, float *points_mut, float flow_thresh,
                              unsigned char *dyn_mask, void *stream_) {
   if (!bev || !w1 || !b1 || !w2 || !b2 || !wh || !bh || !pf || !head || n < 0 || batch <= 0 || h <= 0 || w <= 0) return PCP_ERR_ARG;
-  if (c != PH_C || hidden != PH_H || n_out != PH_NOUT) return PCP_ERR_UNSUPPORTED;
+  if (c != PH_C || (hidden != 32 && hidden != 64) || n_out != PH_NOUT) return PCP_ERR_UNSUPPORTED;
   if ((ld_bev & 3) || (ld_pf & 3) || row_stride < 3 || (((uintptr_t)bev) & 15) || (((uintptr_t)pf) & 15)) return PCP_ERR_ARG;
   if (n == 0) return PCP_OK;
   if (!points) return PCP_ERR_ARG;
@@ -330,7 +351,10 @@ static int point_head_launch(const float *bev, int32_t batch, int32_t h, int32_t
   p.order = order; p.order_count = order_count;
   p.points_mut = points_mut; p.flow_thresh = flow_thresh; p.dyn_mask = dyn_mask;
   long long blocks = (n + PH_BM - 1) / PH_BM;
-  hipLaunchKernelGGL(k_point_head, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p);
+  if (hidden == 32)
+    hipLaunchKernelGGL(k_point_head<32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p);
+  else
+    hipLaunchKernelGGL(k_point_head<64>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }

@@ -16,7 +16,7 @@ from ..utils import common_utils
 
 LAYOUT_OF = {'V2XSimDataset_CAR': 'car', 'V2XSimDataset_RSU': 'car', 'V2XSimDataset_EGO': 'lately', 'V2XSimDataset_EGO_LATE': 'lately',
              'V2XSimDataset_EGO_EARLY': 'early', 'V2XSimDataset_EGO_DISCO': 'disco'}
-AGENTS_OF = {'car': 1, 'lately': 1, 'early': 6, 'disco': 6}
+AGENTS_OF = {'car': 1, 'lately': 1, 'early': 6, 'disco': 6, 'nusc_map': 1}
 
 
 class SyntheticV2XDataset(DatasetInfo, Dataset):
@@ -32,6 +32,9 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         self.points_per_agent = int(syn.get('POINTS_PER_AGENT', 60000))
         self.num_frames = int(syn.get('NUM_FRAMES', 16))
         self.distribution = syn.get('DISTRIBUTION', 'uniform')
+        if dataset_cfg.DATASET == 'NuScenesDataset' and len(enc.used_feature_list) == 12:
+            self.layout = 'nusc_map'       # the five HD-map layers behind the timestamp (synth.nusc_cloud with_map)
+            self.points_per_agent = int(syn.get('POINTS_PER_FRAME', self.points_per_agent))   # the nuScenes configs size the frame
 
     @property
     def mode(self):
@@ -44,7 +47,10 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         parts = []
         n_agents = AGENTS_OF[self.layout]
         for a in range(n_agents):
-            c = synth.agent_cloud(agent=100 * index + a, n_points=self.points_per_agent, layout=self.layout, dist=self.distribution)
+            if self.layout == 'nusc_map':
+                c = synth.nusc_cloud(index, self.points_per_agent, with_map=True, dist=self.distribution)
+            else:
+                c = synth.agent_cloud(agent=100 * index + a, n_points=self.points_per_agent, layout=self.layout, dist=self.distribution)
             if self.layout == 'disco':
                 c[:, -1] = float(a)
             parts.append(c)

@@ -93,6 +93,7 @@ class HunterJr(PackedModule):
         self.meta_sweep_col = model_cfg.get('META_POINTS_FEAT_LOCATION_SWEEP_IDX', -2)
         self.meta_inst_col = model_cfg.get('META_POINTS_FEAT_LOCATION_INSTANCE_IDX', -1)
         self.sorted_gather = True          # MI355X knob: point-head gathers in spatially sorted order (output unchanged)
+        self.fused_point_head = True       # MI355X knob: False runs the five-launch chain (sample, two pointwise, heads, flow, re-sample)
         self.conv_weightor = nn.Sequential(
             conv_bn_relu(2 * num_bev_features, 2 * num_bev_features, padding=1, norm_layer=norm),
             nn.Conv2d(2 * num_bev_features, 2, kernel_size=3, padding=1))
@@ -106,8 +107,8 @@ class HunterJr(PackedModule):
         heads_b = torch.cat([ph.seg[0].bias, ph.reg_flow3d[0].bias, ph.instance_embedding[0].bias], 0).detach().float()
         heads = PackedConv('plain', heads_w.shape[1], heads_w.shape[0], False, pack.pack_plain(heads_w, heads_b))
         fused = None
-        if len(lf) == 6 and heads_w.shape == (8, 384) and lf[0].weight.shape == (32, 384):
-            # plain row-major folded weights for the fused point-head kernel
+        if len(lf) == 6 and heads_w.shape == (8, 384) and tuple(lf[0].weight.shape) in ((32, 384), (64, 384)):
+            # plain row-major folded weights for the fused point-head kernel (hidden width 32 or 64)
             f1 = pack.fold_bn(lf[0].weight.detach().float(), lf[1].weight.detach(), lf[1].bias.detach(), lf[1].running_mean,
                               lf[1].running_var, lf[1].eps)
             f2 = pack.fold_bn(lf[3].weight.detach().float(), lf[4].weight.detach(), lf[4].bias.detach(), lf[4].running_mean,
@@ -147,7 +148,7 @@ class HunterJr(PackedModule):
         pk['conv_input'].run(x, out=cat, out_ch_off=0)
         min_xy = self.point_cloud_range[:2]
         pix = [np.float32(self.voxel_size[0]) * self.bev_image_stride, np.float32(self.voxel_size[1]) * self.bev_image_stride]
-        if pk['fused'] is not None and C == 384:
+        if pk['fused'] is not None and C == 384 and self.fused_point_head:
             # visit the points in the pillariser's bucket order (spatially sorted): the 4 x 384-float gathers of neighbouring
             # points then hit L2; results are written at the original rows, so the output does not change
             stash = batch_dict.get('_pcp_vfe', None)

@@ -3,7 +3,12 @@ with six heads and vel / iou branches) on seeded synthetic 7-column clouds, B = 
 the box counts per step, as in tools/test.py).  Prints a per-layer table of the backbone (B = 4, CUDA events around every launch group)
 and, last, one JSON line.
 
-    python practical-collab-perception_amd/tools/bench_nusc.py [--points 260000] [--steps 20] [--warmup 5]
+    python practical-collab-perception_amd/tools/bench_nusc.py [--points 260000] [--steps 20] [--warmup 5] [--config nomap|corr_withmap]
+                                                                [--unfused-point-head]
+
+--config corr_withmap times pointpillar_jr_corr_withmap instead (13-column clouds, HunterJr between the backbone and the head; the corrector
+moves points in place, so every step runs on a fresh device copy of the cloud, made inside the timed region); --unfused-point-head runs its
+point head as the five-launch chain instead of the fused kernel.
 
 Synthetic weights (pcp_amd.synth.fill_state_dict, gain 1.6): the arithmetic does not depend on them, only the number of boxes that reach
 the NMS does.  A 10-sweep nuScenes cloud holds about 250 000 - 300 000 points.
@@ -24,11 +29,11 @@ from pcdet.models import DatasetInfo, build_network  # noqa: E402
 from pcp_amd import lib, ops, synth  # noqa: E402
 from pcp_amd.conv_dispatch import conv_algo  # noqa: E402
 
-YAML = os.path.join(HERE, 'cfgs', 'nuscenes_models', 'pointpillar_jr_nomap.yaml')
+CFGS = os.path.join(HERE, 'cfgs', 'nuscenes_models')
 
 
-def build_model():
-    cfg = cfg_from_yaml_file(YAML, EasyDict())
+def build_model(config='nomap'):
+    cfg = cfg_from_yaml_file(os.path.join(CFGS, 'pointpillar_jr_%s.yaml' % config), EasyDict())
     vs = [p['VOXEL_SIZE'] for p in cfg.DATA_CONFIG.DATA_PROCESSOR if 'VOXEL_SIZE' in p][0]
     ds = DatasetInfo(cfg.CLASS_NAMES, cfg.DATA_CONFIG.POINT_CLOUD_RANGE, vs, len(cfg.DATA_CONFIG.POINT_FEATURE_ENCODING.used_feature_list))
     model = build_network(cfg.MODEL, len(cfg.CLASS_NAMES), ds)
@@ -47,7 +52,8 @@ def time_steps(model, pts, batch_size, steps, warmup):
                 torch.cuda.synchronize()
                 start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 start.record()
-            preds, _ = model({'points': dev_pts, 'batch_size': batch_size, 'metadata': [{}] * batch_size})
+            pts_in = dev_pts.clone() if getattr(model, 'corrector', None) is not None else dev_pts
+            preds, _ = model({'points': pts_in, 'batch_size': batch_size, 'metadata': [{}] * batch_size})
             boxes = sum(int(p['pred_boxes'].shape[0]) for p in preds)
         end.record()
         torch.cuda.synchronize()
@@ -112,11 +118,19 @@ def main():
     ap.add_argument('--points', type=int, default=260000)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--config', default='nomap', choices=['nomap', 'corr_withmap'])
+    ap.add_argument('--unfused-point-head', action='store_true', help='corr_withmap: the five-launch point head instead of the fused kernel')
     args = ap.parse_args()
-    model = build_model()
-    res = {'metric': 'pointpillar_jr_nomap', 'points_per_frame': args.points, 'cloud': 'synth.nusc_cloud ring, seeded',
+    model = build_model(args.config)
+    res = {'metric': 'pointpillar_jr_' + args.config, 'points_per_frame': args.points, 'cloud': 'synth.nusc_cloud ring, seeded',
            'conv_algo': conv_algo()}
-    clouds = [synth.nusc_cloud(b, args.points, dist='ring') for b in range(4)]
+    corr = getattr(model, 'corrector', None)
+    if corr is not None:
+        corr.fused_point_head = not args.unfused_point_head
+        res['point_head'] = 'fused' if corr.fused_point_head and corr.packed()['fused'] is not None else 'five launches'
+    elif args.unfused_point_head:
+        ap.error('--unfused-point-head needs a config with a corrector')
+    clouds = [synth.nusc_cloud(b, args.points, with_map=args.config != 'nomap', dist='ring') for b in range(4)]
     for B in (1, 4):
         pts = synth.collate(clouds[:B])
         ms, boxes = time_steps(model, pts, B, args.steps, args.warmup)

@@ -1,35 +1,89 @@
-"""Micro-benchmark of the fused HunterJr point head: python tools/bench_pointhead.py"""
+"""Micro-benchmark of the fused HunterJr point head: python tools/bench_pointhead.py [--hidden 32|64] [--cloud car|nusc]
+[--points N per frame] [--frames B] [--stage]
+
+Without options: the fused kernel alone at hidden 32 on 4 x 60 000 'car' points, in index order and in the pillariser's bucket order.
+--stage times the whole point-head stage of HunterJr.forward (sampling through the re-sampling of the corrected rows, the points moved in
+place) three ways: fused in index order, fused in bucket order, and the five-launch chain (sample, two pointwise, heads, flow, re-sample).
+Every timed call gets its own copy of the cloud (the stage moves points), made outside the timed region."""
+import argparse
 import os
 import sys
 
-import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from pcp_amd import ops, synth  # noqa: E402
+from pcp_amd import lib, ops, pack, synth  # noqa: E402
+
+REPS = 10
+
+
+def timed(fn, clouds):
+    """mean us per call of fn(points) over clouds[3:] after three warm-up calls on clouds[:3]"""
+    for c in clouds[:3]:
+        fn(c)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for c in clouds[3:]:
+        fn(c)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1000.0 / len(clouds[3:])
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--hidden', type=int, default=32, choices=[32, 64])
+    ap.add_argument('--cloud', default='car', choices=['car', 'nusc'])
+    ap.add_argument('--points', type=int, default=60000, help='points per frame')
+    ap.add_argument('--frames', type=int, default=4)
+    ap.add_argument('--stage', action='store_true', help='time the whole stage (flow correction and re-sampling included), fused and unfused')
+    args = ap.parse_args()
     dev = 'cuda:0'
-    B, H, W, C = 4, 128, 128, 384
+    B, H, W, C, hid = args.frames, 128, 128, 384, args.hidden
     cat = torch.randn((B, H, W, 2 * C), device=dev)
-    pts = torch.from_numpy(synth.collate([synth.agent_cloud(agent=f, n_points=60000, layout='car') for f in range(B)])).to(dev)
-    grid = ops.make_grid([-51.2, -51.2, -8, 51.2, 51.2, 0], [0.2, 0.2, 8.0], [512, 512, 1], B)
+    if args.cloud == 'nusc':
+        frames = [synth.nusc_cloud(f, args.points, with_map=True, dist='ring') for f in range(B)]
+        rng = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+    else:
+        frames = [synth.agent_cloud(agent=f, n_points=args.points, layout='car') for f in range(B)]
+        rng = [-51.2, -51.2, -8, 51.2, 51.2, 0]
+    pts = torch.from_numpy(synth.collate(frames)).to(dev)
+    grid = ops.make_grid(rng, [0.2, 0.2, 8.0], [512, 512, 1], B)
     vox = ops.voxelize(pts, grid, want_inverse=False, want_counts=False)
     order = ops.voxelize_row_order(vox)
-    w = [torch.randn(s, device=dev) * 0.05 for s in ((32, C), (32,), (C, 32), (C,), (8, C), (8,))]
-    for name, od in (('index order', None), ('bucket order', order)):
-        for _ in range(3):
-            ops.hunter_point_head(cat, pts, [-51.2, -51.2], [0.8, 0.8], *w, channels=C, order=od)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            ops.hunter_point_head(cat, pts, [-51.2, -51.2], [0.8, 0.8], *w, channels=C, order=od)
-        e1.record()
-        torch.cuda.synchronize()
-        print('%-14s %8.1f us' % (name, e0.elapsed_time(e1) * 100))
+    w = [torch.randn(s, device=dev) * 0.05 for s in ((hid, C), (hid,), (C, hid), (C,), (8, C), (8,))]
+    min_xy, pix = [-51.2, -51.2], [0.8, 0.8]
+    if not args.stage:
+        for name, od in (('index order', None), ('bucket order', order)):
+            us = timed(lambda p: ops.hunter_point_head(cat, p, min_xy, pix, *w, channels=C, order=od), [pts] * (3 + REPS))
+            print('%-14s %8.1f us' % (name, us))
+        return
+    from pcdet.models.convnet import PackedConv
+    mlp = [PackedConv('plain', a.shape[1], a.shape[0], True, pack.pack_plain(a, b)) for a, b in ((w[0], w[1]), (w[2], w[3]))]
+    heads = PackedConv('plain', C, 8, False, pack.pack_plain(w[4], w[5]))
+
+    def chain(p):
+        pf = ops.bev_sample_bilinear(cat, p, min_xy, pix, channels=C)
+        h = ops.pointwise(pf, mlp[0].w, mlp[0].b, lib.PW_PLAIN, mlp[0].cin, mlp[0].cout, mlp[0].cout_pad, relu=True)
+        h = ops.pointwise(h, mlp[1].w, mlp[1].b, lib.PW_PLAIN, mlp[1].cin, mlp[1].cout, mlp[1].cout_pad, relu=True, residual=pf)
+        head8 = heads.run(h)
+        dyn = ops.hunter_apply_flow(p, head8, 0.3)
+        ops.bev_sample_bilinear(cat, p, min_xy, pix, out=pf, row_mask=dyn, channels=C)
+        return dyn
+
+    clouds = lambda: [pts.clone() for _ in range(3 + REPS)]
+    n = pts.shape[0]
+    dyn = chain(pts.clone())
+    tag = 'hidden %d, %s cloud, N = %d (%d x %d), %.1f %% of the rows corrected' % (hid, args.cloud, n, B, args.points,
+                                                                                    100.0 * float(dyn.float().mean()))
+    print('point-head stage, ' + tag)
+    rows = [('fused, index order', lambda p: ops.hunter_point_head(cat, p, min_xy, pix, *w, channels=C, flow_thresh=0.3)),
+            ('fused, bucket order', lambda p: ops.hunter_point_head(cat, p, min_xy, pix, *w, channels=C, order=order, flow_thresh=0.3)),
+            ('five-launch chain', chain)]
+    for name, fn in rows:
+        print('  %-20s %9.1f us' % (name, timed(fn, clouds())))
 
 
 if __name__ == '__main__':
