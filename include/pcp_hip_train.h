@@ -329,7 +329,7 @@ typedef struct {
   int32_t stride, n_fg, n_local, n_inst, c;
   int32_t batch, max_inst, num_sweeps;
   const float *points;                          /* rows BEFORE the in-place correction */
-  const float *gt_boxes;                        /* (batch, max_inst, 8) */
+  const float *gt_boxes;                        /* (batch, max_inst, gt_stride): the centre x, y in columns 0, 1 */
   const float *instances_tf;                    /* (batch, max_inst, num_sweeps, 3, 4) */
   const int32_t *fg_idx, *fg_local, *local_key, *local_inst, *inst_key;
   const float *head;                            /* (n, ld_head): [cls(3) | flow(3) | embedding(2)] */
@@ -352,6 +352,8 @@ typedef struct {
                                                    l_dtl_locals_feat, their sum */
   int32_t *labels;                              /* (n): point class targets 0 background / 1 static / 2 moving foreground */
   float *tgt_embedding, *tgt_offset;            /* optional (n_fg, 2) / (n_fg, 3) */
+  int32_t gt_stride;                            /* floats per gt_boxes row, PCP_GT_BOX_MIN_WIDTH .. PCP_GT_BOX_MAX_WIDTH (10 with velocity);
+                                                   0 = 8, the rows of the V2X-Sim models */
 } pcp_hunter_loss_t;
 
 size_t pcp_hunter_loss_workspace_bytes(int64_t n, int32_t n_fg, int32_t n_local, int32_t c);
@@ -371,8 +373,14 @@ int pcp_bev_sample_bilinear_backward(const float *dfeat, int32_t ld_dfeat, const
                                      int32_t row_stride, const float *bev, int32_t ld_bev, int32_t batch, int32_t h, int32_t w, int32_t c,
                                      float min_x, float min_y, float pix_x, float pix_y, float *dbev, int32_t ld_dbev, float *dxyz,
                                      int32_t ld_dxyz, void *stream);
-/* remove_gt_boxes_outside_range: rows whose centre lies in [range[0:3], range[3:6]) keep their order, the rest of (batch, max_boxes, 8) is
- * zero (the reference additionally shrinks max_boxes to the largest kept count; zero rows are padding to every consumer) */
+/* remove_gt_boxes_outside_range: rows whose centre lies in [range[0:3], range[3:6]) keep their order, the rest of (batch, max_boxes, width)
+ * is zero (the reference additionally shrinks max_boxes to the largest kept count; zero rows are padding to every consumer).  Rows are
+ * [x, y, z, ..., class]: 8 floats in the V2X-Sim models, 10 with velocity (nuScenes), at most the 16 codes the head kernels take; any other
+ * width is PCP_ERR_UNSUPPORTED before a launch.  pcp_filter_gt_boxes is the width-8 form. */
+#define PCP_GT_BOX_MIN_WIDTH 8
+#define PCP_GT_BOX_MAX_WIDTH 16
+int pcp_filter_gt_boxes_w(const float *gt_boxes, int32_t batch, int32_t max_boxes, int32_t width, const float *range6_host, float *out,
+                          void *stream);
 int pcp_filter_gt_boxes(const float *gt_boxes, int32_t batch, int32_t max_boxes, const float *range6_host, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------

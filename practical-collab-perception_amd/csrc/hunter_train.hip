@@ -1,4 +1,5 @@
-// a17 -- HunterJr TRAINING branch on the device (configs 1 / 2: v2x_pointpillar_basic_car.yaml / _rsu.yaml).
+// a17 -- HunterJr TRAINING branch on the device (configs 1 / 2: v2x_pointpillar_basic_car.yaml / _rsu.yaml, 8-column gt_boxes; the nuScenes
+// corrector pointpillar_jr_corr_withmap, 10-column gt_boxes: the row width is a run-time argument).
 //
 // Replaces, with their autograd graphs:
 //   HunterJr._build_meta                    pcdet/models/bev_layers/hunter_jr.py:165-196   (2 x torch.unique + scatter_max / scatter_min)
@@ -304,6 +305,7 @@ __global__ __launch_bounds__(HT) void k_hl_points(pcp_hunter_loss_t d, int *__re
                                                  unsigned char *__restrict__ local_mos, double *__restrict__ acc) {
   __shared__ double sh[HT / 64];
   const int j = blockIdx.x * HT + threadIdx.x;
+  const int gt_ld = d.gt_stride > 0 ? d.gt_stride : 8;            // 0: the 8-column rows of the V2X-Sim models
   double emb = 0;
   if (j < d.n_fg) {
     const long long i = d.fg_idx[j];
@@ -317,7 +319,8 @@ __global__ __launch_bounds__(HT) void k_hl_points(pcp_hunter_loss_t d, int *__re
     local_mos[l] = mos ? 1 : 0;                              // same value from every point of the local
     const float *row = d.points + i * d.stride;
     const float *hp = d.head + i * d.ld_head;
-    const float ex = d.gt_boxes[(long long)ikey * 8 + 0] - row[1], ey = d.gt_boxes[(long long)ikey * 8 + 1] - row[2];
+    const float *box = d.gt_boxes + (long long)ikey * gt_ld;       // centre x, y: columns 0, 1 at every row width
+    const float ex = box[0] - row[1], ey = box[1] - row[2];
     emb = (double)(sl1(hp[6] - ex) + sl1(hp[7] - ey));
     const float *tf = d.instances_tf + (long long)d.local_key[l] * 12;
     float off[3];
@@ -766,19 +769,20 @@ __global__ __launch_bounds__(HT) void k_bilinear_backward(const float *__restric
   }
 }
 
-// remove_gt_boxes_outside_range (hunter_toolbox.py:161-184): ordered compaction per frame, zero padding (the row count M is kept)
-__global__ __launch_bounds__(HT) void k_filter_gt(const float *__restrict__ gt, int m, float lo_x, float lo_y, float lo_z, float hi_x, float hi_y,
+// remove_gt_boxes_outside_range (hunter_toolbox.py:161-184): ordered compaction per frame, zero padding (the row count M is kept); rows of
+// `width` floats, the centre in columns 0..2
+__global__ __launch_bounds__(HT) void k_filter_gt(const float *__restrict__ gt, int m, int width, float lo_x, float lo_y, float lo_z, float hi_x, float hi_y,
                                                  float hi_z, float *__restrict__ out) {
   __shared__ int wave_cnt[HT / 64];
   __shared__ int base;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) base = 0;
-  for (int i = tid; i < m * 8; i += HT) out[(long long)b * m * 8 + i] = 0.f;
+  for (int i = tid; i < m * width; i += HT) out[(long long)b * m * width + i] = 0.f;
   __syncthreads();
   for (int start = 0; start < m; start += HT) {
     const int i = start + tid;
     int keep = 0;
-    const float *r = gt + ((long long)b * m + (i < m ? i : 0)) * 8;
+    const float *r = gt + ((long long)b * m + (i < m ? i : 0)) * width;
     if (i < m) keep = (r[0] >= lo_x && r[0] < hi_x && r[1] >= lo_y && r[1] < hi_y && r[2] >= lo_z && r[2] < hi_z) ? 1 : 0;
     const unsigned long long bal = __ballot(keep);
     const int lane = tid & 63, wv = tid >> 6;
@@ -786,7 +790,7 @@ __global__ __launch_bounds__(HT) void k_filter_gt(const float *__restrict__ gt, 
     __syncthreads();
     int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
     for (int k = 0; k < wv; ++k) pos += wave_cnt[k];
-    if (keep) for (int k = 0; k < 8; ++k) out[((long long)b * m + pos) * 8 + k] = r[k];
+    if (keep) for (int k = 0; k < width; ++k) out[((long long)b * m + pos) * width + k] = r[k];
     __syncthreads();
     if (tid == 0) { int t = 0; for (int k = 0; k < HT / 64; ++k) t += wave_cnt[k]; base += t; }
     __syncthreads();
@@ -936,6 +940,7 @@ size_t pcp_hunter_loss_workspace_bytes(int64_t n, int32_t n_fg, int32_t n_local,
 int pcp_hunter_losses(const pcp_hunter_loss_t *d, void *workspace, size_t workspace_bytes, void *stream) {
   if (!d || !workspace || !d->points || !d->gt_boxes || !d->instances_tf || !d->head || !d->dhead || !d->losses || !d->labels) return PCP_ERR_ARG;
   if (d->n <= 0 || d->n > 0x7fffffffLL || d->c <= 0 || d->n_fg < 0 || d->n_local < 0 || d->ld_head < 8 || d->ld_dhead < 8) return PCP_ERR_ARG;
+  if (d->gt_stride != 0 && (d->gt_stride < PCP_GT_BOX_MIN_WIDTH || d->gt_stride > PCP_GT_BOX_MAX_WIDTH)) return PCP_ERR_UNSUPPORTED;
   if (d->n_fg > 0 && (!d->fg_idx || !d->fg_local || !d->local_key || !d->local_inst || !d->inst_key || !d->local_feat || !d->locals_feat ||
                       !d->locals_tf || !d->dlocal_feat_fg || !d->dlocals_feat || !d->dlocals_tf || d->n_local <= 0 || d->ld_locals_tf < 7 ||
                       d->ld_dlocals_tf < 7))
@@ -1005,12 +1010,19 @@ int pcp_bev_sample_bilinear_backward(const float *dfeat, int32_t ld_dfeat, const
   return PCP_OK;
 }
 
-int pcp_filter_gt_boxes(const float *gt_boxes, int32_t batch, int32_t max_boxes, const float *range6_host, float *out, void *stream) {
+int pcp_filter_gt_boxes_w(const float *gt_boxes, int32_t batch, int32_t max_boxes, int32_t width, const float *range6_host, float *out,
+                          void *stream) {
   if (!gt_boxes || !out || !range6_host || batch <= 0 || max_boxes <= 0) return PCP_ERR_ARG;
-  k_filter_gt<<<batch, HT, 0, static_cast<hipStream_t>(stream)>>>(gt_boxes, max_boxes, range6_host[0], range6_host[1], range6_host[2],
+  if (width < PCP_GT_BOX_MIN_WIDTH || width > PCP_GT_BOX_MAX_WIDTH) return PCP_ERR_UNSUPPORTED;
+  if ((long long)max_boxes * width > 0x7fffffffLL) return PCP_ERR_ARG;
+  k_filter_gt<<<batch, HT, 0, static_cast<hipStream_t>(stream)>>>(gt_boxes, max_boxes, width, range6_host[0], range6_host[1], range6_host[2],
                                                                     range6_host[3], range6_host[4], range6_host[5], out);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
+}
+
+int pcp_filter_gt_boxes(const float *gt_boxes, int32_t batch, int32_t max_boxes, const float *range6_host, float *out, void *stream) {
+  return pcp_filter_gt_boxes_w(gt_boxes, batch, max_boxes, 8, range6_host, out, stream);
 }
 
 }  // extern "C"

@@ -84,7 +84,9 @@ def cfg_from_list(cfg_list, config):
                 k, v = item.split(':')
                 current[k] = type(current[k])(v)
         elif type(value) != type(current) and isinstance(current, list):
-            node[leaf] = [type(current[0])(x) for x in value.split(',')]
+            # 'a,b,c': strings stay strings; numbers arrive as the tuple literal_eval made of them
+            items = value if isinstance(value, tuple) else value.split(',')
+            node[leaf] = [type(current[0])(x) for x in items]
         else:
             assert type(value) == type(current), 'type {} does not match original type {}'.format(type(value), type(current))
             node[leaf] = value

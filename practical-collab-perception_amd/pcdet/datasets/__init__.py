@@ -35,6 +35,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         if dataset_cfg.DATASET == 'NuScenesDataset' and len(enc.used_feature_list) == 12:
             self.layout = 'nusc_map'       # the five HD-map layers behind the timestamp (synth.nusc_cloud with_map)
             self.points_per_agent = int(syn.get('POINTS_PER_FRAME', self.points_per_agent))   # the nuScenes configs size the frame
+        self.xy_half = float(syn.get('XY_HALF', 52.0))
 
     @property
     def mode(self):
@@ -48,7 +49,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         n_agents = AGENTS_OF[self.layout]
         for a in range(n_agents):
             if self.layout == 'nusc_map':
-                c = synth.nusc_cloud(index, self.points_per_agent, with_map=True, dist=self.distribution)
+                c = synth.nusc_cloud(index, self.points_per_agent, xy_half=self.xy_half, with_map=True, dist=self.distribution)
             else:
                 c = synth.agent_cloud(agent=100 * index + a, n_points=self.points_per_agent, layout=self.layout, dist=self.distribution)
             if self.layout == 'disco':
@@ -61,7 +62,13 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
             # = 40 boxes per agent, neighbouring agents reporting overlapping boxes so that the NMS has something to merge
             meta['exchange_boxes'] = {a: self.synthetic_exchange_boxes(index, a) for a in range(6)}
         item = {'points': np.concatenate(parts, 0), 'frame_id': index, 'metadata': meta}
-        if self.training:
+        if self.training and self.layout == 'nusc_map':
+            # the HD-map models train on 10-column boxes; the corrector model reads the foreground rows and instances_tf, withmap ignores them
+            item['gt_boxes'] = self.synthetic_gt_boxes_velocity(index)
+            sweeps = int(self.dataset_cfg.get('MAX_SWEEPS', 10))
+            fg, item['instances_tf'] = synth.nusc_instance_foreground(index, item['gt_boxes'], n_sweeps=sweeps)
+            item['points'] = np.concatenate([item['points'], fg], 0)
+        elif self.training:
             item['gt_boxes'] = self.synthetic_gt_boxes(index)
             if self.layout == 'car' and self.dataset_cfg.DATASET in ('V2XSimDataset_CAR', 'V2XSimDataset_RSU'):
                 # configs 1 / 2 train HunterJr: foreground points carry (sweep, instance) and every instance its per-sweep motion
@@ -98,6 +105,20 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         gt[:, 5] = synth.uniform(s, 6, n, 1.4, 2.0)
         gt[:, 6] = synth.uniform(s, 7, n, -3.14159, 3.14159)
         gt[:, 7] = np.floor(synth.uniform(s, 8, n, 1.0, len(self.class_names) + 0.999))
+        return gt
+
+    def synthetic_gt_boxes_velocity(self, index, n_max=40):
+        """(n, 10) [x, y, z, dx, dy, dz, heading, vx, vy, class]: the boxes of synthetic_gt_boxes with the velocity the foreground of
+        synth.nusc_instance_foreground moves at (odd rows drive along their heading, even rows stand still); the centre of the LAST row is
+        put outside the range, so that the corrector's box filter has a row to drop"""
+        g8 = self.synthetic_gt_boxes(index, n_max)
+        n = g8.shape[0]
+        gt = np.zeros((n, 10), dtype=np.float32)
+        gt[:, :7], gt[:, 9] = g8[:, :7], g8[:, 7]
+        speed = np.where(np.arange(n) % 2 == 1, 3.0 + 0.5 * np.arange(n), 0.0)
+        gt[:, 7] = (speed * np.cos(g8[:, 6].astype(np.float64))).astype(np.float32)
+        gt[:, 8] = (speed * np.sin(g8[:, 6].astype(np.float64))).astype(np.float32)
+        gt[n - 1, 0] = float(self.point_cloud_range[3]) + 2.0
         return gt
 
     @staticmethod

@@ -155,9 +155,12 @@ class CenterPoint(Detector3DTemplate):
         return out
 
     def forward(self, batch_dict):
-        if self.training and getattr(self, 'corrector', None) is not None and type(self.backbone_2d).__name__.startswith('SCConvBackbone'):
-            raise NotImplementedError('training HunterJr behind an SC backbone (the nuScenes corrector, pointpillar_jr_corr_withmap) is not '
-                                      'implemented: the corrector trains only in the V2X-Sim car / rsu models; this model is inference only')
+        if (self.training and getattr(self, 'corrector', None) is not None and type(self.backbone_2d).__name__.startswith('SCConvBackbone')
+                and not batch_dict['points'].is_cuda):
+            # before any module runs (the VFE would pillarise a host batch on the CPU path first)
+            raise NotImplementedError('training HunterJr behind an SC backbone (the nuScenes corrector, pointpillar_jr_corr_withmap) runs on '
+                                      'the HIP training path only and the points of this batch are on %s: off the GPU this model is inference only'
+                                      % batch_dict['points'].device)
         batch_dict = self._run_modules(batch_dict)
         if self.training:
             tape = batch_dict.get('_pcp_tape', [])

@@ -10,6 +10,10 @@ assign_target, correct_bev_image), :401-495 (get_training_loss).  No torch.autog
     point heads, point MLP, object head (segment max routing) <- first sampling <- bev <- conv_input <- backbone
 
 and deposits parameter gradients in param.grad.  One host read (three counts) after the locals / instances are built.
+
+The same object trains the nuScenes corrector (pointpillar_jr_corr_withmap: hidden width 64, NUM_SWEEPS 10, 13-column rows, 10-column
+gt_boxes, an SC backbone beneath).  bf16 loop: the two 3x3 ConvBNAct layers run the bf16 kernels and hand float32 maps and gradients to
+the point / scatter / blend kernels, which are float32 only.
 """
 import numpy as np
 import torch
@@ -123,7 +127,7 @@ class HunterTrain:
         if self.sc_ws is None or self.sc_ws.numel() < need or self.sc_ws.device != dev:
             self.sc_ws = torch.empty(need, dtype=torch.uint8, device=dev)               # kept: its cell tables drive the backward
         ops.bev_scatter_mean(points, pf2, B, H, W, min_xy, pix, out=cat, out_ch_off=C, workspace=self.sc_ws)
-        hid = self.w0.forward(Act(cat))
+        hid = self.w0.forward(Act(cat), out_dtype=torch.float32)                       # read by fp32-only kernels, in the bf16 loop too
         f = self._w1_forms()
         logits = torch.empty((B, H, W, 2), dtype=torch.float32, device=dev)
         ops.conv3x3_grouped_small(hid.t, f['small'][0], f['small'][1], [0, 2], logits)
@@ -148,6 +152,7 @@ class HunterTrain:
         d = lib.HunterLoss()
         d.n, d.stride, d.n_fg, d.n_local, d.n_inst, d.c = N, s['pts0'].shape[1], meta.n_fg, meta.n_local, meta.n_inst, C
         d.batch, d.max_inst, d.num_sweeps = s['B'], s['M'], s['S']
+        d.gt_stride = lib.check_gt_box_width(s['gt'].shape[2])
         p = lambda t: t.data_ptr() if t is not None else None
         d.points, d.gt_boxes, d.instances_tf = p(s['pts0']), p(s['gt']), p(s['itf'])
         d.fg_idx, d.fg_local, d.local_key, d.local_inst, d.inst_key = p(meta.fg_idx), p(meta.fg_local), p(meta.local_key), p(meta.local_inst), \
@@ -185,6 +190,8 @@ class HunterTrain:
         B, H, W, C, N = s['B'], s['H'], s['W'], s['C'], s['N']
         dev = s['cat'].device
         cat, dyn = s['cat'], s['dyn']
+        if dfused.t.dtype != torch.float32:                                            # bf16 loop: the head's shared conv hands bf16 over
+            dfused = Act(tl.as_f32(dfused.t, dfused.off, dfused.c), 0, dfused.c)
         if dfused.off != 0 or dfused.t.shape[-1] != C:
             raise ValueError('the fused-map gradient must be a dense (B, H, W, C) buffer')
         dcat = torch.empty((B, H, W, 2 * C), dtype=torch.float32, device=dev)
@@ -200,7 +207,7 @@ class HunterTrain:
         ensure_grad(self.w1.bias).copy_(db[:2])
         w, b, cp = self._w1_forms()['bw']
         dhid = ops.conv3x3(dlogits, w, b, 16, 2 * C, cp, stride=1, relu=False)
-        dcat2 = self.w0.backward(Act(dhid))
+        dcat2 = self.w0.backward(Act(dhid), dx_dtype=torch.float32)
         tops.accumulate(dcat, dcat2.t, 2 * C, src_ch_off=dcat2.off)
         # per-cell mean of the point features; rows the flow head moved were re-sampled at the moved position
         dpf = torch.zeros((N, C), dtype=torch.float32, device=dev)

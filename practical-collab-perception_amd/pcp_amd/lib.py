@@ -163,7 +163,19 @@ class HunterLoss(ctypes.Structure):
                 ('head', vp), ('ld_head', c_i32), ('local_feat', vp), ('ld_local_feat', c_i32), ('locals_feat', vp), ('ld_locals_feat', c_i32),
                 ('locals_tf', vp), ('ld_locals_tf', c_i32), ('coef_fg', c_f), ('coef_locals', c_f), ('grad_scale', c_f),
                 ('dhead', vp), ('ld_dhead', c_i32), ('dlocal_feat_fg', vp), ('dlocals_feat', vp), ('dlocals_tf', vp), ('ld_dlocals_tf', c_i32),
-                ('losses', vp), ('labels', vp), ('tgt_embedding', vp), ('tgt_offset', vp)]
+                ('losses', vp), ('labels', vp), ('tgt_embedding', vp), ('tgt_offset', vp),
+                ('gt_stride', c_i32)]               # floats per gt_boxes row (GT_BOX_MIN_WIDTH .. GT_BOX_MAX_WIDTH); 0 = 8
+
+
+GT_BOX_MIN_WIDTH, GT_BOX_MAX_WIDTH = 8, 16          # include/pcp_hip_train.h: PCP_GT_BOX_MIN_WIDTH / PCP_GT_BOX_MAX_WIDTH
+
+
+def check_gt_box_width(width, what='gt_boxes'):
+    """the refusal of the HunterJr training kernels, on the host and before any launch"""
+    if not GT_BOX_MIN_WIDTH <= int(width) <= GT_BOX_MAX_WIDTH:
+        raise ValueError('%s rows have %d columns: the HunterJr training kernels take %d (x y z dx dy dz heading class) up to %d, the '
+                         'number of box codes the head kernels take' % (what, int(width), GT_BOX_MIN_WIDTH, GT_BOX_MAX_WIDTH))
+    return int(width)
 
 
 PW_PLAIN, PW_SPACE2DEPTH, PW_DEPTH2SPACE = 0, 1, 2
@@ -300,6 +312,7 @@ SYMBOLS.update({
     'pcp_bev_sample_bilinear_backward': (c_i32, [vp, c_i32, vp, vp, c_i64, c_i32, vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f, c_f, vp,
                                                  c_i32, vp, c_i32, vp]),
     'pcp_filter_gt_boxes': (c_i32, [vp, c_i32, c_i32, ctypes.POINTER(c_f), vp, vp]),
+    'pcp_filter_gt_boxes_w': (c_i32, [vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_f), vp, vp]),
     'pcp_distill_loss': (c_i32, [vp, c_i32, vp, c_i32, c_i64, c_i32, c_f, c_f, vp, vp, vp, c_i32, c_i32, vp]),
     'pcp_masked_smooth_l1_rows': (c_i32, [vp, c_i32, vp, c_i32, c_i64, c_i32, c_f, vp, vp, vp]),
     'pcp_pfn_train_features': (c_i32, [vp, c_i64, c_i32, c_i32, ctypes.POINTER(Grid), vp, vp, vp, vp]),

@@ -240,3 +240,36 @@ def instance_foreground(index, gt, n_sweeps=11, per_local=12, max_instances=12):
             r[:, 0:3], r[:, 3], r[:, 4], r[:, 5], r[:, 6] = p, 0.5, dt, sw, i
             rows.append(r)
     return np.concatenate(rows, 0), tf
+
+
+def nusc_instance_foreground(index, gt, n_sweeps=10, per_local=12, max_instances=12, sweeps=(9, 6, 2)):
+    """instance_foreground for the HD-map layout of the nuScenes corrector model: gt (n, 10) [x y z dx dy dz heading vx vy class], rows
+    in the 12-feature layout [x, y, z, intensity, time, four 0/1 map masks, lane direction, sweep, instance] and instances_tf
+    (n, n_sweeps, 3, 4) with the semantics of instance_foreground (odd instances drive along their heading and the rigid motion takes a
+    sweep-s point to the newest sweep, n_sweeps - 1; even instances stand still).  The first min(n, max_instances) rows of gt get points,
+    wherever their centre lies; every (instance, sweep) pair lies inside the (n, n_sweeps) table."""
+    n = gt.shape[0]
+    newest = n_sweeps - 1
+    tf = np.zeros((n, n_sweeps, 3, 4), dtype=np.float32)
+    tf[..., :3, :3] = np.eye(3, dtype=np.float32)
+    rows = []
+    s = SEED_BASE + 6500 + index
+    for i in range(min(n, max_instances)):
+        c, dims, yaw = gt[i, 0:3].astype(np.float64), gt[i, 3:6].astype(np.float64), float(gt[i, 6])
+        moving = i % 2 == 1
+        speed = 3.0 + 0.5 * i
+        R = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]])
+        if moving:
+            for sw in range(n_sweeps):
+                tf[i, sw, :3, 3] = speed * (newest - sw) * 0.1 * np.array([np.cos(yaw), np.sin(yaw), 0.0])
+        for k, sw in enumerate(sweeps):
+            u = uniform(s, 40 * i + k, per_local * 3, -0.5, 0.5).reshape(per_local, 3).astype(np.float64)
+            p = (u * dims) @ R.T + c - (tf[i, sw, :3, 3].astype(np.float64) if moving else 0.0)
+            r = np.zeros((per_local, 12), dtype=np.float32)
+            r[:, 0:3], r[:, 3], r[:, 4] = p, 0.5, (newest - sw) * 0.1
+            for j in range(4):
+                r[:, 5 + j] = (uniform01(s, 40 * i + 4 + 5 * k + j, per_local) < 0.3).astype(np.float32)
+            r[:, 9] = uniform(s, 40 * i + 8 + 5 * k, per_local, -math.pi, math.pi)
+            r[:, 10], r[:, 11] = sw, i
+            rows.append(r)
+    return np.concatenate(rows, 0), tf

@@ -893,11 +893,15 @@ def bev_sample_bilinear_backward(dfeat, points, batch, h, w, c, min_xy, pix_xy, 
 
 
 def filter_gt_boxes(gt_boxes, pc_range):
+    """remove_gt_boxes_outside_range for (B, M, width) rows, width = gt_boxes.shape[2]: 8, or 10 with velocity"""
+    B, M, width = gt_boxes.shape
+    _lib.check_gt_box_width(width)
     L = _lib.load()
-    B, M, _ = gt_boxes.shape
+    _need_cuda(gt_boxes)
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.is_contiguous()
     out = torch.empty_like(gt_boxes)
     rng = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
-    check(L.pcp_filter_gt_boxes(_p(gt_boxes), B, M, rng, _p(out), _stream()), 'pcp_filter_gt_boxes')
+    check(L.pcp_filter_gt_boxes_w(_p(gt_boxes), B, M, width, rng, _p(out), _stream()), 'pcp_filter_gt_boxes_w')
     return out
 
 

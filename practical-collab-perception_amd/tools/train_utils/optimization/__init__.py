@@ -280,11 +280,12 @@ class OneCycle:
         optimizer.lr, optimizer.mom = low, self.moms[0]
 
     def step(self, step):
+        # a phase of zero length (int(pct_start * total_step) == 0: a run of one or two iterations) is skipped, not divided by
         for s, e, a, b in self.lr_phases:
-            if step >= s:
+            if step >= s and e > s:
                 self.optimizer.lr = float(annealing_cos(a, b, (step - s) / (e - s)))
         for s, e, a, b in self.mom_phases:
-            if step >= s:
+            if step >= s and e > s:
                 self.optimizer.mom = float(annealing_cos(a, b, (step - s) / (e - s)))
 
 
