@@ -446,6 +446,8 @@ def pointwise(x, packed, bias, mode, cin, cout, cout_pad, relu=True, out=None, i
     assert x.is_contiguous() and out.is_contiguous()
     if residual_before_relu:
         assert mode == _lib.PW_PLAIN and residual is not None and relu, 'residual_before_relu: PLAIN 1x1 with a residual and a ReLU'
+    if mode == _lib.PW_PLAIN and rows == 0:
+        return out          # no rows, no launch (pcp_pointwise's own answer); torch gives a zero-row tensor a null address, which it refuses
     d = Pointwise(mode, rows, B, H, W, cin, cout, cout_pad, ld_in, out.shape[-1],
                   _lib.RELU_PRE_RESIDUAL if residual_before_relu else (1 if relu else 0))
     if x2 is not None:
