@@ -460,6 +460,54 @@ int pcp_add_relu(const float *z, int32_t ld_z, const float *res, int32_t ld_res,
 int pcp_add_relu_backward(const float *dout, int32_t ld_dout, const float *out, int32_t ld_out, float *dz, int32_t ld_dz, float *dz2,
                           int32_t ld_dz2, int64_t rows, int32_t c, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * World augmentation of a collated training batch (the reference's DataAugmentor random_world_flip / _rotation / _scaling /
+ * _translation and the DataProcessor's mask_points_and_boxes_outside_range, which it runs per sample on the host before collation;
+ * csrc/augment.hip).  Every row / box / matrix is transformed with the parameters of ITS frame, stage by stage in the order of
+ * `stage[]`, each stage with the reference's own float32 operations (nothing is composed into one matrix).
+ *
+ * table (device, batch x PCP_AUG_TABLE_STRIDE float32, written by the host), per frame:
+ *   [0] flip_x (0 / 1: y -> -y)  [1] flip_y (0 / 1: x -> -x)  [2] cos  [3] sin  [4] rot  [5] scale  [6..8] tx ty tz  [9..11] unused
+ * cos / sin are the float32 values the host computed for the rotation matrix; the kernels evaluate no sine or cosine for it.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_AUG_FLIP_X 1
+#define PCP_AUG_FLIP_Y 2
+#define PCP_AUG_ROTATE 3
+#define PCP_AUG_SCALE 4
+#define PCP_AUG_TRANSLATE 5
+#define PCP_AUG_MAX_STAGES 8
+#define PCP_AUG_MAX_BATCH 64
+#define PCP_AUG_TABLE_STRIDE 12
+#define PCP_AUG_MIN_ROW_STRIDE 4  /* frame index + xyz */
+#define PCP_AUG_MAX_ROW_STRIDE 15 /* frame index + 14 feature columns */
+#define PCP_AUG_TILE_ROWS 512     /* rows one workgroup stages through LDS */
+typedef struct pcp_world_aug {
+  int32_t n_stages;
+  int32_t stage[PCP_AUG_MAX_STAGES]; /* PCP_AUG_* in the order they are applied */
+  int32_t batch;
+  int32_t hd_map;   /* rows are [b, x y z i t, 4 map masks, lane_dir, sweep, instance] (row_stride 13): lane_dir follows the flips / rotation */
+  int32_t filter;   /* keep only rows with range[0..2] <= xyz < range[3..5] after the transform, compacted in input order */
+  float range[6];
+} pcp_world_aug_t;
+
+/* points (n, row_stride) float32, column 0 the frame index, 16-byte aligned like `out`.  xyz always; hd_map: column 10 (lane_dir);
+ * row_stride >= 14: column 9 (MoDAR heading) on the rows whose column row_stride - 3 is > 0; every other column keeps its bits.  Rows of
+ * a frame outside [0, batch) are not transformed and, with the filter on, dropped.
+ *   filter off: out[i] = transformed points[i] (out may be points itself); frame_count and the workspace are not used.
+ *   filter on : the kept rows in input order at the front of `out` (n rows of capacity, NOT points itself; the rows behind them are
+ *               left as they are) and frame_count[b] (device, batch int32) = rows kept of frame b.
+ * Two launches with the filter on (count per tile, place), one without; no atomics on the placement path: a call repeats bit for bit. */
+size_t pcp_world_augment_points_workspace_bytes(int64_t n);
+int pcp_world_augment_points(const pcp_world_aug_t *aug, const float *table, const float *points, int64_t n, int32_t row_stride, float *out,
+                             int32_t *frame_count, void *workspace, size_t workspace_bytes, void *stream);
+
+/* gt_boxes (batch, max_boxes, box_width) in place, box_width 8 [x y z dx dy dz heading class] or 10 [.. heading vx vy class]; rows of class 0
+ * (padding) keep their bits; the heading ends with limit_period(h, 0.5, 2 pi).  instances_tf (nullable; batch, max_boxes, n_sweeps, tf_rows,
+ * 4) with tf_rows 3 or 4: every matrix of a box of class != 0 becomes T A T^-1 for each stage in order, evaluated as an affine map in
+ * float32 (a fourth row keeps its bits).  `range` / `filter` / `hd_map` of aug are not read.  One launch. */
+int pcp_world_augment_boxes(const pcp_world_aug_t *aug, const float *table, float *gt_boxes, int32_t max_boxes, int32_t box_width,
+                            float *instances_tf, int32_t n_sweeps, int32_t tf_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,11 +23,15 @@ def load_data_to_gpu(batch_dict):
             batch_dict[key] = torch.from_numpy(val).float().cuda().contiguous()
 
 
-def model_fn_decorator():
+def model_fn_decorator(augmentor=None):
+    """augmentor (pcp_amd.augment.DeviceWorldAugmentor, optional): the world augmentation the reference runs in its DataLoader workers,
+    applied to the collated batch on the device, in training mode only.  None: the batch reaches the model as it was loaded."""
     ModelReturn = namedtuple('ModelReturn', ['loss', 'tb_dict', 'disp_dict'])
 
     def model_func(model, batch_dict):
         load_data_to_gpu(batch_dict)
+        if augmentor is not None and model.training:
+            augmentor(batch_dict)
         ret_dict, tb_dict, disp_dict = model(batch_dict)
         loss = ret_dict['loss']
         (model if hasattr(model, 'update_global_step') else model.module).update_global_step()

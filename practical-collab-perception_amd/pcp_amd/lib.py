@@ -151,6 +151,17 @@ class AnchorLoss(ctypes.Structure):
                 ('code_weights', c_f * 7)]
 
 
+AUG_FLIP_X, AUG_FLIP_Y, AUG_ROTATE, AUG_SCALE, AUG_TRANSLATE = 1, 2, 3, 4, 5       # PCP_AUG_* (include/pcp_hip_train.h)
+AUG_MAX_STAGES, AUG_MAX_BATCH, AUG_TABLE_STRIDE = 8, 64, 12
+AUG_MIN_ROW_STRIDE, AUG_MAX_ROW_STRIDE, AUG_TILE_ROWS = 4, 15, 512
+
+
+class WorldAug(ctypes.Structure):
+    """pcp_world_aug_t (include/pcp_hip_train.h)"""
+    _fields_ = [('n_stages', c_i32), ('stage', c_i32 * AUG_MAX_STAGES), ('batch', c_i32), ('hd_map', c_i32), ('filter', c_i32),
+                ('range', c_f * 6)]
+
+
 class HunterMeta(ctypes.Structure):
     _fields_ = [('batch', c_i32), ('max_inst', c_i32), ('num_sweeps', c_i32), ('sweep_col', c_i32), ('inst_col', c_i32)]
 
@@ -336,6 +347,9 @@ SYMBOLS.update({
                                      c_i32, c_i32, c_i32, c_i32, vp]),
     'pcp_add_relu': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, c_i64, c_i32, vp]),
     'pcp_add_relu_backward': (c_i32, [vp, c_i32, vp, c_i32, vp, c_i32, vp, c_i32, c_i64, c_i32, vp]),
+    'pcp_world_augment_points_workspace_bytes': (c_sz, [c_i64]),
+    'pcp_world_augment_points': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i64, c_i32, vp, vp, vp, c_sz, vp]),
+    'pcp_world_augment_boxes': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp]),
 })
 
 # include/pcp_hip_mp.h (mixed-precision training loop, config 5)

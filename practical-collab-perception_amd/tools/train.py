@@ -49,14 +49,32 @@ def parse_config():
     p.add_argument('--max_ckpt_save_num', type=int, default=30)
     p.add_argument('--output_dir', type=str, default=None)
     p.add_argument('--sync_bn', action='store_true', default=False, help='whether to use sync bn')
+    p.add_argument('--fix_random_seed', action='store_true', default=False, help='seed the device augmentation with 666 + rank')
     p.add_argument('--set', dest='set_cfgs', default=None, nargs=argparse.REMAINDER)
     args = p.parse_args()
     cfg_from_yaml_file(args.cfg_file, cfg)
     cfg.TAG = Path(args.cfg_file).stem
     cfg.EXP_GROUP_PATH = '/'.join(args.cfg_file.split('/')[1:-1])      # reference tools/train.py:61: drop 'cfgs' and the file name
+    if 'SYNTHETIC' not in cfg.DATA_CONFIG:
+        cfg.DATA_CONFIG.SYNTHETIC = {}
+    if 'DEVICE_AUG' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.DEVICE_AUG = False        # present before --set, which only takes keys that exist
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
     return args, cfg
+
+
+def build_augmentor(args, cfg, train_set, logger):
+    """DATA_CONFIG.SYNTHETIC.DEVICE_AUG: the DATA_AUGMENTOR list of the config (the reference's host-side world flip / rotation / scaling /
+    translation and its range mask) on the collated batch on the device (pcp_amd/augment.py); off by default.  Seeded like the reference's
+    --fix_random_seed (666 + rank, tools/train.py:80-81 there); without the flag every run draws differently."""
+    if not cfg.DATA_CONFIG.SYNTHETIC.get('DEVICE_AUG', False) or cfg.DATA_CONFIG.get('DATA_AUGMENTOR', None) is None:
+        return None
+    from pcp_amd.augment import DeviceWorldAugmentor
+    aug = DeviceWorldAugmentor.from_dataset_cfg(cfg.DATA_CONFIG, layout=getattr(train_set, 'layout', 'car'), logger=logger,
+                                                seed=666 + cfg.LOCAL_RANK if args.fix_random_seed else None)
+    logger.info('device world augmentation: stages %s, range filter %s' % ([n for n, _ in aug.queue], 'on' if aug.filter else 'off'))
+    return aug
 
 
 def init_distributed(args, cfg):
@@ -187,7 +205,7 @@ def main():
                                               last_epoch=start_epoch - 1, optim_cfg=cfg.OPTIMIZATION)
     logger.info('**********************Start training %s (%d trainable tensors, %.2f M parameters)**********************'
                 % (cfg.TAG, len(optimizer.params), sum(p.numel() for p in optimizer.params) / 1e6))
-    train_model(model, optimizer, train_loader, model_func=model_fn_decorator(), lr_scheduler=lr_scheduler, optim_cfg=cfg.OPTIMIZATION,
+    train_model(model, optimizer, train_loader, model_func=model_fn_decorator(build_augmentor(args, cfg, train_set, logger)), lr_scheduler=lr_scheduler, optim_cfg=cfg.OPTIMIZATION,
                 start_epoch=start_epoch, total_epochs=args.epochs, start_iter=it, rank=cfg.LOCAL_RANK, tb_log=None, ckpt_save_dir=ckpt_dir,
                 train_sampler=train_sampler, lr_warmup_scheduler=lr_warmup, ckpt_save_interval=args.ckpt_save_interval,
                 max_ckpt_save_num=args.max_ckpt_save_num, logger=logger)
