@@ -28,16 +28,6 @@ constexpr int CK = 16;    // input channels per staged slice
 constexpr int LDK = 20;   // padded LDS row length in floats
 constexpr int CONV_THREADS = 256;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  // blocks b and b+8 share an XCD (round-robin dispatch); give each XCD a contiguous run of logical tiles. Bijective.
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 struct Conv3Params {
   const float *in;
   const float *w;       // [cin/16][9][cout_pad][16]

@@ -33,11 +33,6 @@ struct B3Params {
   int tiles_y, tiles_x, n_tiles;
 };
 
-__device__ __forceinline__ int xcd_remap_b3(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 // S: stride; TH: output rows per workgroup (8 * M-tiles per wave); DB: double-buffered LDS (one barrier per slice, one workgroup per
 // CU with a 128-pixel x 64-channel register tile per wave) or single-buffered (two workgroups per CU overlap each other)
 // TERMS: 3 = split products hi*hi + hi*lo + lo*hi ("bf16x3", ~1e-5); 1 = plain bf16 products hi*hi (8 mantissa bits, ~3e-3: the
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(B3_THREADS, DB ? 1 : 2) void k_conv3x3_bf16x3(B3Par
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int n_ct = p.cout_pad / B3_BN;
-  int lid = xcd_remap_b3(blockIdx.x, gridDim.x);
+  int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int ct = lid % n_ct;                      // cout tiles of one spatial tile are neighbours: they share the patch in L2
   lid /= n_ct;
   const int tx = lid % p.tiles_x;
@@ -175,18 +170,10 @@ __global__ __launch_bounds__(B3_THREADS, DB ? 1 : 2) void k_conv3x3_bf16x3(B3Par
     __syncthreads();
     for (int s = 0; s < n_slices; ++s) {
       const bool more = s + 1 < n_slices;
-#if defined(B3_DIAG_ONE_SLICE)
-      compute(0);
-#elif defined(B3_DIAG_NO_COMMIT)
-      if (more) prefetch(s + 1);
-      compute(0);
-      asm volatile("" :: "v"(preg[0]), "v"(wreg[0]));
-#else
       if (more) prefetch(s + 1);           // in flight during the whole multiply of slice s
       compute(s & 1);
       if (more) commit((s + 1) & 1);       // the other buffer: nobody reads it until the barrier below
       __syncthreads();
-#endif
     }
   } else {
     for (int s = 0; s < n_slices; ++s) {

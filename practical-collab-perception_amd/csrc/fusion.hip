@@ -282,7 +282,6 @@ struct WfParams {
 
 #pragma clang fp contract(on)
 namespace {
-__device__ __forceinline__ f32x16 wf_mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 }
 
 namespace {
@@ -316,10 +315,10 @@ __global__ __launch_bounds__(256, 2) void k_weight_fuse(WfParams p) {
       for (int j = 0; j < 16; j++) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(src + 8 * j);
         const f32x4 w = *reinterpret_cast<const f32x4 *>(w1_row + 8 * j);
-        acc_e = wf_mfma(a.x, w.x, acc_e);
-        acc_e = wf_mfma(a.y, w.y, acc_e);
-        acc_e = wf_mfma(a.z, w.z, acc_e);
-        acc_e = wf_mfma(a.w, w.w, acc_e);
+        acc_e = mfma32(a.x, w.x, acc_e);
+        acc_e = mfma32(a.y, w.y, acc_e);
+        acc_e = mfma32(a.z, w.z, acc_e);
+        acc_e = mfma32(a.w, w.w, acc_e);
       }
     }
     for (int a_i = 0; a_i < p.n_maps; a_i++) {
@@ -328,10 +327,10 @@ __global__ __launch_bounds__(256, 2) void k_weight_fuse(WfParams p) {
 #pragma unroll
       for (int j = 0; j < 16; j++) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(src + 8 * j);
-        acc = wf_mfma(a.x, wb[j].x, acc);
-        acc = wf_mfma(a.y, wb[j].y, acc);
-        acc = wf_mfma(a.z, wb[j].z, acc);
-        acc = wf_mfma(a.w, wb[j].w, acc);
+        acc = mfma32(a.x, wb[j].x, acc);
+        acc = mfma32(a.y, wb[j].y, acc);
+        acc = mfma32(a.z, wb[j].z, acc);
+        acc = mfma32(a.w, wb[j].w, acc);
       }
 #pragma unroll
       for (int e = 0; e < 16; e++) {

@@ -47,11 +47,6 @@ struct McParams {
   int diag;               // timing-only builds (PCP_MP_DIAG): 4 = no copies after the first stage (wrong results)
 };
 
-__device__ __forceinline__ int mc_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 #ifdef MC_STAMP
 // diagnostic build (csrc/build_variant.sh stamp "-DMC_STAMP", tools/stamp_mc.py): s_memtime stamps of wave 0 of every workgroup, kept in
 // memory nothing else reads
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(TH * 32, TH == 16 ? 2 : 1) void k_mp_conv3x3_s1(McP
 
   // ---- this workgroup's run of items (XCD-contiguous: neighbours in the run share patch halos and weights in one L2) --------------------
   const int nwg = gridDim.x;
-  const int lid = mc_xcd_remap(blockIdx.x, nwg);
+  const int lid = xcd_remap(blockIdx.x, nwg);
   const int per = p.n_items / nwg, rem = p.n_items % nwg;
   const int it_begin = lid * per + min(lid, rem);
   const int it_end = it_begin + per + (lid < rem ? 1 : 0);
@@ -360,7 +355,7 @@ __global__ __launch_bounds__(MG_THREADS, 2) void k_mp_conv3x3_gen(MgParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int n_ct = p.cout_pad / MC_BN;
-  int lid = mc_xcd_remap(blockIdx.x, gridDim.x);
+  int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int ct = lid % n_ct;
   lid /= n_ct;
   const int tx = lid % p.tiles_x;

@@ -14,8 +14,8 @@
 //   k_mp_pw_wgrad  weight gradient: out[n][k] = sum_r a[map(r)][n] * b[map(r)][k], the contraction runs over PIXELS.  Rows are copied global ->
 //                LDS as they lie (128-byte records = 64 channels, `buffer_load_dwordx4 ... lds`, 32-byte chunks XOR-swizzled on the source
 //                address) and read back transposed by ds_read_b64_tr_b16, as in k_mp_wgrad3x3 (mp_wgrad.hip); a ring of four 32-row stages
-//                keeps 24 KB per workgroup in flight; split-K partials are reduced in split order by k_mp_pw_reduce (bitwise reproducible).
-#include "pcp_common.h"
+//                keeps 24 KB per workgroup in flight; split-K partials are reduced in split order by k_pw_reduce (bitwise reproducible).
+#include "splitk_common.h"
 #include "../../include/pcp_hip_mp.h"
 
 namespace {
@@ -32,11 +32,6 @@ constexpr int MPW_THREADS = 256;
 constexpr int MPW_BM = 128;      // pixels per workgroup
 constexpr int MPW_BN = 64;       // output channels per workgroup
 constexpr int MPW_CK = 32;       // K per slice (two MFMA k steps)
-
-__device__ __forceinline__ int mpw_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 // eight consecutive channels of a row as bf16 (16 bytes)
 template <typename T> struct Ld8;
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(MPW_THREADS, 2) void k_mp_pw(MpwParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int pw = wave >> 1, cw = wave & 1;                                  // pixel half (64), channel half (32) of the tile
-  const int lid = mpw_xcd_remap(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = lid % p.n_tiles;
   const long long m0 = (long long)(lid / p.n_tiles) * MPW_BM;
   const int n0 = nt * MPW_BN;
@@ -255,26 +250,12 @@ constexpr int MWG_ROWS = 32;             // rows of a stage (two MFMA k steps)
 constexpr int MWG_NST = 4;               // stages resident (three in flight)
 constexpr int MWG_OP = MWG_ROWS * 128;   // bytes of one operand of a stage
 
-struct MwgMap {
-  const void *ptr;
-  int ld, ch, mode, h, w, ky, kx;
-  unsigned bytes;
-};
 struct MwgParams {
-  MwgMap a, b;
+  RowMap a, b;
   long long rows;
   float *part;                           // [nsplit][n_r][k_r]
   int k_tiles, n_r, k_r, nsplit, chunks;
 };
-
-__device__ __forceinline__ long long mwg_row(const MwgMap &m, long long r) {
-  if (m.mode == 0) return r;
-  const int x = (int)(r % m.w);
-  const long long t = r / m.w;
-  const int y = (int)(t % m.h);
-  const long long b = t / m.h;
-  return (b * 2 * m.h + 2 * y + m.ky) * 2 * m.w + 2 * x + m.kx;
-}
 
 __global__ __launch_bounds__(MWG_THREADS, 2) void k_mp_pw_wgrad(MwgParams p) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[MWG_NST * 2 * MWG_OP];     // 32 KB
@@ -296,8 +277,8 @@ __global__ __launch_bounds__(MWG_THREADS, 2) void k_mp_pw_wgrad(MwgParams p) {
     const long long rr = (long long)chunk * MWG_ROWS + rec;
     unsigned oa = MPW_OOB, ob = MPW_OOB;
     if (rr < p.rows) {
-      if (a_ch_ok) oa = (unsigned)((mwg_row(p.a, rr) * p.a.ld + n0 + ch_in) * 2);
-      if (b_ch_ok) ob = (unsigned)((mwg_row(p.b, rr) * p.b.ld + k0 + ch_in) * 2);
+      if (a_ch_ok) oa = (unsigned)((map_row(p.a, rr) * p.a.ld + n0 + ch_in) * 2);
+      if (b_ch_ok) ob = (unsigned)((map_row(p.b, rr) * p.b.ld + k0 + ch_in) * 2);
     }
     unsigned char *base = lds + (st % MWG_NST) * 2 * MWG_OP + wave * 1024;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_void *)base, 16, (int)oa, 0, 0, 0);
@@ -347,30 +328,6 @@ __global__ __launch_bounds__(MWG_THREADS, 2) void k_mp_pw_wgrad(MwgParams p) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_mp_pw_reduce(const float *__restrict__ part, int nsplit, int n, int k, int n_r, int k_r,
-                                                     float *__restrict__ out, int ld_out, int accumulate) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const long long t = (long long)blockIdx.x * 64 + lane;
-  float s = 0.f;
-  int kk = 0, nn = 0;
-  if (t < (long long)n * k) {
-    kk = (int)(t % k);
-    nn = (int)(t / k);
-    const float *src = part + (long long)nn * k_r + kk;
-    const long long stride = (long long)n_r * k_r;
-    for (int i = sl; i < nsplit; i += 4) s += src[i * stride];
-  }
-  red[sl][lane] = s;
-  __syncthreads();
-  if (sl == 0 && t < (long long)n * k) {
-    const float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-    float *d = out + (long long)nn * ld_out + kk;
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-inline int mwg_round64(int v) { return (v + 63) / 64 * 64; }
 inline int mwg_split(long long rows, int n_r, int k_r, int *chunks) {
   const long long c = (rows + MWG_ROWS - 1) / MWG_ROWS;
   *chunks = (int)c;
@@ -433,7 +390,7 @@ int pcp_mp_pointwise(const pcp_mp_pointwise_t *d, const void *in, const void *w_
 
 size_t pcp_mp_pointwise_wgrad_workspace_bytes(int64_t rows, int32_t n, int32_t k) {
   int chunks;
-  const int n_r = mwg_round64(n), k_r = mwg_round64(k);
+  const int n_r = round64(n), k_r = round64(k);
   const int ns = mwg_split(rows, n_r, k_r, &chunks);
   return (size_t)ns * n_r * k_r * sizeof(float);
 }
@@ -446,17 +403,9 @@ int pcp_mp_pointwise_wgrad(const pcp_mp_rowmap_t *a, const pcp_mp_rowmap_t *b, i
   if ((((uintptr_t)a->ptr) | ((uintptr_t)b->ptr)) & 15) return PCP_ERR_ARG;
   if (a->extent_bytes == 0 || b->extent_bytes == 0 || a->extent_bytes > 0x7fffffffULL || b->extent_bytes > 0x7fffffffULL) return PCP_ERR_UNSUPPORTED;
   MwgParams p{};
-  auto cvt = [](const pcp_mp_rowmap_t *m) {
-    MwgMap r;
-    r.ptr = m->ptr; r.ld = m->ld; r.ch = m->channels; r.mode = m->lattice ? 1 : 0;
-    r.h = m->grid_h; r.w = m->grid_w; r.ky = m->ky; r.kx = m->kx;
-    r.bytes = (unsigned)m->extent_bytes;
-    return r;
-  };
-  p.a = cvt(a); p.b = cvt(b);
-  if ((p.a.mode && (p.a.h <= 0 || p.a.w <= 0)) || (p.b.mode && (p.b.h <= 0 || p.b.w <= 0))) return PCP_ERR_ARG;
+  if (to_rowmap(a, (unsigned)a->extent_bytes, &p.a) != PCP_OK || to_rowmap(b, (unsigned)b->extent_bytes, &p.b) != PCP_OK) return PCP_ERR_ARG;
   p.rows = rows;
-  p.n_r = mwg_round64(a->channels); p.k_r = mwg_round64(b->channels);
+  p.n_r = round64(a->channels); p.k_r = round64(b->channels);
   p.k_tiles = p.k_r / 64;
   p.nsplit = mwg_split(rows, p.n_r, p.k_r, &p.chunks);
   if (workspace_bytes < (size_t)p.nsplit * p.n_r * p.k_r * sizeof(float)) return PCP_ERR_WORKSPACE;
@@ -464,7 +413,7 @@ int pcp_mp_pointwise_wgrad(const pcp_mp_rowmap_t *a, const pcp_mp_rowmap_t *b, i
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_mp_pw_wgrad, dim3((p.n_r / 64) * p.k_tiles, p.nsplit), dim3(MWG_THREADS), 0, s, p);
   const long long total = (long long)a->channels * b->channels;
-  hipLaunchKernelGGL(k_mp_pw_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float *)workspace, p.nsplit,
+  hipLaunchKernelGGL(k_pw_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float *)workspace, p.nsplit,
                      a->channels, b->channels, p.n_r, p.k_r, out, ld_out, accumulate);
   PCP_CHECK_LAUNCH();
   return PCP_OK;

@@ -32,11 +32,8 @@ constexpr unsigned WG_OOB = 0x80000000u;
 constexpr int WG_THREADS = 512;            // wave = (quadrant of the tile, half of the taps)
 constexpr int WG_DW = 32;                 // dy columns of a strip
 
-#ifndef WG_DEPTH_S1
-#define WG_DEPTH_S1 2
-#endif
 template <int S> struct WgCfg;
-template <> struct WgCfg<1> { static constexpr int TR = 4, XWP = 34, XHALF = 0, DEPTH = WG_DEPTH_S1; };      // XWP: x records per row in LDS; DEPTH: stages of copy in flight (2 measured no faster)
+template <> struct WgCfg<1> { static constexpr int TR = 4, XWP = 34, XHALF = 0, DEPTH = 2; };      // XWP: x records per row in LDS; DEPTH: stages of copy in flight (2 measured no faster)
 template <> struct WgCfg<2> { static constexpr int TR = 2, XWP = 72, XHALF = 36, DEPTH = 1; };     // [parity][36]; a third group ahead would not fit the LDS
 
 struct WgParams {
@@ -46,11 +43,6 @@ struct WgParams {
   int n_cob, n_cib, n_strips, n_rsplit, rows_per, n_split;
   unsigned x_bytes, dy_bytes;
 };
-
-__device__ __forceinline__ int wg_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 #ifdef WG_STAMP
 __device__ unsigned long long wg_stamps[1024 * 24];
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_mp_wgrad3x3(WgParams p) {
 
   // ---- which (pair, split) --------------------------------------------------------------------------------------------------------------
   const int n_pairs = p.n_cob * p.n_cib;
-  int lid = wg_xcd_remap(blockIdx.x, gridDim.x);
+  int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int pair = lid % n_pairs;
   const int split = lid / n_pairs;
   const int cob = pair / p.n_cib, cib = pair % p.n_cib;

@@ -42,6 +42,18 @@ static inline int pcp_zero_async(void *ptr, size_t bytes, hipStream_t stream) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// workgroup -> logical tile.  Blocks b and b+8 share an XCD (round-robin dispatch); give each XCD a contiguous run of logical tiles, so
+// that the tiles which share an input patch (or a stripe of a map) sit on one XCD's L2. Bijective.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+}
+
+// v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
 // ---- workspace layout of pcp_voxelize / pcp_pfn_scatter (offsets in bytes, all 256-B aligned) -----------------------
 struct VoxLayout {
   size_t cell_count;    // int32 [cells]   points per cell (zeroed every call)

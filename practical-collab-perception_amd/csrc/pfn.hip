@@ -67,8 +67,6 @@ __device__ __forceinline__ float fkey_inv(unsigned k) {
 //   max_p fl(c + d_p) = fl(c + max_p d_p) (rounding is monotone).
 constexpr int XLD = 36;           // padded row of the x / xmax0 tiles (floats): conflict-free ds_read_b128 groups
 
-__device__ __forceinline__ f32x16 mfma32p(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
 // The kernel is latency bound (a 64-pillar workgroup holds ~120 points = two chunks behind a chain of dependent global loads): ONE x tile
 // and an extra barrier per chunk keep the LDS at 39 KB, i.e. four workgroups per CU instead of three -- 267 -> 233 us on 1.44 M points.
 constexpr int PFN_NBUF = 1, PFN_WGS = 4;
@@ -273,10 +271,10 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const f32x4 a = *reinterpret_cast<const f32x4 *>(xa + 8 * j);
-      acc = mfma32p(a.x, wp[j].x, acc);
-      acc = mfma32p(a.y, wp[j].y, acc);
-      acc = mfma32p(a.z, wp[j].z, acc);
-      acc = mfma32p(a.w, wp[j].w, acc);
+      acc = mfma32(a.x, wp[j].x, acc);
+      acc = mfma32(a.y, wp[j].y, acc);
+      acc = mfma32(a.z, wp[j].z, acc);
+      acc = mfma32(a.w, wp[j].w, acc);
     }
     if (base == s0) PFN_STAMP_AT(7);
     const int o = ct * 32 + r;
@@ -326,10 +324,10 @@ __global__ __launch_bounds__(PFN_THREADS, PFN_WGS) void k_pfn(PfnParams p) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const f32x4 a = *reinterpret_cast<const f32x4 *>(xa + 8 * j);
-      acc = mfma32p(a.x, wm[j].x, acc);
-      acc = mfma32p(a.y, wm[j].y, acc);
-      acc = mfma32p(a.z, wm[j].z, acc);
-      acc = mfma32p(a.w, wm[j].w, acc);
+      acc = mfma32(a.x, wm[j].x, acc);
+      acc = mfma32(a.y, wm[j].y, acc);
+      acc = mfma32(a.z, wm[j].z, acc);
+      acc = mfma32(a.w, wm[j].w, acc);
     }
     PFN_STAMP_AT(14);
 #pragma unroll

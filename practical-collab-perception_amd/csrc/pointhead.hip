@@ -51,15 +51,11 @@ struct PointHeadParams {
   unsigned char *dyn_mask;
 };
 
-// blocks b and b+8 share an XCD (round-robin dispatch): give each XCD a CONTIGUOUS run of point tiles, so that in the spatially
-// sorted visiting order each XCD's 4 MiB L2 holds only its own stripe of the BEV map (bijective remap)
+// xcd_remap (pcp_common.h) over point tiles: in the spatially sorted visiting order each XCD's 4 MiB L2 holds only its own stripe of the BEV
+// map.  The 64-bit copy stays: with the shared int form k_point_head compiles to other instructions (profiles/conv_helpers_refactor.txt)
 __device__ __forceinline__ long long xcd_remap_ph(long long bid, long long nwg) {
   const long long q = nwg >> 3, r = nwg & 7, x = bid & 7;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ f32x16 mfma_ph(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
 template <int PH_H>
@@ -158,7 +154,6 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   }
   __syncthreads();
 
-#ifndef PH_DIAG_GATHER_ONLY
   // ---- phase 2: H1 partial over this wave's K quarter (96 channels = 12 groups of 8) -----------------------------------------
   {
     f32x16 acc[PH_NT];
@@ -174,10 +169,10 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
 #pragma unroll
       for (int t = 0; t < PH_NT; t++) {
         f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + t * 32 * PH_C + g * 8);
-        acc[t] = mfma_ph(a.x, bq.x, acc[t]);
-        acc[t] = mfma_ph(a.y, bq.y, acc[t]);
-        acc[t] = mfma_ph(a.z, bq.z, acc[t]);
-        acc[t] = mfma_ph(a.w, bq.w, acc[t]);
+        acc[t] = mfma32(a.x, bq.x, acc[t]);
+        acc[t] = mfma32(a.y, bq.y, acc[t]);
+        acc[t] = mfma32(a.z, bq.z, acc[t]);
+        acc[t] = mfma32(a.w, bq.w, acc[t]);
       }
     }
     // the four waves' partials go through `red` one 32-column tile at a time (PH_H = 64: red is reused, not doubled)
@@ -196,7 +191,6 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   }
   __syncthreads();
 
-#ifndef PH_DIAG_SKIP34
   // ---- phase 3: final = relu(H1 W2^T + b2) + F, three 32-channel column tiles per wave, in place -----------------------------
   {
     f32x4 a[PH_H / 8];
@@ -212,10 +206,10 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
 #pragma unroll
       for (int g = 0; g < PH_H / 8; g++) {
         f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + g * 8);
-        acc = mfma_ph(a[g].x, bq.x, acc);
-        acc = mfma_ph(a[g].y, bq.y, acc);
-        acc = mfma_ph(a[g].z, bq.z, acc);
-        acc = mfma_ph(a[g].w, bq.w, acc);
+        acc = mfma32(a[g].x, bq.x, acc);
+        acc = mfma32(a[g].y, bq.y, acc);
+        acc = mfma32(a[g].z, bq.z, acc);
+        acc = mfma32(a[g].w, bq.w, acc);
       }
       const int n = ct * 32 + r;
       const float bias = p.b2[n];
@@ -229,8 +223,6 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   }
   __syncthreads();
 
-#endif
-#if !defined(PH_DIAG_SKIP34) && !defined(PH_DIAG_SKIP4)
   // ---- phase 4: the three heads as one (8 x C) matrix, as an MFMA GEMM with N padded 8 -> 32 (lanes r >= 8 feed zeros): K = C split
   //      over the four waves like phase 2, partials reduced through LDS.  (A per-thread 384-long dot product cost 250 us per launch:
   //      8 threads walking each LDS row serialise on the banks.)
@@ -245,10 +237,10 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
     for (int g = 0; g < 12; g++) {
       f32x4 a = *reinterpret_cast<const f32x4 *>(asrc + g * 8);
       f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + g * 8);
-      acc = mfma_ph(a.x, bq.x * bmask, acc);
-      acc = mfma_ph(a.y, bq.y * bmask, acc);
-      acc = mfma_ph(a.z, bq.z * bmask, acc);
-      acc = mfma_ph(a.w, bq.w * bmask, acc);
+      acc = mfma32(a.x, bq.x * bmask, acc);
+      acc = mfma32(a.y, bq.y * bmask, acc);
+      acc = mfma32(a.z, bq.z * bmask, acc);
+      acc = mfma32(a.w, bq.w * bmask, acc);
     }
     if (r < PH_NOUT) {
 #pragma unroll
@@ -325,8 +317,6 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
       }
     }
   }
-#endif
-#endif  // PH_DIAG_GATHER_ONLY
 }
 
 }  // namespace

@@ -7,9 +7,9 @@
 //   looks the 128 input cells of the tap up in the pillariser's cell -> pillar-rank table (pcp_voxelize workspace),
 //   compacts the occupied ones (ballot prefix, pixel order) into rows of at most 32,
 //   gathers their 64-float pillar rows into an LDS A tile (four chunks in flight in a register ring) and multiplies
-//   [32 x 64] x [64 x C] on v_mfma_f32_16x16x4_f32 (wave = 16-row half x 32-channel half over the whole K, the tap's weight fragments
-//   from L2 straight into registers, two items ahead),
-//   adds its final product block straight into the pixels' accumulators in LDS (one barrier per chunk).
+//   [32 x 64] x [64 x C] on v_mfma_f32_16x16x4_f32 (wave = 16 output channels over all rows and the whole K, the tap's weight fragments
+//   from L2 straight into registers),
+//   adds its final product block straight into the pixels' accumulators in LDS (one barrier per two chunks).
 // No atomics and a fixed summation order (taps ascending, K halves fixed): deterministic.  Work: 2.25 products per pillar instead of
 // 9 per output pixel, i.e. ~4x fewer MFMAs at 20 % occupancy after padding the row tiles to 32; the dense canvas is neither read nor
 // (when no caller asks for `spatial_features`) written.
@@ -37,11 +37,7 @@ struct SpParams {
 template <bool OUT_BF16>
 __global__ __launch_bounds__(SP_THREADS, 2) void k_sparse_conv_s2(SpParams p) {
   __shared__ __attribute__((aligned(16))) float acc[SP_PIX * 64];          // per-pixel accumulators
-#ifdef SP_ROW_SPLIT
-  __shared__ __attribute__((aligned(16))) float atile[2][32 * SP_ALD];      // gathered pillar rows of the chunk (double buffered)
-#else
   __shared__ __attribute__((aligned(16))) float atile[4][32 * SP_ALD];      // gathered pillar rows of two stages x two items
-#endif
   __shared__ int row_rank[9][SP_PIX];                                       // compacted (tap-wise) pillar ranks ...
   __shared__ unsigned char row_pix[9][SP_PIX];                              // ... and the output pixel each row belongs to
   __shared__ int cnt[9][2];
@@ -91,132 +87,10 @@ __global__ __launch_bounds__(SP_THREADS, 2) void k_sparse_conv_s2(SpParams p) {
   }
   __syncthreads();
 
-#ifdef SP_ROW_SPLIT
-  if (total > 0) {
-    // wave = (16-row half of the chunk, 32-channel half of the outputs): its product block [16 x 32] over the whole K = 64 is final, so
-    // it is added straight into the accumulators of its rows' pixels -- no partial sums, no result tile in LDS, ONE barrier per item
-    // (in-kernel stamps of the first version, which split K over the waves: result tile write 430 + second barrier 150 +
-    // scatter-add 1 450 of 4 300 cycles per item)
-    const int rh = wave >> 1, nh = wave & 1;
-    const int m16 = lane & 15, q4 = lane >> 4;
-    const int g_row = tid >> 3, g_q = (tid & 7) * 2;                       // gather: row, first of two 16-byte columns
-    // work items = (tap, 32-row chunk) in ascending order (thread 0 lists them; at most 9 taps x 4 chunks)
-    __shared__ unsigned char item_tap[36], item_chunk[36];
-    __shared__ int n_items_s;
-    if (tid == 0) {
-      int k = 0;
-      for (int t = 0; t < 9; t++)
-        for (int c0 = 0; c0 < cnt[t][0] + cnt[t][1]; c0 += 32) { item_tap[k] = (unsigned char)t; item_chunk[k] = (unsigned char)(c0 >> 5); k++; }
-      n_items_s = k;
-    }
-    __syncthreads();
-    const int n_items = n_items_s;
-    // Register rings, statically indexed through the 4x unrolled loop: the pillar rows of four items and the weight fragments of two
-    // items ahead are in flight (a dependent L2 / HBM access costs ~2 us, an item ~1 us).  All loads are UNCONDITIONAL with clamped
-    // indices (rows past the chunk re-read a valid row and are zeroed when they are stored to LDS), so the number of outstanding
-    // loads is static and hipcc's counted s_waitcnt waits for the oldest slot only.
-    constexpr int DEPTH = 4;
-    f32x4 g[DEPTH][2];
-    f32x4 wq[2][2][4];                                   // [ring slot][16-channel subtile][k group j]: W[t][32 nh + 16 s + m16][16 j + 4 q4 ..]
-    auto gather = [&](int k, f32x4 (&dst)[2]) {
-      const int kc = min(k, n_items - 1);
-      const int t = item_tap[kc], c0 = item_chunk[kc] * 32;
-      const int row = min(c0 + g_row, cnt[t][0] + cnt[t][1] - 1);
-      const float *src = p.pf + (long long)row_rank[t][row] * SP_CIN + g_q * 4;
-      dst[0] = *reinterpret_cast<const f32x4 *>(src);
-      dst[1] = *reinterpret_cast<const f32x4 *>(src + 4);
-    };
-    auto wload = [&](int k, f32x4 (&dst)[2][4]) {
-      const int t = item_tap[min(k, n_items - 1)];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; s2++) {
-        const float *wr = p.w + ((long long)(t * 64 + nh * 32 + s2 * 16 + m16)) * SP_CIN + 4 * q4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) dst[s2][j] = *reinterpret_cast<const f32x4 *>(wr + 16 * j);
-      }
-    };
-    wload(0, wq[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    wload(1, wq[1]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < DEPTH; u++) {
-      gather(u, g[u]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // one pipeline stage = one item; ring slots are indexed by the compile-time stage number u
-    auto stage = [&](int k, f32x4 (&gu)[2], f32x4 (&wu)[2][4], float *at) {
-          const int t = item_tap[k], c0 = item_chunk[k] * 32;
-      const int rows = min(32, cnt[t][0] + cnt[t][1] - c0);
-      const bool live = g_row < rows;
-      const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4 *>(at + g_row * SP_ALD + g_q * 4) = live ? gu[0] : zero4;
-      *reinterpret_cast<f32x4 *>(at + g_row * SP_ALD + g_q * 4 + 4) = live ? gu[1] : zero4;
-      __builtin_amdgcn_sched_barrier(0);
-      gather(k + DEPTH, gu);
-      __builtin_amdgcn_sched_barrier(0);
-      // pixels of this lane's four rows (16 rh + 4 q4 + i): four consecutive bytes of the compaction table, one LDS read
-      const unsigned pix4 = *reinterpret_cast<const unsigned *>(&row_pix[t][min(c0 + rh * 16 + q4 * 4, SP_PIX - 4)]);
-      __syncthreads();
-      // [16 rows x 64] x [64 x 32] on v_mfma_f32_16x16x4_f32; MFMA (j, kk) multiplies k = 16 j + 4 q4 + kk
-      typedef float f32x4c __attribute__((ext_vector_type(4)));
-      f32x4c c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
-      const float *xa = at + (rh * 16 + m16) * SP_ALD + 4 * q4;
-      f32x4 a[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) a[j] = *reinterpret_cast<const f32x4 *>(xa + 16 * j);
-      // the accumulators' old values do not depend on the products: requested BEFORE the MFMAs so their LDS round trip (and that of
-      // the pixel look-up above) runs under the matrix work instead of after it (in-kernel stamps: 1 600 + 800 of 4 700 cycles per item)
-      int pixs[4];
-      float old0[4], old1[4];
-      const int col = nh * 32 + m16;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int row = rh * 16 + q4 * 4 + i;
-        pixs[i] = row < rows ? (int)((pix4 >> (8 * i)) & 255u) : -1;
-        const int pa = pixs[i] >= 0 ? pixs[i] : 0;
-        old0[i] = acc[pa * 64 + col];
-        old1[i] = acc[pa * 64 + col + 16];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-          c0v = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][kk], wu[0][j][kk], c0v, 0, 0, 0);
-          c1v = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][kk], wu[1][j][kk], c1v, 0, 0, 0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-      wload(k + 2, wu);                       // this slot's fragments are consumed: refill it for the item after next
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        if (pixs[i] >= 0) {
-          acc[pixs[i] * 64 + col] = old0[i] + c0v[i];
-          acc[pixs[i] * 64 + col + 16] = old1[i] + c1v[i];
-        }
-    };
-    // Main loop: groups of DEPTH items with NO conditional stage, so the number of loads in flight at every wait is static (a guard
-    // around a stage makes it path dependent and hipcc falls back to s_waitcnt vmcnt(0): every item then waits for the gather it has
-    // just issued -- the reason prefetch depth, resident weights and occupancy all measured the same 127-133 us).
-    int k0 = 0;
-    for (; k0 + DEPTH <= n_items; k0 += DEPTH) {
-      stage(k0 + 0, g[0], wq[0], atile[0]);
-      stage(k0 + 1, g[1], wq[1], atile[1]);
-      stage(k0 + 2, g[2], wq[0], atile[0]);
-      stage(k0 + 3, g[3], wq[1], atile[1]);
-    }
-    // tail: the remaining (< DEPTH) items already sit in ring slots 0 ..
-    if (k0 + 0 < n_items) stage(k0 + 0, g[0], wq[0], atile[0]);
-    if (k0 + 1 < n_items) stage(k0 + 1, g[1], wq[1], atile[1]);
-    if (k0 + 2 < n_items) stage(k0 + 2, g[2], wq[0], atile[0]);
-    __syncthreads();
-  }
-
-#else
   if (total > 0) {
     // Round 3: wave w owns output channels [16 w, 16 w + 16) for ALL rows of an item, so an accumulator word (pixel, channel) is only ever
     // touched by one wave: the read-modify-write of the per-pixel accumulators needs no cross-wave ordering and TWO items (taps) share one
-    // barrier -- 64 instead of 32 MFMAs per wave between barriers, half the barriers (the row-split form sat at 22 - 25 % matrix-pipe busy:
+    // barrier -- 64 instead of 32 MFMAs per wave between barriers, half the barriers (the row-split form, DESIGN_HISTORY.md section 9, sat at 22 - 25 % matrix-pipe busy:
     // ~4 300 cycles per item around 1 024 cycles of MFMA).  Same products in the same order per (row, channel): results are bit-identical.
     const int m16 = lane & 15, q4 = lane >> 4;
     const int g_row = tid >> 3, g_q = (tid & 7) * 2;                       // gather: row, first of two 16-byte columns
@@ -351,7 +225,6 @@ __global__ __launch_bounds__(SP_THREADS, 2) void k_sparse_conv_s2(SpParams p) {
     if (k0 + 2 < n_items) stage(k0 + 2, g[2], g[3], wq[2], wq[3], atile[2], atile[3]);
     __syncthreads();
   }
-#endif
 
   // ---- epilogue: bias + ReLU, one 256-byte row per pixel --------------------------------------------------------------------------
   {

@@ -9,7 +9,7 @@
 // VGPRs), stages one dy tile and ONE input patch with halo per pixel tile in LDS and re-reads the patch at the nine shifts
 // (9 MFMAs per 10 ds_read_b32).  The pixel range is split over blockIdx.y; partial sums go to a workspace in a fixed order and
 // are reduced by a second kernel (deterministic, no float atomics), which also emits PyTorch's (cout, cin, 3, 3) layout.
-#include "pcp_common.h"
+#include "splitk_common.h"
 
 namespace {
 
@@ -179,22 +179,6 @@ __global__ __launch_bounds__(256) void k_wgrad3x3_reduce(const float *__restrict
 }
 
 // ---- pointwise family -------------------------------------------------------------------------------------------------------
-struct RowMap {
-  const float *ptr;
-  int ld, ch;                  // pixel stride, valid channels
-  int mode;                    // 0: pixel = r;  1: r = (b, y, x) on an (h, w) grid -> pixel (b, 2y + ky, 2x + kx) of a (2h, 2w) grid
-  int h, w, ky, kx;
-};
-
-__device__ __forceinline__ long long map_row(const RowMap &m, long long r) {
-  if (m.mode == 0) return r;
-  const int x = (int)(r % m.w);
-  const long long t = r / m.w;
-  const int y = (int)(t % m.h);
-  const long long b = t / m.h;
-  return (b * 2 * m.h + 2 * y + m.ky) * 2 * m.w + 2 * x + m.kx;
-}
-
 struct WgPwParams {
   RowMap a, b;                 // out[n][k] = sum_r a[map(r)][n] * b[map(r)][k]
   long long rows;
@@ -237,8 +221,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad_pw(WgPwParams p) {
       ra[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       rb[u] = ra[u];
       if (r < p.rows) {
-        if (n0 + q * 4 < p.a.ch) ra[u] = *reinterpret_cast<const float4 *>(p.a.ptr + map_row(p.a, r) * p.a.ld + n0 + q * 4);
-        if (k0 + q * 4 < p.b.ch) rb[u] = *reinterpret_cast<const float4 *>(p.b.ptr + map_row(p.b, r) * p.b.ld + k0 + q * 4);
+        if (n0 + q * 4 < p.a.ch) ra[u] = *reinterpret_cast<const float4 *>((const float *)p.a.ptr + map_row(p.a, r) * p.a.ld + n0 + q * 4);
+        if (k0 + q * 4 < p.b.ch) rb[u] = *reinterpret_cast<const float4 *>((const float *)p.b.ptr + map_row(p.b, r) * p.b.ld + k0 + q * 4);
       }
     }
   };
@@ -277,33 +261,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad_pw(WgPwParams p) {
     const int n = n0 + wn + (r >> 2) * 8 + hl * 4 + (r & 3);
     out[(long long)n * p.k_r + k0 + wk + l32] = acc[r];
   }
-  // (quadrants without channels are not written: k_wgrad_pw_reduce reads n < channels, k < channels only)
+  // (quadrants without channels are not written: k_pw_reduce reads n < channels, k < channels only)
 }
-
-__global__ __launch_bounds__(256) void k_wgrad_pw_reduce(const float *__restrict__ part, int nsplit, int n, int k, int n_r, int k_r,
-                                                        float *__restrict__ out, int ld_out, int accumulate) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const long long t = (long long)blockIdx.x * 64 + lane;
-  float s = 0.f;
-  int kk = 0, nn = 0;
-  if (t < (long long)n * k) {
-    kk = (int)(t % k);
-    nn = (int)(t / k);
-    const float *src = part + (long long)nn * k_r + kk;
-    const long long stride = (long long)n_r * k_r;
-    for (int i = sl; i < nsplit; i += 4) s += src[i * stride];
-  }
-  red[sl][lane] = s;
-  __syncthreads();
-  if (sl == 0 && t < (long long)n * k) {
-    const float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-    float *d = out + (long long)nn * ld_out + kk;
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-inline int round64(int v) { return (v + 63) / 64 * 64; }
 
 struct Wg3Plan { int th, tw, tiles_y, tiles_x, n_tiles, nsplit, cout_r, cin_r; };
 
@@ -391,14 +350,7 @@ int pcp_pointwise_wgrad(const pcp_rowmap_t *a, const pcp_rowmap_t *b, int64_t ro
   if ((a->channels & 3) || (b->channels & 3) || (a->ld & 3) || (b->ld & 3) || a->channels <= 0 || b->channels <= 0) return PCP_ERR_ARG;
   if ((((uintptr_t)a->ptr) | ((uintptr_t)b->ptr)) & 15) return PCP_ERR_ARG;
   WgPwParams p{};
-  auto cvt = [](const pcp_rowmap_t *m) {
-    RowMap r;
-    r.ptr = m->ptr; r.ld = m->ld; r.ch = m->channels; r.mode = m->lattice ? 1 : 0;
-    r.h = m->grid_h; r.w = m->grid_w; r.ky = m->ky; r.kx = m->kx;
-    return r;
-  };
-  p.a = cvt(a); p.b = cvt(b);
-  if ((p.a.mode && (p.a.h <= 0 || p.a.w <= 0)) || (p.b.mode && (p.b.h <= 0 || p.b.w <= 0))) return PCP_ERR_ARG;
+  if (to_rowmap(a, 0, &p.a) != PCP_OK || to_rowmap(b, 0, &p.b) != PCP_OK) return PCP_ERR_ARG;
   p.rows = rows;
   p.n_r = round64(a->channels); p.k_r = round64(b->channels);
   p.k_tiles = p.k_r / 64;
@@ -408,7 +360,7 @@ int pcp_pointwise_wgrad(const pcp_rowmap_t *a, const pcp_rowmap_t *b, int64_t ro
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_wgrad_pw, dim3((p.n_r / 64) * p.k_tiles, p.nsplit), dim3(WG_THREADS), 0, s, p);
   const long long total = (long long)a->channels * b->channels;
-  hipLaunchKernelGGL(k_wgrad_pw_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float *)workspace, p.nsplit,
+  hipLaunchKernelGGL(k_pw_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float *)workspace, p.nsplit,
                      a->channels, b->channels, p.n_r, p.k_r, out, ld_out, accumulate);
   PCP_CHECK_LAUNCH();
   return PCP_OK;

@@ -23,12 +23,7 @@
 #include "pcp_common.h"
 
 #ifdef WINO_STAMP
-#ifndef WINO_STAMP_S0
-#define WINO_STAMP_S0 16
-#endif
-#ifndef WINO_STAMP_BLOCK
-#define WINO_STAMP_BLOCK 0
-#endif
+constexpr int WINO_STAMP_S0 = 16, WINO_STAMP_BLOCK = 0;     // the eight slices and the workgroup that are stamped
 __device__ unsigned long long wino_dbg[8 * 8 * 8];          // [slice 0..7][wave][stamp]
 #define STAMP(slot)                                                                             \
   do {                                                                                          \
@@ -65,15 +60,6 @@ struct WinoParams {
   int tiles_x, tiles_y, n_spatial;
 };
 
-__device__ __forceinline__ int xcd_remap_w(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ f32x16 mfma32w(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // RT = 32-tile row blocks per workgroup: RT = 2 -> 16x16 output pixels (64 tiles, 1 workgroup per CU, least weight traffic:
 // the large-Cin layers); RT = 1 -> 8 rows x 16 columns of pixels (32 tiles, 2 workgroups per CU so one's prologue/epilogue
 // hides under the other's main loop: the short-K layers).
@@ -104,7 +90,7 @@ __global__ __launch_bounds__(WTHREADS, (RT == 2 ? 2 : 4)) void k_conv3x3_wino(Wi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
 
-  const int lid = xcd_remap_w(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = lid / p.n_spatial;                    // N-tile is the slow index: one XCD works on few N-tiles at a time,
   int sp = lid % p.n_spatial;                          // so their transformed weights stay in that XCD's L2
   const int tile_x = sp % p.tiles_x;
@@ -224,10 +210,10 @@ __global__ __launch_bounds__(WTHREADS, (RT == 2 ? 2 : 4)) void k_conv3x3_wino(Wi
         f32x4 a = *reinterpret_cast<const f32x4 *>(vsrc + (pi * C::TILES + rt * 32) * WLD);
 #pragma unroll
         for (int ct = 0; ct < 2; ct++) {
-          acc[pi][rt][ct] = mfma32w(a.x, bf[pi][ct].x, acc[pi][rt][ct]);
-          acc[pi][rt][ct] = mfma32w(a.y, bf[pi][ct].y, acc[pi][rt][ct]);
-          acc[pi][rt][ct] = mfma32w(a.z, bf[pi][ct].z, acc[pi][rt][ct]);
-          acc[pi][rt][ct] = mfma32w(a.w, bf[pi][ct].w, acc[pi][rt][ct]);
+          acc[pi][rt][ct] = mfma32(a.x, bf[pi][ct].x, acc[pi][rt][ct]);
+          acc[pi][rt][ct] = mfma32(a.y, bf[pi][ct].y, acc[pi][rt][ct]);
+          acc[pi][rt][ct] = mfma32(a.z, bf[pi][ct].z, acc[pi][rt][ct]);
+          acc[pi][rt][ct] = mfma32(a.w, bf[pi][ct].w, acc[pi][rt][ct]);
         }
       }
   };

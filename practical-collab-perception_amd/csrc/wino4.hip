@@ -34,11 +34,6 @@ struct W4Geom {
   int ld_in, ld_out, relu;
 };
 
-__device__ __forceinline__ int xcd_remap_g(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 // B^T x for the 6-point transform (Lavin & Gray, F(4,3))
 __device__ __forceinline__ void bt6(const f32x4 d0, const f32x4 d1, const f32x4 d2, const f32x4 d3, const f32x4 d4, const f32x4 d5,
                                     f32x4 (&t)[6]) {
@@ -158,7 +153,6 @@ struct GemmParams {
   int m_tiles, n_tiles;
 };
 
-__device__ __forceinline__ f32x16 mfma32g(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 __global__ __launch_bounds__(G_THREADS, 2) void k_w4_gemm(GemmParams p) {
   __shared__ __attribute__((aligned(16))) float lds[4 * G_TILE_FLOATS];          // A[2] | B[2]
@@ -241,7 +235,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_w4_gemm(GemmParams p) {
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
-          for (int c = 0; c < 2; c++) acc[i][c] = mfma32g(af[i][kk], bf[c][kk], acc[i][c]);
+          for (int c = 0; c < 2; c++) acc[i][c] = mfma32(af[i][kk], bf[c][kk], acc[i][c]);
     }
   };
   auto store_tile = [&](int t) {

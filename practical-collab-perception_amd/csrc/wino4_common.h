@@ -1,5 +1,5 @@
-// What the fused Winograd F(4x4, 3x3) kernels share: the XCD remap (k_wino4f, k_wino4h, k_wino4c) and, for the two half-size kernels
-// k_wino4h (wino4h.hip) and k_wino4c (wino4c.hip), which differ only in how the waves split the products and in the output transform: the
+// What the fused Winograd F(4x4, 3x3) kernels share beyond pcp_common.h (whose XCD remap k_wino4f, k_wino4h and k_wino4c use): for the two half-size
+// kernels k_wino4h (wino4h.hip) and k_wino4c (wino4c.hip), which differ only in how the waves split the products and in the output transform: the
 // item geometry, the launch parameters, the 6-point transforms and the stand-alone input transform.  The two kernels give the same bits
 // (tests/test_gpu_ops.py) BECAUSE these are one instruction sequence: change them here, for both.  The raw-patch staging is the same text in
 // both kernels and stays there: moved here, in any form tried, its offset set-up compiles to other instructions (profiles/wino4_refactor.txt).
@@ -23,12 +23,6 @@
 #endif
 
 namespace {
-
-// workgroup -> item: consecutive items on ONE XCD (the hardware deals consecutive workgroups round robin over the eight)
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 // ---- the half-size item: 16 x 16 output pixels (16 Winograd tiles) x 64 output channels, 8-channel slices ------------------------------------
 constexpr int H4_CK = 8;                                  // input channels per slice

@@ -42,11 +42,6 @@ struct WsParams {
   int tiles_x, tiles_y, n_spatial;
 };
 
-__device__ __forceinline__ int xcd_remap_ws(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 template <int CHUNK>
 struct WsCfg {
   static constexpr int CB = 2;                      // 32-channel output blocks per workgroup
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
   const int ph = wave >> 1;                     // position half: Winograd position rows {0,1} or {2,3}
   const int cb = wave & 1;                      // 32-channel output block inside the workgroup's 64-channel N tile
 
-  const int lid = xcd_remap_ws(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = lid / p.n_spatial;             // N tile is the slow index (its weights stay in the XCD's L2)
   int sp = lid % p.n_spatial;
   const int tile_x = sp % p.tiles_x;
@@ -144,10 +139,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
   auto raw_read = [&](const float *buf, int kp) {
     const float *src = buf + 2 * kp * C::PLANE;
     Raw d;
-#ifdef WS_DIAG_NO_LDSREAD
-    d.p0 = d.p1 = d.q0 = d.q1 = d.s0 = d.s1 = float2{sgn * (float)kp, (float)lane};   // timing-only build: no LDS reads in the loop
-    return d;
-#endif
     d.p0 = *reinterpret_cast<const float2 *>(src + offP);
     d.p1 = *reinterpret_cast<const float2 *>(src + offP + 2);
     d.q0 = *reinterpret_cast<const float2 *>(src + offQ);
@@ -157,10 +148,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
     return d;
   };
   auto transform = [&](const Raw &d, float (&a)[8]) {
-#ifdef WS_DIAG_NO_XFORM
-    a[0] = d.p0.x; a[1] = d.p0.y; a[2] = d.p1.x; a[3] = d.p1.y; a[4] = d.q0.x; a[5] = d.q0.y; a[6] = d.s0.x; a[7] = d.s1.y;   // timing only
-    return;
-#endif
     const float ta0 = d.p0.x - d.q0.x, ta1 = d.p0.y - d.q0.y, ta2 = d.p1.x - d.q1.x, ta3 = d.p1.y - d.q1.y;
     const float tb0 = fmaf(sgn, d.s0.x, d.q0.x), tb1 = fmaf(sgn, d.s0.y, d.q0.y), tb2 = fmaf(sgn, d.s1.x, d.q1.x),
                 tb3 = fmaf(sgn, d.s1.y, d.q1.y);
@@ -181,9 +168,6 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
   const unsigned u_lane = (unsigned)lane * 16u;
   f32x4 bq[4][2];
   auto b_load = [&](int kpg, f32x4 (&dst)[2]) {
-#ifdef WS_DIAG_NO_BLOAD
-    if (kpg > 1) return;                                                             // timing-only build: B stays in registers
-#endif
     const char *s = ubase + kpg * u_kp_bytes;                                        // wave-uniform
     dst[0] = *reinterpret_cast<const f32x4 *>(s + u_lane);
     dst[1] = *reinterpret_cast<const f32x4 *>(s + 1024 + u_lane);
@@ -218,9 +202,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
       if (kp + 1 < C::KP) dn = raw_read(buf, kp + 1);
       b_load(kp0 + kp + 2, bq[(kp + 2) & 3]);
       // the next stage's raw patch is requested late in this stage so that the in-order vmcnt of the B fragments never waits on it
-#ifndef WS_DIAG_NO_STAGE
       if (kp == C::KP - 3) raw_load(min(s + 1, n_stages - 1));
-#endif
       __builtin_amdgcn_sched_barrier(0);          // every request above stays ahead of this step's MFMAs in program order
       const f32x4 b0 = bq[kp & 3][0], b1 = bq[kp & 3][1];
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[0], b0.x, acc[0], 0, 0, 0);
@@ -247,14 +229,9 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_wino_ws(WsParams p) {
         for (int i = 0; i < 8; i++) a_cur[i] = a_nxt[i];
       }
     }
-#ifndef WS_DIAG_NO_STAGE
     if (s + 1 < n_stages) raw_store((s + 1) & 1);
     __syncthreads();
-#endif
   }
-#ifdef WS_DIAG_NO_STAGE
-  __syncthreads();
-#endif
 
   // ---- epilogue: Y = A^T M A with A^T = [[1,1,1,0],[0,1,-1,-1]], split over the two position halves.
   //      half 0 holds M rows 0, 1:  u0 = M0 + M1, u1 = M1;  half 1 holds M rows 2, 3:  u0 = M2, u1 = -(M2 + M3).
