@@ -53,7 +53,8 @@ enum {
                                    (workgroup, cell) pair (built-in); 0 = one global atomic per row (rounds 1 - 5) */
   PCP_OPT_CONV_S2_FORM = 7,     /* pcp_conv3x3, stride 2, cout_pad % 64 == 0: 1 = the 8 x 8-pixel x 64-channel form of k_conv3x3, 2 = the wide form
                                    k_conv3x3_s2w (bit-identical; built-in: the wide form) */
-  PCP_OPT_COUNT = 8
+  PCP_OPT_GTS_PASTE_FORM = 8,   /* pcp_gt_sample_paste_points: 1 = one thread per output row, no LDS (built-in 0: 512-row tiles staged through LDS) */
+  PCP_OPT_COUNT = 9
 };
 int pcp_set_option(int32_t option, int64_t value);
 int64_t pcp_get_option(int32_t option);          /* the override, or -1 while the built-in rule applies (also for an unknown option) */

@@ -508,6 +508,50 @@ int pcp_world_augment_points(const pcp_world_aug_t *aug, const float *table, con
 int pcp_world_augment_boxes(const pcp_world_aug_t *aug, const float *table, float *gt_boxes, int32_t max_boxes, int32_t box_width,
                             float *instances_tf, int32_t n_sweeps, int32_t tf_rows, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * gt_sampling on a collated training batch (the reference's DataBaseSampler.__call__ / add_sampled_boxes_to_scene, which it runs per
+ * sample on the host; csrc/gt_sample.hip).  The host draws the candidates (the numpy pointer / permutation state machine) and writes
+ *   frame_table (device, batch x (n_groups + 2) int32), per frame: [0] n_own = its real gt boxes (class column > 0, rows 0 .. n_own - 1),
+ *               [1 + g] .. [2 + g] = the candidate slots of sample group g, in class order;
+ *   cand_db     (device, n_cand int32) the database index of every candidate slot;
+ *   cand_box    (device, n_cand x PCP_GTS_CAND_STRIDE float32) [x y z dx dy dz heading, vx vy mapped into the frame, 1-based class id].
+ * The device decides which candidates collide and pastes the others.  accepted (device, batch x acc_cap x PCP_GTS_ACC_STRIDE int32), per
+ * frame and accepted object in order: [slot, database index, exclusive prefix of the point counts, point count];
+ * counts (device, 2 batch + 1 int32): [b] accepted objects, [batch + b] rows added, [2 batch] the error word of the paste.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_GTS_MAX_GROUPS 16  /* sample groups (classes) */
+#define PCP_GTS_MAX_CAND 64    /* candidates per class per frame */
+#define PCP_GTS_MAX_BOXES 512  /* existing + accepted boxes per frame; the host wrapper refuses existing + CANDIDATE boxes above it, since every candidate may be accepted */
+#define PCP_GTS_CAND_STRIDE 10
+#define PCP_GTS_ACC_STRIDE 4
+
+/* One workgroup per frame walks the groups in order: a candidate is accepted iff its rotated BEV IoU (the arithmetic of pcp_nms_rotated /
+ * pcp_boxes_bev_pairwise) with every existing box and with every OTHER candidate of its group is 0; the accepted boxes join the existing
+ * ones before the next group.  gt_boxes (batch, max_boxes, box_width 8 | 10); db_count (n_db int32) the points of every database object.
+ * Also clears the error word. */
+int pcp_gt_sample_select(const float *gt_boxes, int32_t batch, int32_t max_boxes, int32_t box_width, const int32_t *frame_table,
+                         int32_t n_groups, const int32_t *cand_db, const float *cand_box, int32_t n_cand, const int32_t *db_count, int32_t n_db,
+                         int32_t *accepted, int32_t acc_cap, int32_t *counts, void *stream);
+
+/* out (capacity n + max_added rows of row_stride floats, 16-byte aligned like points): every frame's own rows in their input order followed
+ * by its accepted objects' stored rows (db_points rows of row_stride - 1 floats starting at row db_offset[db]) in order, column 0 = the
+ * frame index, xyz + the candidate's float32 box centre (a float32 add), column inst_col = n_own + the object's position in the frame's
+ * accepted list, every other column bit for bit.  The input rows must be grouped by ascending frame index; the first row of every frame is
+ * found on the device (segments: batch + 1 int32 of scratch).  A descending neighbour pair (error word 1) or a frame index outside
+ * [0, batch) (2) sets counts[2 batch] and nothing is written.  max_added: an upper bound of the rows added (the grid is sized by it).
+ * Two launches, no atomics: a call repeats bit for bit. */
+int pcp_gt_sample_paste_points(const float *points, int64_t n, int32_t row_stride, int32_t batch, const int32_t *frame_table, int32_t n_groups,
+                               const int32_t *accepted, int32_t acc_cap, const int32_t *counts, const float *cand_box, const float *db_points,
+                               const int32_t *db_offset, int32_t inst_col, int64_t max_added, float *out, int32_t *segments, void *stream);
+
+/* gt_out (batch, max_boxes_out, box_width) and tf_out (nullable; batch, max_boxes_out, n_sweeps, tf_rows 3 | 4, 4): own rows bit for bit,
+ * then the accepted objects (box7, vx vy of cand_box when box_width is 10, the class id; the first tf_rows rows of db_tf (n_db, n_sweeps,
+ * 4, 4)), then padding as the collation writes it (zero boxes, identity 3 x 3).  One launch. */
+int pcp_gt_sample_paste_boxes(const float *gt_boxes, int32_t batch, int32_t max_boxes, int32_t box_width, const float *instances_tf,
+                              int32_t n_sweeps, int32_t tf_rows, const int32_t *frame_table, int32_t n_groups, const int32_t *accepted,
+                              int32_t acc_cap, const int32_t *counts, const float *cand_box, const float *db_tf, float *gt_out, float *tf_out,
+                              int32_t max_boxes_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

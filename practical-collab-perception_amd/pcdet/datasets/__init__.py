@@ -36,6 +36,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
             self.layout = 'nusc_map'       # the five HD-map layers behind the timestamp (synth.nusc_cloud with_map)
             self.points_per_agent = int(syn.get('POINTS_PER_FRAME', self.points_per_agent))   # the nuScenes configs size the frame
         self.xy_half = float(syn.get('XY_HALF', 52.0))
+        self.gt_boxes_max = int(syn.get('GT_BOXES', 40))      # boxes of a training frame before the index-dependent cut
 
     @property
     def mode(self):
@@ -57,6 +58,14 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
             parts.append(c)
         meta = {'sample_token': 'synthetic_%06d' % index, 'lidar_id': 1,
                 'se3_from_ego': {a: synth.agent_pose(a) for a in range(n_agents) if a != 1}}
+        if self.training and self.dataset_cfg.DATASET == 'NuScenesDataset':
+            # the pose gt_sampling maps a database object's global velocity with (database_sampler.py reads metadata['tf_target_from_glob'])
+            r = np.random.RandomState(77000 + int(index))
+            yaw = r.uniform(-np.pi, np.pi)
+            T = np.eye(4)
+            T[:2, :2] = [[np.cos(yaw), -np.sin(yaw)], [np.sin(yaw), np.cos(yaw)]]
+            T[:3, 3] = [r.uniform(-200.0, 200.0), r.uniform(-200.0, 200.0), r.uniform(-1.0, 1.0)]
+            meta['tf_target_from_glob'] = T
         if self.dataset_cfg.DATASET == 'V2XSimDataset_EGO_LATE':
             # box-level fusion reads every agent's detections from the exchange database (v2x_sim_dataset_ego_late.py): synthetic stand-in
             # = 40 boxes per agent, neighbouring agents reporting overlapping boxes so that the NMS has something to merge
@@ -91,8 +100,9 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         out[:, 8] = gt[:, 7]
         return out[agent::2].copy()                       # every agent sees a different subset
 
-    def synthetic_gt_boxes(self, index, n_max=40):
+    def synthetic_gt_boxes(self, index, n_max=None):
         """(n, 8) [x, y, z, dx, dy, dz, heading, class] car-sized boxes inside the range, n varies with the frame"""
+        n_max = self.gt_boxes_max if n_max is None else n_max
         n = n_max - (index % 7)
         s = synth.SEED_BASE + 5000 + index
         r = self.point_cloud_range
@@ -107,7 +117,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
         gt[:, 7] = np.floor(synth.uniform(s, 8, n, 1.0, len(self.class_names) + 0.999))
         return gt
 
-    def synthetic_gt_boxes_velocity(self, index, n_max=40):
+    def synthetic_gt_boxes_velocity(self, index, n_max=None):
         """(n, 10) [x, y, z, dx, dy, dz, heading, vx, vy, class]: the boxes of synthetic_gt_boxes with the velocity the foreground of
         synth.nusc_instance_foreground moves at (odd rows drive along their heading, even rows stand still); the centre of the LAST row is
         put outside the range, so that the corrector's box filter has a row to drop"""

@@ -5,8 +5,9 @@ torch-CPU) and masks the points outside the range afterwards (data_processor.py 
 is collated and on the GPU already, so DeviceWorldAugmentor
 
   * parses DATA_AUGMENTOR the way DataAugmentor.__init__ does and keeps the four world transforms in list order (random_world_flip,
-    random_world_rotation, random_world_scaling, random_world_translation); every other entry (gt_sampling needs a database, the local
-    augmentations and dropouts need RoI data, ...) is skipped with one logged line;
+    random_world_rotation, random_world_scaling, random_world_translation); gt_sampling runs in front of them when a DeviceGtSampler is given
+    (pcp_amd/gt_sampler.py: it holds the database); every other entry (the local augmentations and dropouts need RoI data, ...) is
+    skipped with one logged line;
   * draw(): draws, frame by frame, exactly the numpy calls the reference makes for consecutive samples;
   * apply(): two launches on the current stream (points; gt_boxes + instances_tf) and the float64 se3_from_ego update on the host.
 
@@ -25,6 +26,7 @@ from .ops import _need_cuda, _p, _stream
 
 WORLD_TRANSFORMS = ('random_world_flip', 'random_world_rotation', 'random_world_scaling', 'random_world_translation')
 RANGE_FILTER = 'mask_points_and_boxes_outside_range'
+GT_SAMPLING = 'gt_sampling'
 BOX_WIDTHS = (8, 10)                 # [x y z dx dy dz heading class] / [.. heading vx vy class]
 TF_ROWS = (3, 4)                     # instances_tf (B, M, S, 3 | 4, 4)
 
@@ -84,9 +86,9 @@ class DeviceWorldAugmentor:
     """aug_cfg: the DATA_AUGMENTOR section (AUG_CONFIG_LIST, DISABLE_AUG_LIST) or the bare list; layout: the dataset layout
     (pcdet.datasets: 'nusc_map' rows carry the HD-map lane direction); data_processor: the DATA_PROCESSOR list -- the range filter runs
     when it names mask_points_and_boxes_outside_range (REMOVE_OUTSIDE_BOXES is not read: the models' own pcp_filter_gt_boxes covers
-    the boxes)."""
+    the boxes); gt_sampler: a DeviceGtSampler, without one a gt_sampling entry is skipped like the other entries the device path lacks."""
 
-    def __init__(self, aug_cfg, point_cloud_range, layout='car', data_processor=None, logger=None, seed=None):
+    def __init__(self, aug_cfg, point_cloud_range, layout='car', data_processor=None, logger=None, seed=None, gt_sampler=None):
         self.logger = logger or logging.getLogger(__name__)
         self.rng = np.random.RandomState(seed)          # the generator __call__ draws from (tools/train.py seeds it per rank)
         self.point_cloud_range = [float(v) for v in point_cloud_range]
@@ -99,9 +101,14 @@ class DeviceWorldAugmentor:
         disabled = [] if is_list else list(_get(aug_cfg, 'DISABLE_AUG_LIST', []) or [])
         self.queue = []                    # (name, config) in list order
         self.skipped = []
+        self.gt_sampler = None             # set when the list holds an enabled gt_sampling entry and a sampler was given
         for cur in cfg_list:
             name = _get(cur, 'NAME')
             if name in disabled:
+                continue
+            if name == GT_SAMPLING and gt_sampler is not None:
+                self.gt_sampler = gt_sampler
+                self.queue.append((name, cur))
                 continue
             if name not in WORLD_TRANSFORMS:
                 self.skipped.append(name)
@@ -110,6 +117,8 @@ class DeviceWorldAugmentor:
             self.queue.append((name, cur))
         self.stages = []                   # PCP_AUG_* in the order the kernels apply them
         for name, cur in self.queue:
+            if name == GT_SAMPLING:
+                continue
             if name == 'random_world_flip':
                 for axis in _get(cur, 'ALONG_AXIS_LIST'):
                     assert axis in ('x', 'y'), axis
@@ -121,23 +130,32 @@ class DeviceWorldAugmentor:
             raise ValueError('%d augmentation stages: the kernels take %d' % (len(self.stages), _lib.AUG_MAX_STAGES))
 
     @classmethod
-    def from_dataset_cfg(cls, dataset_cfg, layout='car', logger=None, seed=None):
+    def from_dataset_cfg(cls, dataset_cfg, layout='car', logger=None, seed=None, gt_sampler=None):
         return cls(dataset_cfg.DATA_AUGMENTOR, dataset_cfg.POINT_CLOUD_RANGE, layout, data_processor=_get(dataset_cfg, 'DATA_PROCESSOR', []),
-                   logger=logger, seed=seed)
+                   logger=logger, seed=seed, gt_sampler=gt_sampler)
 
     @staticmethod
     def rot_range(cur):
         r = _get(cur, 'WORLD_ROT_ANGLE')
         return [-r, r] if not isinstance(r, (list, tuple)) else list(r)
 
-    def draw(self, batch_size, rng):
+    def draw(self, batch_size, rng, gt_classes=None):
         """rng: numpy.random.RandomState.  Frame after frame, the calls the reference makes on numpy's global generator for consecutive
-        samples, in its order; with RandomState(s) the parameters equal the reference's after np.random.seed(s)."""
+        samples, in its order; with RandomState(s) the parameters equal the reference's after np.random.seed(s).  With a gt sampler,
+        gt_classes[b] are the class ids of frame b's original boxes and the sampler's draws for frame b come before its world draws."""
         B = int(batch_size)
+        if self.gt_sampler is not None and (gt_classes is None or len(gt_classes) != B):
+            raise ValueError('draw() with a gt sampler needs gt_classes, the class ids of the original boxes of each of the %d frames' % B)
         p = {'flip_x': np.zeros(B, dtype=bool), 'flip_y': np.zeros(B, dtype=bool), 'noise_rot': np.zeros(B, dtype=np.float64),
              'noise_scale': np.ones(B, dtype=np.float64), 'noise_translate': np.zeros((B, 3), dtype=np.float32)}
+        if self.gt_sampler is not None:
+            p['gt_sampled'] = []
         for b in range(B):
+            if self.gt_sampler is not None:
+                p['gt_sampled'].append(self.gt_sampler.draw(gt_classes[b], rng))
             for name, cur in self.queue:
+                if name == GT_SAMPLING:
+                    continue
                 if name == 'random_world_flip':
                     for axis in _get(cur, 'ALONG_AXIS_LIST'):
                         p['flip_%s' % axis][b] = rng.choice([False, True], replace=False, p=[0.5, 0.5])
@@ -240,6 +258,8 @@ class DeviceWorldAugmentor:
         stores flip_x / flip_y / noise_rot / noise_scale per frame as the reference's collated batch carries them"""
         B = int(batch_dict['batch_size'])
         assert len(params['flip_x']) == B, (len(params['flip_x']), B)
+        if self.gt_sampler is not None:                      # the paste first: pasted points and boxes go through the transforms and the mask
+            self.gt_sampler.apply(batch_dict, params['gt_sampled'])
         points = batch_dict['points']
         _need_cuda(points)
         table_dev = torch.from_numpy(self.table(params)).to(points.device)
@@ -268,4 +288,5 @@ class DeviceWorldAugmentor:
         return batch_dict
 
     def __call__(self, batch_dict, rng=None):
-        return self.apply(batch_dict, self.draw(batch_dict['batch_size'], self.rng if rng is None else rng))
+        classes = self.gt_sampler.frame_gt_classes(batch_dict['gt_boxes']) if self.gt_sampler is not None else None
+        return self.apply(batch_dict, self.draw(batch_dict['batch_size'], self.rng if rng is None else rng, classes))

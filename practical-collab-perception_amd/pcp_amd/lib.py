@@ -154,6 +154,7 @@ class AnchorLoss(ctypes.Structure):
 AUG_FLIP_X, AUG_FLIP_Y, AUG_ROTATE, AUG_SCALE, AUG_TRANSLATE = 1, 2, 3, 4, 5       # PCP_AUG_* (include/pcp_hip_train.h)
 AUG_MAX_STAGES, AUG_MAX_BATCH, AUG_TABLE_STRIDE = 8, 64, 12
 AUG_MIN_ROW_STRIDE, AUG_MAX_ROW_STRIDE, AUG_TILE_ROWS = 4, 15, 512
+GTS_MAX_GROUPS, GTS_MAX_CAND, GTS_MAX_BOXES, GTS_CAND_STRIDE, GTS_ACC_STRIDE = 16, 64, 512, 10, 4      # PCP_GTS_* (include/pcp_hip_train.h)
 
 
 class WorldAug(ctypes.Structure):
@@ -350,6 +351,9 @@ SYMBOLS.update({
     'pcp_world_augment_points_workspace_bytes': (c_sz, [c_i64]),
     'pcp_world_augment_points': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i64, c_i32, vp, vp, vp, c_sz, vp]),
     'pcp_world_augment_boxes': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp]),
+    'pcp_gt_sample_select': (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, vp, vp, c_i32, vp, c_i32, vp, c_i32, vp, vp]),
+    'pcp_gt_sample_paste_points': (c_i32, [vp, c_i64, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, vp, vp, vp, c_i32, c_i64, vp, vp, vp]),
+    'pcp_gt_sample_paste_boxes': (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, vp, vp, vp, vp, c_i32, vp]),
 })
 
 # include/pcp_hip_mp.h (mixed-precision training loop, config 5)
@@ -390,9 +394,9 @@ SYMBOLS.update({
 # PCP_OPT_* of include/pcp_hip.h.  The C library never reads the environment; the PCP_* variables of earlier rounds are mapped onto the option
 # table ONCE, here, when the library is loaded (set_option() changes an option later, e.g. from a test)
 OPTIONS = {'pfn_crowd': 0, 'pfn_crowd_blocks': 1, 'pfn_wps': 2, 'wino4c_nw': 3, 'mp_th16_min': 4, 'mp_diag': 5, 'vox_aggregate': 6,
-           'conv_s2_form': 7}
+           'conv_s2_form': 7, 'gts_paste_form': 8}
 _OPTION_ENV = {'PCP_PFN_CROWD': 'pfn_crowd', 'PCP_PFN_CROWD_BLOCKS': 'pfn_crowd_blocks', 'PCP_PFN_WPS': 'pfn_wps', 'PCP_WINO4C_NW': 'wino4c_nw',
-               'PCP_MP_TH16_MIN': 'mp_th16_min', 'PCP_MP_DIAG': 'mp_diag', 'PCP_VOX_AGGREGATE': 'vox_aggregate', 'PCP_CONV_S2_FORM': 'conv_s2_form'}
+               'PCP_MP_TH16_MIN': 'mp_th16_min', 'PCP_MP_DIAG': 'mp_diag', 'PCP_VOX_AGGREGATE': 'vox_aggregate', 'PCP_CONV_S2_FORM': 'conv_s2_form', 'PCP_GTS_PASTE_FORM': 'gts_paste_form'}
 
 _LIB = None
 

@@ -1,6 +1,13 @@
 """Times pcp_world_augment_points (csrc/augment.hip) against the same sequence written in eager torch ops on the GPU.
 
-    python bench_augment.py [--iters 30] [--warmup 5] [--out FILE]
+    python bench_augment.py [--iters 30] [--warmup 5] [--out FILE] [--gt-sampling]
+
+--gt-sampling times the ground-truth database paste instead (csrc/gt_sample.hip through pcp_amd/gt_sampler.py): the nuScenes cloud at
+B = 1 and B = 4, the reference's SAMPLE_GROUPS, a synthetic database of 300 objects.  Timed: DeviceGtSampler.apply() with the tile form of
+pcp_gt_sample_paste_points (512 output rows staged through LDS), the same with the row-per-thread form (library option gts_paste_form = 1),
+the two point-paste launches alone in both forms, the paste followed by the world stages, and the same paste written in torch ops
+(torch.cat per frame plus index arithmetic, given the accepted list); all outputs are compared for equality.  GB/s: rows read once plus
+rows written once.
 
 Shapes: the nuScenes cloud (260 000 rows and 4 x 260 000 rows of 1 + 12 columns, HD-map layout) and the DiscoNet cloud (4 x 360 000 rows
 of 1 + 6 columns).  All stages (flip x, flip y, rotation, scaling, translation) with the range filter on.  CUDA events around every call
@@ -81,13 +88,155 @@ def timed(fn, warmup, iters):
     return float(ms.mean() * 1e3), float(ms.min() * 1e3)
 
 
+NUSC_CLASSES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle', 'pedestrian', 'traffic_cone']
+GT_SAMPLING = {'NAME': 'gt_sampling', 'PREPARE': {'filter_by_min_points': ['%s:5' % c for c in NUSC_CLASSES]},
+               'SAMPLE_GROUPS': ['car:2', 'truck:3', 'construction_vehicle:7', 'bus:4', 'trailer:6', 'barrier:2', 'motorcycle:6', 'bicycle:6',
+                                 'pedestrian:2', 'traffic_cone:2'],
+               'NUM_POINT_FEATURES': 10, 'LIMIT_WHOLE_SCENE': True, 'POINT_FEAT_INDEX_OFFSET_FROM_RAW_FEAT': {'SWEEP_INDEX': 0, 'INSTANCE_INDEX': 1}}
+N_SWEEPS = 10
+
+
+def make_database(n_obj=300, seed=1):
+    from pcp_amd.gt_sampler import DeviceGtDatabase
+    r = np.random.RandomState(seed)
+    cells = r.permutation(21 * 21)[:n_obj]
+    boxes = np.zeros((n_obj, 9), np.float32)
+    boxes[:, 0], boxes[:, 1] = (cells % 21 - 10) * 4.8 + r.uniform(-0.5, 0.5, n_obj), (cells // 21 - 10) * 4.8 + r.uniform(-0.5, 0.5, n_obj)
+    boxes[:, 2] = r.uniform(-2.0, -0.5, n_obj)
+    boxes[:, 3:6] = np.stack([r.uniform(0.5, 4.5, n_obj), r.uniform(0.5, 2.2, n_obj), r.uniform(1.0, 2.5, n_obj)], 1)
+    boxes[:, 6] = r.uniform(-3.1, 3.1, n_obj)
+    boxes[:, 7:9] = r.uniform(-8, 8, (n_obj, 2))
+    counts = r.randint(20, 201, n_obj)
+    pts = r.uniform(-0.5, 0.5, (int(counts.sum()), 12)).astype(np.float32)
+    tf = np.tile(np.eye(4, dtype=np.float32), (n_obj, N_SWEEPS, 1, 1))
+    tf[:, :, :3, 3] = r.uniform(-5, 5, (n_obj, N_SWEEPS, 3))
+    names = [NUSC_CLASSES[i % 10] for i in range(n_obj)]
+    return DeviceGtDatabase(names, boxes, counts, r.uniform(-6, 6, (n_obj, 3)), tf, pts)
+
+
+def torch_paste(points, per_frame, B, sampler, acc, n_own, cand_box):
+    """the same paste in torch ops, given the accepted list acc[b] = (slots, database indices): own rows, then per accepted object its
+    stored rows + the box centre with the frame and instance columns set, one torch.cat"""
+    db = sampler.db
+    parts = []
+    for b in range(B):
+        parts.append(points[b * per_frame:(b + 1) * per_frame])
+        slots, idx = acc[b]
+        if idx.numel() == 0:
+            continue
+        cnt = db.counts_dev[idx].long()
+        obj = torch.repeat_interleave(torch.arange(idx.numel(), device=points.device), cnt)
+        start = torch.cumsum(cnt, 0) - cnt
+        rows = db.offsets_dev[idx].long()[obj] + (torch.arange(obj.numel(), device=points.device) - start[obj])
+        new = torch.empty((obj.numel(), points.shape[1]), dtype=torch.float32, device=points.device)
+        new[:, 0] = float(b)
+        new[:, 1:] = db.points_dev[rows]
+        new[:, 1:4] += cand_box[slots][obj, :3]
+        new[:, sampler.inst_col] = (n_own[b] + obj).float()
+        parts.append(new)
+    return torch.cat(parts, 0)
+
+
+def gt_sampling_bench(args):
+    import ctypes
+    from pcp_amd import lib
+    from pcp_amd.gt_sampler import DeviceGtSampler
+    from pcp_amd.ops import _p, _stream
+    rr = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+    db = make_database()
+    lines = ['gt_sampling paste (pcp_gt_sample_select / _paste_points / _paste_boxes), %s, mean (min) of %d calls after %d warm-up calls; database: %d '
+             'objects, %d rows of 12 floats' % (torch.cuda.get_device_name(0), args.iters, args.warmup, len(db), int(db.counts.sum()))]
+    for B in (1, 4):
+        per_frame, S, M = 260000, 13, 30
+        sampler = DeviceGtSampler(GT_SAMPLING, NUSC_CLASSES, db)
+        aug = DeviceWorldAugmentor([GT_SAMPLING] + AUG, rr, layout='nusc_map', data_processor=MASK, gt_sampler=sampler)
+        r = np.random.RandomState(3)
+        gt = np.zeros((B, M + 2, 10), np.float32)
+        gt[:, :M, 0:2], gt[:, :M, 2] = r.uniform(-50, 50, (B, M, 2)), r.uniform(-2, -0.5, (B, M))
+        gt[:, :M, 3:6], gt[:, :M, 6] = r.uniform(0.5, 4.5, (B, M, 3)), r.uniform(-3.1, 3.1, (B, M))
+        gt[:, :M, 9] = r.randint(1, 11, (B, M))
+        tf = np.tile(np.eye(4, dtype=np.float32)[:3], (B, M + 2, N_SWEEPS, 1, 1))
+        glob = np.eye(4)
+        glob[:2, :2] = [[np.cos(0.7), -np.sin(0.7)], [np.sin(0.7), np.cos(0.7)]]
+        pts = make_cloud(B, per_frame, S, True, rr).cuda()
+        batch = {'points': pts, 'gt_boxes': torch.from_numpy(gt).cuda(), 'instances_tf': torch.from_numpy(tf).cuda(), 'batch_size': B,
+                 'metadata': [{'tf_target_from_glob': glob} for _ in range(B)]}
+        classes = sampler.frame_gt_classes(batch['gt_boxes'])
+        params = aug.draw(B, np.random.RandomState(7), classes)
+        drawn = params['gt_sampled']
+        out = sampler.apply(dict(batch), drawn)
+        lib.set_option('gts_paste_form', 1)
+        out_rows = sampler.apply(dict(batch), drawn)
+        lib.set_option('gts_paste_form', None)
+        n_acc = [int(t.numel()) for t in out['gt_sampled_db_index']]
+        added = int(out['gt_sampled_rows'].sum())
+        ft, cand_db, cand_box, max_added = sampler.candidate_table(drawn, 10, batch['metadata'])
+        cand_box_d = torch.from_numpy(cand_box).cuda()
+        # the accepted slots for the torch form: database index -> slot inside the frame's candidate range (an index may repeat across frames only)
+        acc = []
+        for b in range(B):
+            idx = out['gt_sampled_db_index'][b].long()
+            lo, hi = int(ft[b, 1]), int(ft[b, -1])
+            slot_of = {int(d): lo + k for k, d in enumerate(cand_db[lo:hi])}
+            acc.append((torch.tensor([slot_of[int(d)] for d in idx.cpu()], dtype=torch.long, device='cuda'), idx))
+        n_own = ft[:, 0].tolist()
+        want = torch_paste(pts, per_frame, B, sampler, acc, n_own, cand_box_d)
+        torch.cuda.synchronize()
+        eq_rows, eq_torch = torch.equal(out['points'], out_rows['points']), torch.equal(out['points'], want)
+        both = aug.apply(dict(batch), params)
+        # the two point-paste launches alone, on the buffers of one prepared call
+        G, T = len(sampler.groups), int(cand_db.size)
+        dev = pts.device
+        ft_d, db_d = torch.from_numpy(ft).to(dev), torch.from_numpy(cand_db).to(dev)
+        cap = max(int((ft[:, 1 + G] - ft[:, 1]).max()), 1)
+        acc_d = torch.empty((B, cap, lib.GTS_ACC_STRIDE), dtype=torch.int32, device=dev)
+        counts = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+        seg = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        buf = torch.empty((pts.shape[0] + max_added, S), dtype=torch.float32, device=dev)
+        L = lib.load()
+        lib.check(L.pcp_gt_sample_select(_p(batch['gt_boxes']), B, M + 2, 10, _p(ft_d), G, _p(db_d), _p(cand_box_d), T, _p(db.counts_dev), len(db), _p(acc_d),
+                                         cap, _p(counts), _stream()), 'pcp_gt_sample_select')
+
+        def launches():
+            lib.check(L.pcp_gt_sample_paste_points(_p(pts), pts.shape[0], S, B, _p(ft_d), G, _p(acc_d), cap, _p(counts), _p(cand_box_d), _p(db.points_dev),
+                                                   _p(db.offsets_dev), sampler.inst_col, max_added, _p(buf), _p(seg), _stream()), 'pcp_gt_sample_paste_points')
+
+        k_us, k_min = timed(launches, args.warmup, args.iters)
+        lib.set_option('gts_paste_form', 1)
+        r_us, r_min = timed(launches, args.warmup, args.iters)
+        a1_us, a1_min = timed(lambda: sampler.apply(dict(batch), drawn), args.warmup, args.iters)
+        lib.set_option('gts_paste_form', None)
+        a0_us, a0_min = timed(lambda: sampler.apply(dict(batch), drawn), args.warmup, args.iters)
+        w_us, w_min = timed(lambda: aug.apply(dict(batch), params), args.warmup, args.iters)
+        t_us, t_min = timed(lambda: torch_paste(pts, per_frame, B, sampler, acc, n_own, cand_box_d), args.warmup, args.iters)
+        n = B * per_frame
+        useful = (n * S + added * 12 + (n + added) * S) * 4
+        lines.append('nuScenes B=%d %8d rows x %2d floats, %d candidates, accepted %s, %d rows pasted, outputs equal: tile vs row-per-thread %s, tile vs torch ops %s'
+                     % (B, n, S, T, n_acc, added, eq_rows, eq_torch))
+        lines.append('  point paste launches alone: LDS tiles %8.1f us (%7.1f) %7.1f GB/s | row per thread %8.1f us (%7.1f) %7.1f GB/s'
+                     % (k_us, k_min, useful / k_us / 1e3, r_us, r_min, useful / r_us / 1e3))
+        lines.append('  apply() (table, select, paste, one read, boxes): LDS tiles %8.1f us (%7.1f) | row per thread %8.1f us (%7.1f) | torch ops (points only, '
+                     'accepted list given) %8.1f us (%7.1f) %6.1f GB/s' % (a0_us, a0_min, a1_us, a1_min, t_us, t_min, useful / t_us / 1e3))
+        lines.append('  paste + world stages + range mask: %8.1f us (%7.1f), kept %d of %d rows' % (w_us, w_min, int(both['points'].shape[0]), n + added))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', type=str, default=None)
+    ap.add_argument('--gt-sampling', action='store_true', help='time the ground-truth database paste instead of the world stages')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_augment.py needs the GPU'
+    if args.gt_sampling:
+        text = '\n'.join(gt_sampling_bench(args))
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write(text + '\n')
+        return
     lines = ['pcp_world_augment_points vs the eager torch-op chain, %s, mean (min) of %d calls after %d warm-up calls'
              % (torch.cuda.get_device_name(0), args.iters, args.warmup)]
     for name, B, per_frame, S, hd_map, rr in SHAPES:

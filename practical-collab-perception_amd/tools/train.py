@@ -49,7 +49,7 @@ def parse_config():
     p.add_argument('--max_ckpt_save_num', type=int, default=30)
     p.add_argument('--output_dir', type=str, default=None)
     p.add_argument('--sync_bn', action='store_true', default=False, help='whether to use sync bn')
-    p.add_argument('--fix_random_seed', action='store_true', default=False, help='seed the device augmentation with 666 + rank')
+    p.add_argument('--fix_random_seed', action='store_true', default=False, help='seed the device augmentation with 666 + rank (with DEVICE_GT_SAMPLING: python, numpy and torch too)')
     p.add_argument('--set', dest='set_cfgs', default=None, nargs=argparse.REMAINDER)
     args = p.parse_args()
     cfg_from_yaml_file(args.cfg_file, cfg)
@@ -59,9 +59,47 @@ def parse_config():
         cfg.DATA_CONFIG.SYNTHETIC = {}
     if 'DEVICE_AUG' not in cfg.DATA_CONFIG.SYNTHETIC:
         cfg.DATA_CONFIG.SYNTHETIC.DEVICE_AUG = False        # present before --set, which only takes keys that exist
+    if 'DEVICE_GT_SAMPLING' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.DEVICE_GT_SAMPLING = False
+    if 'GT_DATABASE_FRAMES' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.GT_DATABASE_FRAMES = 8
+    if 'GT_DROP_UNSTOCKED_GROUPS' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.GT_DROP_UNSTOCKED_GROUPS = False
+    if 'GT_BOXES' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.GT_BOXES = 40                # boxes of a synthetic training frame (pcdet/datasets)
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
     return args, cfg
+
+
+def build_gt_sampler(cfg, train_set, logger):
+    """DATA_CONFIG.SYNTHETIC.DEVICE_GT_SAMPLING (only with DEVICE_AUG): a ground-truth database cut out of the first GT_DATABASE_FRAMES
+    training items and a DeviceGtSampler from the config's gt_sampling entry (pcp_amd/gt_sampler.py).  A sample group whose class has no
+    object left after PREPARE is refused by the sampler, as the issue of an empty database is in the reference.  A few synthetic frames
+    do not stock every class, so SYNTHETIC.GT_DROP_UNSTOCKED_GROUPS (default False) leaves such groups out instead, with a logged line.
+    NUM_POINT_FEATURES is the database's own column count - 2 (the reference's HD-map model configs override the dataset's 5 with 10 the
+    same way); a differing config value is logged."""
+    if not cfg.DATA_CONFIG.SYNTHETIC.get('DEVICE_GT_SAMPLING', False):
+        return None
+    aug_cfg = cfg.DATA_CONFIG.DATA_AUGMENTOR
+    entry = next((c for c in aug_cfg.AUG_CONFIG_LIST if c.NAME == 'gt_sampling'), None)
+    if entry is None or 'gt_sampling' in aug_cfg.get('DISABLE_AUG_LIST', []):
+        logger.info('device gt_sampling: the config lists no enabled gt_sampling entry')
+        return None
+    from pcp_amd.gt_sampler import DeviceGtDatabase, DeviceGtSampler
+    frames = min(int(cfg.DATA_CONFIG.SYNTHETIC.get('GT_DATABASE_FRAMES', 8)), len(train_set))
+    db, _infos = DeviceGtDatabase.build_from_dataset(train_set, frames, min_points=1)
+    need = dict((x.split(':')[0], int(x.split(':')[1])) for x in entry.get('PREPARE', {}).get('filter_by_min_points', []))
+    stocked = {n for n, c in zip(db.names, db.counts) if c >= need.get(n, 0)}
+    entry = dict(entry)
+    if int(entry.get('NUM_POINT_FEATURES', db.columns - 2)) != db.columns - 2:
+        logger.info('device gt_sampling: NUM_POINT_FEATURES %s of the config -> %d, the columns of this dataset' % (entry.get('NUM_POINT_FEATURES'), db.columns - 2))
+    entry['NUM_POINT_FEATURES'] = db.columns - 2
+    dropped = [g for g in entry['SAMPLE_GROUPS'] if g.split(':')[0] in cfg.CLASS_NAMES and g.split(':')[0] not in stocked]
+    if dropped and cfg.DATA_CONFIG.SYNTHETIC.get('GT_DROP_UNSTOCKED_GROUPS', False):
+        entry['SAMPLE_GROUPS'] = [g for g in entry['SAMPLE_GROUPS'] if g not in dropped]
+        logger.info('device gt_sampling: no object of %s in the %d-frame database, groups left out' % ([g.split(':')[0] for g in dropped], frames))
+    return DeviceGtSampler(entry, cfg.CLASS_NAMES, db, logger=logger)
 
 
 def build_augmentor(args, cfg, train_set, logger):
@@ -72,7 +110,10 @@ def build_augmentor(args, cfg, train_set, logger):
         return None
     from pcp_amd.augment import DeviceWorldAugmentor
     aug = DeviceWorldAugmentor.from_dataset_cfg(cfg.DATA_CONFIG, layout=getattr(train_set, 'layout', 'car'), logger=logger,
-                                                seed=666 + cfg.LOCAL_RANK if args.fix_random_seed else None)
+                                                seed=666 + cfg.LOCAL_RANK if args.fix_random_seed else None,
+                                                gt_sampler=build_gt_sampler(cfg, train_set, logger))
+    if aug.gt_sampler is not None:
+        logger.info('device gt_sampling: database sizes %s' % aug.gt_sampler.class_sizes())
     logger.info('device world augmentation: stages %s, range filter %s' % ([n for n, _ in aug.queue], 'on' if aug.filter else 'off'))
     return aug
 
@@ -150,6 +191,10 @@ def choose_resume_checkpoint(model, ckpt_dir, logger, optimizer=None):
 def main():
     args, cfg = parse_config()
     dist_train, total_gpus = init_distributed(args, cfg)
+    if args.fix_random_seed and cfg.DATA_CONFIG.SYNTHETIC.get('DEVICE_GT_SAMPLING', False):
+        # reference tools/train.py:80-81.  Only with the new switch: a gt_sampling run repeats bit for bit (initial weights, the loader's
+        # shuffle, hence which frames meet which candidates); every other run keeps what the flag did before, the augmentor's seed alone
+        common_utils.set_random_seed(666 + cfg.LOCAL_RANK)
     if args.batch_size is None:
         args.batch_size = cfg.OPTIMIZATION.BATCH_SIZE_PER_GPU
     else:
