@@ -488,6 +488,8 @@ typedef struct pcp_world_aug {
   int32_t hd_map;   /* rows are [b, x y z i t, 4 map masks, lane_dir, sweep, instance] (row_stride 13): lane_dir follows the flips / rotation */
   int32_t filter;   /* keep only rows with range[0..2] <= xyz < range[3..5] after the transform, compacted in input order */
   float range[6];
+  int32_t raw_heading; /* pcp_world_augment_boxes: 1 = leave the heading as the stages made it (object stages follow and the reference applies
+                          limit_period once, behind its whole list); 0 = end with limit_period */
 } pcp_world_aug_t;
 
 /* points (n, row_stride) float32, column 0 the frame index, 16-byte aligned like `out`.  xyz always; hd_map: column 10 (lane_dir);
@@ -502,7 +504,7 @@ int pcp_world_augment_points(const pcp_world_aug_t *aug, const float *table, con
                              int32_t *frame_count, void *workspace, size_t workspace_bytes, void *stream);
 
 /* gt_boxes (batch, max_boxes, box_width) in place, box_width 8 [x y z dx dy dz heading class] or 10 [.. heading vx vy class]; rows of class 0
- * (padding) keep their bits; the heading ends with limit_period(h, 0.5, 2 pi).  instances_tf (nullable; batch, max_boxes, n_sweeps, tf_rows,
+ * (padding) keep their bits; the heading ends with limit_period(h, 0.5, 2 pi) unless aug->raw_heading.  instances_tf (nullable; batch, max_boxes, n_sweeps, tf_rows,
  * 4) with tf_rows 3 or 4: every matrix of a box of class != 0 becomes T A T^-1 for each stage in order, evaluated as an affine map in
  * float32 (a fourth row keeps its bits).  `range` / `filter` / `hd_map` of aug are not read.  One launch. */
 int pcp_world_augment_boxes(const pcp_world_aug_t *aug, const float *table, float *gt_boxes, int32_t max_boxes, int32_t box_width,
@@ -551,6 +553,81 @@ int pcp_gt_sample_paste_boxes(const float *gt_boxes, int32_t batch, int32_t max_
                               int32_t n_sweeps, int32_t tf_rows, const int32_t *frame_table, int32_t n_groups, const int32_t *accepted,
                               int32_t acc_cap, const int32_t *counts, const float *cand_box, const float *db_tf, float *gt_out, float *tf_out,
                               int32_t max_boxes_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-object augmentation of a collated training batch (the reference's random_local_translation / _rotation / _scaling,
+ * random_local_frustum_dropout and random_world_frustum_dropout, augmentor_utils.py; csrc/object_augment.hip).  The reference walks the
+ * boxes of a sample in order; box i masks the points inside it as it is BEFORE its own change (get_points_in_box), changes them, then
+ * changes itself, and later boxes see the moved points.  A box never depends on another box, so pcp_object_augment_boxes runs every box
+ * through the sub-stages and records its state in front of each; a point walks sub-stages x boxes against those states.
+ *
+ * params (device, batch x n_stages x max_boxes x PCP_OBJ_PARAM_STRIDE float32, written by the host), per sub-stage and box:
+ *   [0] the drawn value as float32 (offset / scale / angle / intensity)  [1] cos  [2] sin of the angle (ROTATE only, host float32)  [3] unused
+ * box_states (device, batch x n_stages x max_boxes x PCP_OBJ_STATE_STRIDE float32, written by pcp_object_augment_boxes):
+ *   [0..2] centre  [3] dx/2 + 0.1  [4] dy/2 + 0.1  [5] dz/2 (-1 on padding rows: nothing is inside)  [6] cos(-heading)  [7] sin(-heading)
+ *   [8] offset | scale | cos | dropout threshold  [9] sin  [10..11] unused
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_OBJ_TRANSLATE_X 1
+#define PCP_OBJ_TRANSLATE_Y 2
+#define PCP_OBJ_TRANSLATE_Z 3
+#define PCP_OBJ_SCALE 4
+#define PCP_OBJ_ROTATE 5
+#define PCP_OBJ_DROP_TOP 6          /* local frustum dropouts: inside box i and z >= (z + dz/2) - intensity dz, ... */
+#define PCP_OBJ_DROP_BOTTOM 7
+#define PCP_OBJ_DROP_LEFT 8
+#define PCP_OBJ_DROP_RIGHT 9
+#define PCP_OBJ_WORLD_DROP_TOP 10   /* world frustum dropouts: a row filter against frame_thr; only as the single stage of a points call */
+#define PCP_OBJ_WORLD_DROP_BOTTOM 11
+#define PCP_OBJ_WORLD_DROP_LEFT 12
+#define PCP_OBJ_WORLD_DROP_RIGHT 13
+#define PCP_OBJ_MAX_STAGES 16       /* sub-stages of one call (a translation over x y z is three) */
+#define PCP_OBJ_MAX_BOXES 512       /* box rows per frame (max_boxes) */
+#define PCP_OBJ_LDS_BOXES 64        /* box states staged in LDS at a time, next to the two row tiles */
+#define PCP_OBJ_STATE_STRIDE 12
+#define PCP_OBJ_PARAM_STRIDE 4
+typedef struct pcp_object_aug {
+  int32_t n_stages;
+  int32_t stage[PCP_OBJ_MAX_STAGES]; /* PCP_OBJ_* in the order they are applied */
+  int32_t batch;
+  int32_t limit_heading; /* pcp_object_augment_boxes ends with limit_period(h, 0.5, 2 pi): set when no world stage follows */
+} pcp_object_aug_t;
+
+/* gt_boxes (batch, max_boxes <= PCP_OBJ_MAX_BOXES, box_width 8 | 10) in place: translation adds to its coordinate only (the velocity
+ * stays), scaling multiplies dx dy dz, rotation adds to the heading (the centre goes through the reference's subtract, rotate, add-back of
+ * its own value and keeps its bits; box_width 10 is refused with PCP_ERR_UNSUPPORTED as the reference's velocity branch raises),
+ * dropouts leave the box.  Rows of class 0 keep their bits.  n_boxes[b] (device, batch int32) = 1 + the last row of class != 0.
+ * Stages PCP_OBJ_TRANSLATE_X .. PCP_OBJ_DROP_RIGHT only.  One launch. */
+int pcp_object_augment_boxes(const pcp_object_aug_t *aug, const float *params, float *gt_boxes, int32_t max_boxes, int32_t box_width,
+                             float *box_states, int32_t *n_boxes, void *stream);
+
+/* points (n, row_stride) float32 like pcp_world_augment_points (column 0 the frame index, 16-byte aligned like `out`); the frames a tile
+ * holds are read from its rows, a tile that straddles frames walks each of them.  Only xyz change; every other column keeps its bits.
+ * Rows of a frame outside [0, batch) pass untouched.  Without a dropout stage: one launch, out[i] = points[i] moved (out may be points).
+ * With one: the surviving rows in input order at the front of `out` (n rows of capacity, not points itself), frame_count (device,
+ * batch + 1 int32): [b] = rows kept of frame b, [batch] = rows of a frame outside [0, batch), all kept, so the sum is the rows written;
+ * two launches (count per tile, place), no atomics on the placement path: a call repeats bit for bit.
+ * A single PCP_OBJ_WORLD_DROP_* stage reads frame_thr (device, batch float32) instead of box states: TOP keeps z < thr, BOTTOM z > thr,
+ * LEFT y < thr, RIGHT y > thr. */
+size_t pcp_object_augment_points_workspace_bytes(int64_t n);
+int pcp_object_augment_points(const pcp_object_aug_t *aug, const float *box_states, const int32_t *n_boxes, int32_t max_boxes,
+                              const float *frame_thr, const float *points, int64_t n, int32_t row_stride, float *out, int32_t *frame_count,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* extent[2 b], extent[2 b + 1] (device float32) = min, max of column `col` (2 = y, 3 = z) over the rows of frame b; +inf, -inf for a frame
+ * without rows.  Two launches (per tile, per frame), no float atomics: deterministic. */
+size_t pcp_frame_extent_workspace_bytes(int64_t n, int32_t batch);
+int pcp_frame_extent(const float *points, int64_t n, int32_t row_stride, int32_t batch, int32_t col, float *extent, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* The box half of a world frustum dropout and its threshold.  direction PCP_OBJ_WORLD_DROP_*; intensity (device, batch float32).
+ * frame_thr[b] = max - intensity (max - min) (TOP, LEFT) or min + intensity (max - min) (BOTTOM, RIGHT) in float32; a frame without
+ * extent gets the threshold every row and box passes (+-inf) and its boxes are copied as they are.  gt_out / tf_out (not the inputs):
+ * the boxes of class != 0 whose z (TOP, BOTTOM) or y (LEFT, RIGHT) passes the strict test, in order, their instances_tf rows (nullable;
+ * batch, max_boxes, n_sweeps, tf_rows 3 | 4, 4) with them, then zero boxes and the collation's identity padding.  n_boxes_out[b] = survivors.
+ * One launch. */
+int pcp_object_augment_drop_boxes(const float *gt_boxes, int32_t batch, int32_t max_boxes, int32_t box_width, const float *instances_tf,
+                                  int32_t n_sweeps, int32_t tf_rows, const float *extent, const float *intensity, int32_t direction,
+                                  float *frame_thr, float *gt_out, float *tf_out, int32_t *n_boxes_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void k_aug_boxes(pcp_world_aug_t a, const floa
       }
     }
     // limit_period(h, 0.5, 2 pi) = h - floor(h / period + 0.5) * period, every operation rounded to float32 as torch-CPU does
-    h = __fsub_rn(h, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(h, AUG_2PI), 0.5f)), AUG_2PI));
+    if (!a.raw_heading) h = __fsub_rn(h, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(h, AUG_2PI), 0.5f)), AUG_2PI));
     box[0] = x;
     box[1] = y;
     box[2] = z;

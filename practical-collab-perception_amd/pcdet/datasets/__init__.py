@@ -145,6 +145,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
             for i, b in enumerate(batch_list):
                 gt[i, :b['gt_boxes'].shape[0]] = b['gt_boxes']
             ret['gt_boxes'] = gt
+            ret['num_gt_boxes'] = [int(b['gt_boxes'].shape[0]) for b in batch_list]   # the host's numbers: the device augmentor draws per box
             if 'instances_tf' in batch_list[0]:
                 tf = np.zeros((len(batch_list), m) + batch_list[0]['instances_tf'].shape[1:], dtype=np.float32)
                 tf[..., :3, :3] = np.eye(3, dtype=np.float32)

@@ -7,7 +7,8 @@ is collated and on the GPU already, so DeviceWorldAugmentor
   * parses DATA_AUGMENTOR the way DataAugmentor.__init__ does and keeps the four world transforms in list order (random_world_flip,
     random_world_rotation, random_world_scaling, random_world_translation); gt_sampling runs in front of them when a DeviceGtSampler is given
     (pcp_amd/gt_sampler.py: it holds the database); every other entry (the local augmentations and dropouts need RoI data, ...) is
-    skipped with one logged line;
+    skipped with one logged line; object_stages=True also takes the per-object entries (random_local_translation / _rotation / _scaling,
+    random_local_frustum_dropout, random_world_frustum_dropout: pcp_amd/object_augment.py) in list order;
   * draw(): draws, frame by frame, exactly the numpy calls the reference makes for consecutive samples;
   * apply(): two launches on the current stream (points; gt_boxes + instances_tf) and the float64 se3_from_ego update on the host.
 
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from . import object_augment as _obj
 from .lib import check
 from .ops import _need_cuda, _p, _stream
 
@@ -86,9 +88,11 @@ class DeviceWorldAugmentor:
     """aug_cfg: the DATA_AUGMENTOR section (AUG_CONFIG_LIST, DISABLE_AUG_LIST) or the bare list; layout: the dataset layout
     (pcdet.datasets: 'nusc_map' rows carry the HD-map lane direction); data_processor: the DATA_PROCESSOR list -- the range filter runs
     when it names mask_points_and_boxes_outside_range (REMOVE_OUTSIDE_BOXES is not read: the models' own pcp_filter_gt_boxes covers
-    the boxes); gt_sampler: a DeviceGtSampler, without one a gt_sampling entry is skipped like the other entries the device path lacks."""
+    the boxes); gt_sampler: a DeviceGtSampler, without one a gt_sampling entry is skipped like the other entries the device path lacks;
+    object_stages: the per-object entries (object_augment.OBJECT_STAGES) join the queue instead of being skipped."""
 
-    def __init__(self, aug_cfg, point_cloud_range, layout='car', data_processor=None, logger=None, seed=None, gt_sampler=None):
+    def __init__(self, aug_cfg, point_cloud_range, layout='car', data_processor=None, logger=None, seed=None, gt_sampler=None,
+                 object_stages=False):
         self.logger = logger or logging.getLogger(__name__)
         self.rng = np.random.RandomState(seed)          # the generator __call__ draws from (tools/train.py seeds it per rank)
         self.point_cloud_range = [float(v) for v in point_cloud_range]
@@ -110,6 +114,9 @@ class DeviceWorldAugmentor:
                 self.gt_sampler = gt_sampler
                 self.queue.append((name, cur))
                 continue
+            if object_stages and name in _obj.OBJECT_STAGES:
+                self.queue.append((name, cur))
+                continue
             if name not in WORLD_TRANSFORMS:
                 self.skipped.append(name)
                 self.logger.info('DeviceWorldAugmentor: %s is not a world transform of the device path, skipped' % name)
@@ -117,60 +124,129 @@ class DeviceWorldAugmentor:
             self.queue.append((name, cur))
         self.stages = []                   # PCP_AUG_* in the order the kernels apply them
         for name, cur in self.queue:
-            if name == GT_SAMPLING:
+            if name == GT_SAMPLING or name in _obj.OBJECT_STAGES:
                 continue
-            if name == 'random_world_flip':
-                for axis in _get(cur, 'ALONG_AXIS_LIST'):
-                    assert axis in ('x', 'y'), axis
-                    self.stages.append(_lib.AUG_FLIP_X if axis == 'x' else _lib.AUG_FLIP_Y)
-            else:
-                self.stages.append({'random_world_rotation': _lib.AUG_ROTATE, 'random_world_scaling': _lib.AUG_SCALE,
-                                    'random_world_translation': _lib.AUG_TRANSLATE}[name])
+            self.stages.extend(self.world_stage_codes(name, cur))
         if len(self.stages) > _lib.AUG_MAX_STAGES:
             raise ValueError('%d augmentation stages: the kernels take %d' % (len(self.stages), _lib.AUG_MAX_STAGES))
+        self.has_object_stages = any(name in _obj.OBJECT_STAGES for name, _ in self.queue)
+        self._plan()
+
+    @staticmethod
+    def world_stage_codes(name, cur):
+        if name == 'random_world_flip':
+            out = []
+            for axis in _get(cur, 'ALONG_AXIS_LIST'):
+                assert axis in ('x', 'y'), axis
+                out.append(_lib.AUG_FLIP_X if axis == 'x' else _lib.AUG_FLIP_Y)
+            return out
+        return [{'random_world_rotation': _lib.AUG_ROTATE, 'random_world_scaling': _lib.AUG_SCALE,
+                 'random_world_translation': _lib.AUG_TRANSLATE}[name]]
+
+    def _plan(self):
+        """with object stages: the launches in list order.  self.steps: dicts(kind 'gt' | 'world' | 'local' | 'wdrop', q: queue indices,
+        stages).  Consecutive world entries share one call of the world kernels, consecutive local entries one of the object kernels.
+        self.splits: queue indices in front of which the per-frame box counts must be read back before the draws go on, i.e. the first
+        object entry behind an enabled gt_sampling or a world frustum dropout."""
+        self.steps, self.splits = [], []
+        if not self.has_object_stages:
+            return
+        changed = False                                 # a device stage has changed the box counts since the last read
+        for qi, (name, cur) in enumerate(self.queue):
+            if name == GT_SAMPLING:
+                if any(n in _obj.OBJECT_STAGES for n, _ in self.queue[:qi]):
+                    # apply() pastes in front of every other stage, and the draws of an earlier object stage cover the original boxes only
+                    raise ValueError('gt_sampling behind %s: the device path pastes first, so gt_sampling must stand in front of every '
+                                     'per-object stage of the list' % [n for n, _ in self.queue[:qi] if n in _obj.OBJECT_STAGES][0])
+                self.steps.append({'kind': 'gt', 'q': [qi], 'stages': []})
+                changed = True
+                continue
+            if name in _obj.LOCAL_STAGES:
+                if changed:
+                    self.splits.append(qi)
+                    changed = False
+                subs = [c for c, _, _ in _obj.sub_stages(name, cur)]
+                last = self.steps[-1] if self.steps else None
+                if last is not None and last['kind'] == 'local' and qi not in self.splits and len(last['stages']) + len(subs) <= _lib.OBJ_MAX_STAGES:
+                    last['q'].append(qi)
+                    last['stages'].extend(subs)
+                else:
+                    self.steps.append({'kind': 'local', 'q': [qi], 'stages': subs})
+            elif name == _obj.WORLD_DROPOUT:
+                self.steps.append({'kind': 'wdrop', 'q': [qi], 'stages': [c for c, _, _ in _obj.sub_stages(name, cur)]})
+                changed = True
+            else:
+                codes = self.world_stage_codes(name, cur)
+                last = self.steps[-1] if self.steps else None
+                if last is not None and last['kind'] == 'world':
+                    last['q'].append(qi)
+                    last['stages'].extend(codes)
+                else:
+                    self.steps.append({'kind': 'world', 'q': [qi], 'stages': codes})
+        # the heading's limit_period and the range mask come once, behind the whole list
+        if self.steps[-1]['kind'] != 'world' and (self.filter or self.steps[-1]['kind'] != 'local'):
+            self.steps.append({'kind': 'world', 'q': [], 'stages': []})
 
     @classmethod
-    def from_dataset_cfg(cls, dataset_cfg, layout='car', logger=None, seed=None, gt_sampler=None):
+    def from_dataset_cfg(cls, dataset_cfg, layout='car', logger=None, seed=None, gt_sampler=None, object_stages=False):
         return cls(dataset_cfg.DATA_AUGMENTOR, dataset_cfg.POINT_CLOUD_RANGE, layout, data_processor=_get(dataset_cfg, 'DATA_PROCESSOR', []),
-                   logger=logger, seed=seed, gt_sampler=gt_sampler)
+                   logger=logger, seed=seed, gt_sampler=gt_sampler, object_stages=object_stages)
 
     @staticmethod
     def rot_range(cur):
         r = _get(cur, 'WORLD_ROT_ANGLE')
         return [-r, r] if not isinstance(r, (list, tuple)) else list(r)
 
-    def draw(self, batch_size, rng, gt_classes=None):
+    def draw(self, batch_size, rng, gt_classes=None, n_boxes=None, entries=None, params=None):
         """rng: numpy.random.RandomState.  Frame after frame, the calls the reference makes on numpy's global generator for consecutive
         samples, in its order; with RandomState(s) the parameters equal the reference's after np.random.seed(s).  With a gt sampler,
-        gt_classes[b] are the class ids of frame b's original boxes and the sampler's draws for frame b come before its world draws."""
+        gt_classes[b] are the class ids of frame b's original boxes and the sampler's draws for frame b come before its world draws.
+        With object stages n_boxes[b] is the number of real boxes of frame b (one uniform per box and sub-stage); their values land in
+        p['object'][queue index][b].  entries = (lo, hi) draws only the queue entries lo .. hi - 1 into `params` (__call__ uses it when the
+        box counts have to be read back in the middle of the list)."""
         B = int(batch_size)
+        if self.has_object_stages and (n_boxes is None or len(n_boxes) != B):
+            raise ValueError('draw() with object stages needs n_boxes, the number of real boxes of each of the %d frames' % B)
+        lo_q, hi_q = entries if entries is not None else (0, len(self.queue))
+        if params is not None:
+            p = params
+            for b in range(B):
+                self._draw_frame(b, rng, p, gt_classes, n_boxes, lo_q, hi_q)
+            return p
         if self.gt_sampler is not None and (gt_classes is None or len(gt_classes) != B):
             raise ValueError('draw() with a gt sampler needs gt_classes, the class ids of the original boxes of each of the %d frames' % B)
         p = {'flip_x': np.zeros(B, dtype=bool), 'flip_y': np.zeros(B, dtype=bool), 'noise_rot': np.zeros(B, dtype=np.float64),
              'noise_scale': np.ones(B, dtype=np.float64), 'noise_translate': np.zeros((B, 3), dtype=np.float32)}
         if self.gt_sampler is not None:
             p['gt_sampled'] = []
+        if self.has_object_stages:
+            p['object'] = {qi: [None] * B for qi, (name, _) in enumerate(self.queue) if name in _obj.OBJECT_STAGES}
         for b in range(B):
-            if self.gt_sampler is not None:
-                p['gt_sampled'].append(self.gt_sampler.draw(gt_classes[b], rng))
-            for name, cur in self.queue:
-                if name == GT_SAMPLING:
-                    continue
-                if name == 'random_world_flip':
-                    for axis in _get(cur, 'ALONG_AXIS_LIST'):
-                        p['flip_%s' % axis][b] = rng.choice([False, True], replace=False, p=[0.5, 0.5])
-                elif name == 'random_world_rotation':
-                    lo, hi = self.rot_range(cur)
-                    p['noise_rot'][b] = rng.uniform(lo, hi)
-                elif name == 'random_world_scaling':
-                    lo, hi = _get(cur, 'WORLD_SCALE_RANGE')
-                    p['noise_scale'][b] = rng.uniform(lo, hi)
-                else:
-                    std = _get(cur, 'NOISE_TRANSLATE_STD')
-                    assert len(std) == 3
-                    p['noise_translate'][b] = np.array([rng.normal(0, std[0], 1), rng.normal(0, std[1], 1), rng.normal(0, std[2], 1)],
-                                                       dtype=np.float32).T
+            self._draw_frame(b, rng, p, gt_classes, n_boxes, lo_q, hi_q)
         return p
+
+    def _draw_frame(self, b, rng, p, gt_classes, n_boxes, lo_q, hi_q):
+        if self.gt_sampler is not None and lo_q == 0:
+            p['gt_sampled'].append(self.gt_sampler.draw(gt_classes[b], rng))
+        for qi, (name, cur) in enumerate(self.queue):
+            if name == GT_SAMPLING or not lo_q <= qi < hi_q:
+                continue
+            if name in _obj.OBJECT_STAGES:
+                p['object'][qi][b] = _obj.draw_entry(name, cur, n_boxes[b], rng)
+            elif name == 'random_world_flip':
+                for axis in _get(cur, 'ALONG_AXIS_LIST'):
+                    p['flip_%s' % axis][b] = rng.choice([False, True], replace=False, p=[0.5, 0.5])
+            elif name == 'random_world_rotation':
+                lo, hi = self.rot_range(cur)
+                p['noise_rot'][b] = rng.uniform(lo, hi)
+            elif name == 'random_world_scaling':
+                lo, hi = _get(cur, 'WORLD_SCALE_RANGE')
+                p['noise_scale'][b] = rng.uniform(lo, hi)
+            else:
+                std = _get(cur, 'NOISE_TRANSLATE_STD')
+                assert len(std) == 3
+                p['noise_translate'][b] = np.array([rng.normal(0, std[0], 1), rng.normal(0, std[1], 1), rng.normal(0, std[2], 1)],
+                                                   dtype=np.float32).T
 
     def table(self, p):
         """(B, AUG_TABLE_STRIDE) float32: the per-frame parameters as the kernels read them (include/pcp_hip_train.h)"""
@@ -183,7 +259,7 @@ class DeviceWorldAugmentor:
         t[:, 6:9] = p['noise_translate']
         return t
 
-    def descriptor(self, batch_size, stages=None, filter=None):
+    def descriptor(self, batch_size, stages=None, filter=None, raw_heading=False):
         stages = self.stages if stages is None else list(stages)
         a = _lib.WorldAug()
         a.n_stages = len(stages)
@@ -194,6 +270,7 @@ class DeviceWorldAugmentor:
         a.filter = int(self.filter if filter is None else filter)
         for i, v in enumerate(self.point_cloud_range):
             a.range[i] = v
+        a.raw_heading = int(bool(raw_heading))
         return a
 
     # ---- the two launches ---------------------------------------------------------------------------------------------------------
@@ -230,8 +307,9 @@ class DeviceWorldAugmentor:
         kept = counts.cpu().numpy()
         return out[:int(kept.sum())], kept
 
-    def augment_boxes(self, gt_boxes, instances_tf, table_dev, stages=None):
-        """gt_boxes (B, M, 8 | 10), instances_tf (B, M, S, 3 | 4, 4) or None -> new tensors; one launch"""
+    def augment_boxes(self, gt_boxes, instances_tf, table_dev, stages=None, raw_heading=False):
+        """gt_boxes (B, M, 8 | 10), instances_tf (B, M, S, 3 | 4, 4) or None -> new tensors; one launch.  raw_heading: no limit_period at the
+        end (object stages follow)"""
         _need_cuda(gt_boxes, instances_tf, table_dev)
         if gt_boxes.dim() != 3 or gt_boxes.shape[2] not in BOX_WIDTHS:
             raise ValueError('gt_boxes of shape %s: the augmentation kernel takes (B, M, W) with W in %s (x y z dx dy dz heading [vx vy] class)'
@@ -247,7 +325,7 @@ class DeviceWorldAugmentor:
             n_sweeps, tf_rows = int(instances_tf.shape[2]), int(instances_tf.shape[3])
             instances_tf = instances_tf.float().contiguous().clone()
         gt_boxes = gt_boxes.float().contiguous().clone()
-        a = self.descriptor(B, stages, False)
+        a = self.descriptor(B, stages, False, raw_heading)
         if M > 0 and (instances_tf is None or n_sweeps > 0):
             check(_lib.load().pcp_world_augment_boxes(ctypes.byref(a), _p(table_dev), _p(gt_boxes), M, W, _p(instances_tf), n_sweeps, tf_rows,
                                                       _stream()), 'pcp_world_augment_boxes')
@@ -261,8 +339,13 @@ class DeviceWorldAugmentor:
         if self.gt_sampler is not None:                      # the paste first: pasted points and boxes go through the transforms and the mask
             self.gt_sampler.apply(batch_dict, params['gt_sampled'])
         points = batch_dict['points']
+        if self.has_object_stages:
+            self.check_plan(batch_dict, self.steps)
         _need_cuda(points)
         table_dev = torch.from_numpy(self.table(params)).to(points.device)
+        if self.has_object_stages:
+            self.run_steps(batch_dict, params, [s for s in self.steps if s['kind'] != 'gt'], table_dev)
+            return self._finish(batch_dict, params)
         batch_dict['points'], kept = self.augment_points(points, table_dev, B)
         if kept is not None:
             batch_dict['aug_points_kept'] = kept
@@ -272,6 +355,58 @@ class DeviceWorldAugmentor:
                 batch_dict['instances_tf'] = tf
         elif batch_dict.get('instances_tf', None) is not None:
             raise ValueError('instances_tf without gt_boxes: the class column of gt_boxes tells the real objects from the padding')
+        return self._finish(batch_dict, params)
+
+    def run_steps(self, batch_dict, params, steps, table_dev=None):
+        """the launches of `steps` (self.steps entries other than the paste) on batch_dict, in order"""
+        B = int(batch_dict['batch_size'])
+        self.check_plan(batch_dict, steps)
+        if table_dev is None:
+            table_dev = torch.from_numpy(self.table(params)).to(batch_dict['points'].device)
+        for step in steps:
+            final = step is self.steps[-1]
+            if step['kind'] == 'world':
+                filt = self.filter and final
+                if step['stages'] or filt:
+                    batch_dict['points'], kept = self.augment_points(batch_dict['points'], table_dev, B, stages=step['stages'], filter=filt)
+                    if kept is not None:
+                        batch_dict['aug_points_kept'] = kept
+                batch_dict['gt_boxes'], tf = self.augment_boxes(batch_dict['gt_boxes'], batch_dict.get('instances_tf', None), table_dev,
+                                                                stages=step['stages'], raw_heading=not final)
+                if tf is not None:
+                    batch_dict['instances_tf'] = tf
+            elif step['kind'] == 'local':
+                if not step['stages']:
+                    continue
+                values = [np.concatenate([np.asarray(params['object'][qi][b], dtype=np.float64).reshape(len(_obj.sub_stages(*self.queue[qi])), -1)
+                                          for qi in step['q'] if len(_obj.sub_stages(*self.queue[qi]))], axis=0) for b in range(B)]
+                batch_dict['points'], batch_dict['gt_boxes'], _ = _obj.local_stages(batch_dict['points'], batch_dict['gt_boxes'].float(),
+                                                                                    step['stages'], values, limit_heading=final)
+            elif step['kind'] == 'wdrop':
+                qi = step['q'][0]
+                for k, direction in enumerate(step['stages']):
+                    inten = [float(np.asarray(params['object'][qi][b]).reshape(-1)[k]) for b in range(B)]
+                    batch_dict['points'], batch_dict['gt_boxes'], tf, _, _ = _obj.world_dropout(
+                        batch_dict['points'], batch_dict['gt_boxes'].float(), batch_dict.get('instances_tf', None), direction, inten)
+                    if tf is not None:
+                        batch_dict['instances_tf'] = tf
+
+    @staticmethod
+    def check_plan(batch_dict, steps):
+        """the refusals of every object step of `steps`, before the first launch of any of them: no world stage changes the dtype, the box
+        width or the number of box rows, so what holds for the batch as it arrives holds at each step"""
+        stages = [c for s in steps if s['kind'] in ('local', 'wdrop') for c in s['stages']]
+        if not stages:
+            return
+        if batch_dict.get('gt_boxes', None) is None:
+            raise ValueError('object stages need gt_boxes: they move the points inside each box')
+        gt, pts = batch_dict['gt_boxes'], batch_dict['points']
+        _obj._check_boxes(gt.float(), stages)                    # run_steps hands the boxes over as float32
+        _obj._check_points(pts, int(batch_dict['batch_size']))
+
+    def _finish(self, batch_dict, params):
+        if self.gt_sampler is not None or self.has_object_stages:
+            batch_dict.pop('num_gt_boxes', None)            # the loader's counts: the paste and the world dropout have changed them
         meta = batch_dict.get('metadata', None)
         if meta is not None:
             batch_dict['metadata'] = [dict(m, se3_from_ego=augment_se3_from_ego(m['se3_from_ego'], self.stages, params, b))
@@ -287,6 +422,33 @@ class DeviceWorldAugmentor:
             batch_dict['noise_scale'] = np.asarray(params['noise_scale']).copy()
         return batch_dict
 
+    @staticmethod
+    def box_counts(batch_dict):
+        """the real boxes of every frame: batch_dict['num_gt_boxes'] when the loader put the host's numbers there, else one read of the class
+        column's per-frame counts (B integers)"""
+        if batch_dict.get('num_gt_boxes', None) is not None:
+            return [int(v) for v in batch_dict['num_gt_boxes']]
+        return [int(v) for v in (batch_dict['gt_boxes'][..., -1] != 0).sum(dim=1).cpu().tolist()]
+
     def __call__(self, batch_dict, rng=None):
+        rng = self.rng if rng is None else rng
         classes = self.gt_sampler.frame_gt_classes(batch_dict['gt_boxes']) if self.gt_sampler is not None else None
-        return self.apply(batch_dict, self.draw(batch_dict['batch_size'], self.rng if rng is None else rng, classes))
+        if not self.has_object_stages:
+            return self.apply(batch_dict, self.draw(batch_dict['batch_size'], rng, classes))
+        B = int(batch_dict['batch_size'])
+        n_boxes = [len(c) for c in classes] if classes is not None else self.box_counts(batch_dict)
+        if not self.splits:
+            return self.apply(batch_dict, self.draw(B, rng, classes, n_boxes))
+        # the box counts change on the device in the middle of the list: draw up to there, run, read the counts back (once per such place), go on
+        bounds = [0] + self.splits + [len(self.queue)]
+        params = None
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            if lo > 0:
+                batch_dict.pop('num_gt_boxes', None)
+                n_boxes = self.box_counts(batch_dict)
+            params = self.draw(B, rng, classes, n_boxes, entries=(lo, hi)) if params is None else self.draw(B, rng, classes, n_boxes, (lo, hi), params)
+            if lo == 0 and self.gt_sampler is not None:
+                self.gt_sampler.apply(batch_dict, params['gt_sampled'])
+            steps = [s for s in self.steps if s['kind'] != 'gt' and (all(lo <= q < hi for q in s['q']) if s['q'] else hi == len(self.queue))]
+            self.run_steps(batch_dict, params, steps)
+        return self._finish(batch_dict, params)

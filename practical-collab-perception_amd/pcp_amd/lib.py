@@ -160,7 +160,19 @@ GTS_MAX_GROUPS, GTS_MAX_CAND, GTS_MAX_BOXES, GTS_CAND_STRIDE, GTS_ACC_STRIDE = 1
 class WorldAug(ctypes.Structure):
     """pcp_world_aug_t (include/pcp_hip_train.h)"""
     _fields_ = [('n_stages', c_i32), ('stage', c_i32 * AUG_MAX_STAGES), ('batch', c_i32), ('hd_map', c_i32), ('filter', c_i32),
-                ('range', c_f * 6)]
+                ('range', c_f * 6), ('raw_heading', c_i32)]
+
+
+# PCP_OBJ_* (include/pcp_hip_train.h)
+OBJ_TRANSLATE_X, OBJ_TRANSLATE_Y, OBJ_TRANSLATE_Z, OBJ_SCALE, OBJ_ROTATE = 1, 2, 3, 4, 5
+OBJ_DROP_TOP, OBJ_DROP_BOTTOM, OBJ_DROP_LEFT, OBJ_DROP_RIGHT = 6, 7, 8, 9
+OBJ_WORLD_DROP_TOP, OBJ_WORLD_DROP_BOTTOM, OBJ_WORLD_DROP_LEFT, OBJ_WORLD_DROP_RIGHT = 10, 11, 12, 13
+OBJ_MAX_STAGES, OBJ_MAX_BOXES, OBJ_LDS_BOXES, OBJ_STATE_STRIDE, OBJ_PARAM_STRIDE = 16, 512, 64, 12, 4
+
+
+class ObjectAug(ctypes.Structure):
+    """pcp_object_aug_t (include/pcp_hip_train.h)"""
+    _fields_ = [('n_stages', c_i32), ('stage', c_i32 * OBJ_MAX_STAGES), ('batch', c_i32), ('limit_heading', c_i32)]
 
 
 class HunterMeta(ctypes.Structure):
@@ -351,6 +363,12 @@ SYMBOLS.update({
     'pcp_world_augment_points_workspace_bytes': (c_sz, [c_i64]),
     'pcp_world_augment_points': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i64, c_i32, vp, vp, vp, c_sz, vp]),
     'pcp_world_augment_boxes': (c_i32, [ctypes.POINTER(WorldAug), vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp]),
+    'pcp_object_augment_boxes': (c_i32, [ctypes.POINTER(ObjectAug), vp, vp, c_i32, c_i32, vp, vp, vp]),
+    'pcp_object_augment_points_workspace_bytes': (c_sz, [c_i64]),
+    'pcp_object_augment_points': (c_i32, [ctypes.POINTER(ObjectAug), vp, vp, c_i32, vp, vp, c_i64, c_i32, vp, vp, vp, c_sz, vp]),
+    'pcp_frame_extent_workspace_bytes': (c_sz, [c_i64, c_i32]),
+    'pcp_frame_extent': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, vp, vp, c_sz, vp]),
+    'pcp_object_augment_drop_boxes': (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, c_i32, vp, vp, vp, vp, vp]),
     'pcp_gt_sample_select': (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, vp, vp, c_i32, vp, c_i32, vp, c_i32, vp, vp]),
     'pcp_gt_sample_paste_points': (c_i32, [vp, c_i64, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, vp, vp, vp, c_i32, c_i64, vp, vp, vp]),
     'pcp_gt_sample_paste_boxes': (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, vp, vp, vp, vp, c_i32, vp]),

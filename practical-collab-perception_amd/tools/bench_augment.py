@@ -1,6 +1,12 @@
 """Times pcp_world_augment_points (csrc/augment.hip) against the same sequence written in eager torch ops on the GPU.
 
-    python bench_augment.py [--iters 30] [--warmup 5] [--out FILE] [--gt-sampling]
+    python bench_augment.py [--iters 30] [--warmup 5] [--out FILE] [--gt-sampling | --object]
+
+--object times the per-object walk instead (csrc/object_augment.hip through pcp_amd/object_augment.py): 260 000 rows x 1 frame and x 4 frames
+of 1 + 5 columns, 40 boxes per frame of (B, 40, 8).  Two lists: moves only (translation x y z, rotation, scaling: 5 sub-stages, one point
+launch) and the same plus a local frustum dropout top / left (7 sub-stages, count + place launches and the read of the kept counts).
+Timed: pcp_object_augment_points alone on ready box states, local_stages() as a whole (parameter table, box kernel, point kernel), and the
+same walk written in torch ops (per frame, sub-stage and box a masked update on the frame's rows; --torch-iters calls, it is slow).
 
 --gt-sampling times the ground-truth database paste instead (csrc/gt_sample.hip through pcp_amd/gt_sampler.py): the nuScenes cloud at
 B = 1 and B = 4, the reference's SAMPLE_GROUPS, a synthetic database of 300 objects.  Timed: DeviceGtSampler.apply() with the tile form of
@@ -221,16 +227,107 @@ def gt_sampling_bench(args):
     return lines
 
 
+def make_boxes(B, M, seed=3):
+    """(B, M, 8): M cars on a jittered grid inside +-48 m, any heading"""
+    rng = np.random.RandomState(seed)
+    g = np.zeros((B, M, 8), dtype=np.float32)
+    side = int(np.ceil(np.sqrt(M)))
+    for b in range(B):
+        for m in range(M):
+            g[b, m, 0:2] = (np.array([m % side, m // side]) + 0.5) / side * 96.0 - 48.0 + rng.uniform(-2, 2, 2)
+            g[b, m, 2] = rng.uniform(-2.5, -0.5)
+            g[b, m, 3:6] = [rng.uniform(3.8, 5.2), rng.uniform(1.7, 2.3), rng.uniform(1.4, 2.0)]
+            g[b, m, 6] = rng.uniform(-3.1, 3.1)
+            g[b, m, 7] = 1
+    return g
+
+
+def torch_walk(points, gt, stages, values, per_frame):
+    """the walk of csrc/object_augment.hip in torch ops on the device: values (B, K, M) float32 CUDA; nothing is read by the host until the
+    final boolean index"""
+    from pcp_amd import lib as L
+    out = points.clone()
+    alive = torch.ones(out.shape[0], dtype=torch.bool, device=out.device)
+    for b in range(gt.shape[0]):
+        sub, al, g = out[b * per_frame:(b + 1) * per_frame], alive[b * per_frame:(b + 1) * per_frame], gt[b].clone()
+        for k, st in enumerate(stages):
+            for i in range(g.shape[0]):
+                box, v = g[i], values[b, k, i]
+                sx, sy, sz = sub[:, 1] - box[0], sub[:, 2] - box[1], sub[:, 3] - box[2]
+                ca, sa = torch.cos(-box[6]), torch.sin(-box[6])
+                lx, ly = sx * ca + sy * (-sa), sx * sa + sy * ca
+                m = (sz.abs() <= box[5] / 2) & (lx.abs() <= box[3] / 2 + 0.1) & (ly.abs() <= box[4] / 2 + 0.1) & al
+                if st <= L.OBJ_TRANSLATE_Z:
+                    sub[:, st] = torch.where(m, sub[:, st] + v, sub[:, st])
+                    g[i, st - 1] += v
+                elif st == L.OBJ_SCALE:
+                    for a, d in ((1, sx), (2, sy), (3, sz)):
+                        sub[:, a] = torch.where(m, d * v + box[a - 1], sub[:, a])
+                    g[i, 3:6] *= v
+                elif st == L.OBJ_ROTATE:
+                    c, s_ = torch.cos(v), torch.sin(v)
+                    sub[:, 1] = torch.where(m, sx * c - sy * s_ + box[0], sub[:, 1])
+                    sub[:, 2] = torch.where(m, sx * s_ + sy * c + box[1], sub[:, 2])
+                    g[i, 6] += v
+                elif st == L.OBJ_DROP_TOP:
+                    al &= ~(m & (sub[:, 3] >= (box[2] + box[5] / 2) - v * box[5]))
+                elif st == L.OBJ_DROP_LEFT:
+                    al &= ~(m & (sub[:, 2] >= (box[1] + box[4] / 2) - v * box[4]))
+    return out[alive]
+
+
+def object_bench(args):
+    import ctypes
+    from pcp_amd import lib as L
+    from pcp_amd import object_augment as obj
+    from pcp_amd.ops import _p, _stream
+    moves = [L.OBJ_TRANSLATE_X, L.OBJ_TRANSLATE_Y, L.OBJ_TRANSLATE_Z, L.OBJ_ROTATE, L.OBJ_SCALE]
+    lists = [('moves (5 sub-stages)', moves), ('moves + dropout top, left (7 sub-stages)', moves + [L.OBJ_DROP_TOP, L.OBJ_DROP_LEFT])]
+    rng_of = {L.OBJ_ROTATE: (-0.3, 0.3), L.OBJ_SCALE: (0.9, 1.1), L.OBJ_DROP_TOP: (0.1, 0.4), L.OBJ_DROP_LEFT: (0.1, 0.4)}
+    M, S, per_frame = 40, 6, 260000
+    lines = ['pcp_object_augment_points vs the same walk in torch ops, %s, %d boxes per frame, mean (min) of %d calls after %d warm-up calls '
+             '(torch ops: %d calls after 1)' % (torch.cuda.get_device_name(0), M, args.iters, args.warmup, args.torch_iters)]
+    for B in (1, 4):
+        pts = make_cloud(B, per_frame, S, False, [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]).cuda()
+        gt = torch.from_numpy(make_boxes(B, M)).cuda()
+        n = B * per_frame
+        for tag, stages in lists:
+            rs = np.random.RandomState(5)
+            values = [np.stack([rs.uniform(*rng_of.get(st, (-0.5, 0.5)), M) for st in stages]) for _ in range(B)]
+            got, g_out, kept = obj.local_stages(pts, gt, stages, values)
+            vt = torch.from_numpy(np.stack(values).astype(np.float32)).cuda()
+            want = torch_walk(pts, gt, stages, vt, per_frame)
+            torch.cuda.synchronize()
+            same = got.shape[0] == want.shape[0]
+            err = float((got[:, 1:4] - want[:, 1:4]).abs().max()) if same else float('nan')
+            # the point kernel alone: box states made once
+            a = obj.descriptor(stages, B)
+            params = torch.from_numpy(obj.param_table(stages, values, M)).cuda()
+            states = torch.empty((B, len(stages), M, L.OBJ_STATE_STRIDE), dtype=torch.float32, device='cuda')
+            nb = torch.empty(B, dtype=torch.int32, device='cuda')
+            L.check(L.load().pcp_object_augment_boxes(ctypes.byref(a), _p(params), _p(gt.clone()), M, 8, _p(states), _p(nb), _stream()), 'boxes')
+            k_us, k_min = timed(lambda: obj._points_call(a, states, nb, M, None, pts), args.warmup, args.iters)
+            w_us, w_min = timed(lambda: obj.local_stages(pts, gt, stages, values), args.warmup, args.iters)
+            t_us, t_min = timed(lambda: torch_walk(pts, gt, stages, vt, per_frame), 1, args.torch_iters)
+            useful = (n + int(got.shape[0])) * S * 4
+            lines.append('B=%d %8d rows x %d floats, %s, kept %8d: point kernel %8.1f us (%7.1f) %7.1f GB/s | local_stages() %8.1f us (%7.1f) | '
+                         'torch ops %10.1f us (%9.1f) | x%.0f, rows equal %s, max |xyz diff| %.2g'
+                         % (B, n, S, tag, got.shape[0], k_us, k_min, useful / k_us / 1e3, w_us, w_min, t_us, t_min, t_us / k_us, same, err))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', type=str, default=None)
     ap.add_argument('--gt-sampling', action='store_true', help='time the ground-truth database paste instead of the world stages')
+    ap.add_argument('--object', action='store_true', help='time the per-object walk (local moves, local frustum dropouts) instead')
+    ap.add_argument('--torch-iters', type=int, default=3, help='--object: timed calls of the torch-ops walk')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_augment.py needs the GPU'
-    if args.gt_sampling:
-        text = '\n'.join(gt_sampling_bench(args))
+    if args.gt_sampling or args.object:
+        text = '\n'.join(object_bench(args) if args.object else gt_sampling_bench(args))
         print(text)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -61,6 +61,8 @@ def parse_config():
         cfg.DATA_CONFIG.SYNTHETIC.DEVICE_AUG = False        # present before --set, which only takes keys that exist
     if 'DEVICE_GT_SAMPLING' not in cfg.DATA_CONFIG.SYNTHETIC:
         cfg.DATA_CONFIG.SYNTHETIC.DEVICE_GT_SAMPLING = False
+    if 'DEVICE_OBJECT_AUG' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.DEVICE_OBJECT_AUG = False  # with DEVICE_AUG: the per-object entries of the list run too (object_stages=True)
     if 'GT_DATABASE_FRAMES' not in cfg.DATA_CONFIG.SYNTHETIC:
         cfg.DATA_CONFIG.SYNTHETIC.GT_DATABASE_FRAMES = 8
     if 'GT_DROP_UNSTOCKED_GROUPS' not in cfg.DATA_CONFIG.SYNTHETIC:
@@ -111,7 +113,8 @@ def build_augmentor(args, cfg, train_set, logger):
     from pcp_amd.augment import DeviceWorldAugmentor
     aug = DeviceWorldAugmentor.from_dataset_cfg(cfg.DATA_CONFIG, layout=getattr(train_set, 'layout', 'car'), logger=logger,
                                                 seed=666 + cfg.LOCAL_RANK if args.fix_random_seed else None,
-                                                gt_sampler=build_gt_sampler(cfg, train_set, logger))
+                                                gt_sampler=build_gt_sampler(cfg, train_set, logger),
+                                                object_stages=bool(cfg.DATA_CONFIG.SYNTHETIC.get('DEVICE_OBJECT_AUG', False)))
     if aug.gt_sampler is not None:
         logger.info('device gt_sampling: database sizes %s' % aug.gt_sampler.class_sizes())
     logger.info('device world augmentation: stages %s, range filter %s' % ([n for n, _ in aug.queue], 'on' if aug.filter else 'off'))
