@@ -125,7 +125,9 @@ int pcp_mp_conv3x3_plan(const pcp_mp_conv3x3_t *desc, int32_t *fast_kernel, doub
  * pixel-contraction GEMM on v_mfma_f32_32x32x16_bf16 (operands transposed out of the NHWC LDS images by ds_read_b64_tr_b16), fp32
  * accumulation, split over the pixels with a fixed-order reduction (bitwise reproducible).  x, dy: bf16 (the activations / gradients the
  * bf16 loop stores; the descriptor's dtype fields must say PCP_DT_BF16), 16-byte aligned, ld % 8 == 0; dw float32 (cout, cin, 3, 3).
- * cin % 8 == 0, cout % 8 == 0 (padded to 64 x 64 tiles internally); stride 2 needs even in_h, in_w.
+ * cin % 8 == 0, cout % 8 == 0 (padded to 64 x 64 tiles internally); stride 2 needs even in_h, in_w.  x and dy may be channel windows of
+ * wider buffers (ld_x >= cin, ld_dy >= cout, the pointers at the window's first channel): nothing past the last channel of the last
+ * pixel's window is read.
  * Replaces the weight-gradient half of nn.Conv2d's autograd node under autocast.  workspace: pcp_mp_conv3x3_wgrad_workspace_bytes.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct {

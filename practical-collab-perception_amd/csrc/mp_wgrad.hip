@@ -328,7 +328,7 @@ struct WgPlan { int n_cob, n_cib, n_strips, n_rsplit, rows_per, n_split, oh, ow;
 
 bool wg_plan(const pcp_mp_wgrad3x3_t *d, WgPlan &pl) {
   if (!d || d->batch <= 0 || d->in_h <= 0 || d->in_w <= 0 || d->cin <= 0 || d->cout <= 0 || (d->stride != 1 && d->stride != 2)) return false;
-  if ((d->cin % 8) || (d->cout % 8) || (d->ld_x % 8) || (d->ld_dy % 8)) return false;
+  if ((d->cin % 8) || (d->cout % 8) || (d->ld_x % 8) || (d->ld_dy % 8) || d->ld_x < d->cin || d->ld_dy < d->cout) return false;
   if (d->x_dtype != PCP_DT_BF16 || d->dy_dtype != PCP_DT_BF16) return false;
   if (d->stride == 2 && ((d->in_h | d->in_w) & 1)) return false;
   pl.oh = d->in_h / d->stride;
@@ -377,7 +377,12 @@ int pcp_mp_conv3x3_wgrad(const pcp_mp_wgrad3x3_t *d, const void *x, const void *
   p.batch = d->batch; p.h = d->in_h; p.w = d->in_w; p.oh = pl.oh; p.ow = pl.ow; p.cin = d->cin; p.cout = d->cout;
   p.ld_x = d->ld_x; p.ld_dy = d->ld_dy;
   p.n_cob = pl.n_cob; p.n_cib = pl.n_cib; p.n_strips = pl.n_strips; p.n_rsplit = pl.n_rsplit; p.rows_per = pl.rows_per; p.n_split = pl.n_split;
-  p.x_bytes = (unsigned)xb; p.dy_bytes = (unsigned)db;
+  // the buffer ranges end with the last channel of the last pixel's WINDOW: x and dy may point ch_off channels into a wider buffer, and a
+  // 128-byte record copy of a channel block that holds fewer than 64 channels reaches past the window (into columns / rows of the tile
+  // nobody reduces).  With the whole map's size as the range, the records of the last pixels were read up to ch_off channels past the end
+  // of the allocation; now those pieces are out of range and come back as zeros.  (cin, cout, ld % 8 == 0: a 16-byte piece is never cut)
+  p.x_bytes = (unsigned)(xb - (long long)(d->ld_x - d->cin) * 2);
+  p.dy_bytes = (unsigned)(db - (long long)(d->ld_dy - d->cout) * 2);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nwg = (unsigned)(pl.n_cob * pl.n_cib * pl.n_split);
   if (d->stride == 1) hipLaunchKernelGGL(k_mp_wgrad3x3<1>, dim3(nwg), dim3(WG_THREADS), 0, s, p);
