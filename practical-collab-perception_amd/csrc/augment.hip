@@ -15,15 +15,14 @@
 
 namespace {
 
+#include "aug_tile.h"
+
 constexpr int AUG_THREADS = 256;
 constexpr int AUG_ITEMS = PCP_AUG_TILE_ROWS / AUG_THREADS;       // rows per thread
 constexpr int AUG_WAVES = AUG_THREADS / PCP_WAVE;
 constexpr int TS = PCP_AUG_TABLE_STRIDE;
 static_assert(PCP_AUG_TILE_ROWS % AUG_THREADS == 0 && (PCP_AUG_TILE_ROWS * 4) % 16 == 0, "a tile starts 16-byte aligned for every stride");
 static_assert(2 * (PCP_AUG_TILE_ROWS * PCP_AUG_MAX_ROW_STRIDE + 4) * 4 <= 65536, "both tile buffers fit the LDS of one workgroup");
-
-constexpr float AUG_PI = 3.14159274101257324f;                   // float32(np.pi): what numpy adds to a float32 column
-constexpr float AUG_2PI = 6.28318548202514648f;                  // float32(2 * np.pi)
 
 // atan2(sin v, cos v): how the reference brings lane_dir and the MoDAR heading back into [-pi, pi]
 __device__ __forceinline__ float aug_wrap(float v) { return atan2f(sinf(v), cosf(v)); }
@@ -91,26 +90,6 @@ __device__ __forceinline__ bool aug_row(const float *row, int S, const pcp_world
   return r.x >= a.range[0] && r.x < a.range[3] && r.y >= a.range[1] && r.y < a.range[4] && r.z >= a.range[2] && r.z < a.range[5];
 }
 
-// `count` floats from src (16-byte aligned) into LDS: 16-byte loads, the last count % 4 floats one by one
-__device__ __forceinline__ void aug_stage_in(float *lds, const float *__restrict__ src, int count) {
-  const int n4 = count >> 2;
-  const f32x4 *s4 = reinterpret_cast<const f32x4 *>(src);
-  f32x4 *d4 = reinterpret_cast<f32x4 *>(lds);
-  for (int i = threadIdx.x; i < n4; i += AUG_THREADS) d4[i] = s4[i];
-  for (int i = (n4 << 2) + threadIdx.x; i < count; i += AUG_THREADS) lds[i] = src[i];
-}
-
-// LDS floats [lo, hi) to dst0[lo .. hi), where dst0 is 16-byte aligned: 16-byte stores over the aligned middle, single floats at both ends
-__device__ __forceinline__ void aug_stage_out(float *__restrict__ dst0, const float *lds, int lo, int hi) {
-  int alo = (lo + 3) & ~3, ahi = hi & ~3;
-  if (alo > ahi) alo = ahi = hi;                                      // no aligned middle: everything goes through the first loop
-  for (int i = lo + threadIdx.x; i < alo; i += AUG_THREADS) dst0[i] = lds[i];
-  f32x4 *d4 = reinterpret_cast<f32x4 *>(dst0);
-  const f32x4 *s4 = reinterpret_cast<const f32x4 *>(lds);
-  for (int i = (alo >> 2) + threadIdx.x; i < (ahi >> 2); i += AUG_THREADS) d4[i] = s4[i];
-  for (int i = ahi + threadIdx.x; i < hi; i += AUG_THREADS) dst0[i] = lds[i];
-}
-
 // rows of this tile inside the range -> tile_cnt[tile]; per frame -> frame_count (integer adds: the order does not reach the result)
 __global__ __launch_bounds__(AUG_THREADS) void k_aug_count(const float *__restrict__ points, long long n, int S, pcp_world_aug_t a,
                                                            const float *__restrict__ table, int *__restrict__ tile_cnt,
@@ -122,9 +101,8 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_count(const float *__restri
   const long long base = (long long)blockIdx.x * PCP_AUG_TILE_ROWS;
   const int rows = (int)((n - base) < PCP_AUG_TILE_ROWS ? (n - base) : PCP_AUG_TILE_ROWS);
   if (threadIdx.x < PCP_AUG_MAX_BATCH) s_frame[threadIdx.x] = 0;
-  aug_stage_in(in, points + base * S, rows * S);
+  aug_stage_in<AUG_THREADS>(in, points + base * S, rows * S);
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int it = 0; it < AUG_ITEMS; it++) {
     const int r = it * AUG_THREADS + threadIdx.x;
@@ -135,19 +113,9 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_count(const float *__restri
       keep = aug_row(in + r * S, S, a, table, v, modar);
       if (keep && a.filter) atomicAdd(&s_frame[(int)in[r * S]], 1);  // kept with the filter on: the frame index is inside [0, batch)
     }
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) s_wave[it][wave] = __popcll(bal);
+    aug_tile_rank<AUG_THREADS>(keep, it, s_wave);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-#pragma unroll
-    for (int it = 0; it < AUG_ITEMS; it++)
-#pragma unroll
-      for (int w = 0; w < AUG_WAVES; w++) tot += s_wave[it][w];
-    tile_cnt[blockIdx.x] = tot;
-  }
-  if ((int)threadIdx.x < a.batch && s_frame[threadIdx.x]) atomicAdd(&frame_count[threadIdx.x], s_frame[threadIdx.x]);
+  aug_tile_count_finish<AUG_THREADS>(s_wave, s_frame, a.batch, tile_cnt, frame_count);
 }
 
 __global__ __launch_bounds__(AUG_THREADS) void k_aug_place(const float *__restrict__ points, long long n, int S, pcp_world_aug_t a,
@@ -160,13 +128,9 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_place(const float *__restri
   __shared__ long long s_before[AUG_WAVES];
   const long long base = (long long)blockIdx.x * PCP_AUG_TILE_ROWS;
   const int rows = (int)((n - base) < PCP_AUG_TILE_ROWS ? (n - base) : PCP_AUG_TILE_ROWS);
-  aug_stage_in(in, points + base * S, rows * S);
-  // rows kept by the tiles in front of this one: every workgroup adds the per-tile counts up itself (a few KB from L2), no scan launch
-  long long before = 0;
-  if (a.filter)
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += AUG_THREADS) before += tile_cnt[i];
+  aug_stage_in<AUG_THREADS>(in, points + base * S, rows * S);
+  const long long before = a.filter ? aug_tile_before<AUG_THREADS>(tile_cnt) : 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   bool keep[AUG_ITEMS];
   int rank[AUG_ITEMS];
 #pragma unroll
@@ -184,49 +148,14 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_place(const float *__restri
       if (a.hd_map) row[10] = v.lane;
       if (modar) row[9] = v.head;
     }
-    const unsigned long long bal = __ballot(keep[it]);
-    rank[it] = __popcll(bal & ((1ULL << lane) - 1ULL));
-    if (lane == 0) s_wave[it][wave] = __popcll(bal);
+    rank[it] = aug_tile_rank<AUG_THREADS>(keep[it], it, s_wave);
   }
   if (!a.filter) {                                                    // same place, same alignment: the tile goes back as it came
     __syncthreads();
-    aug_stage_out(out + base * S, in, 0, rows * S);
+    aug_stage_out<AUG_THREADS>(out + base * S, in, 0, rows * S);
     return;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
-  if (lane == 0) s_before[wave] = before;
-  __syncthreads();
-  before = 0;
-#pragma unroll
-  for (int w = 0; w < AUG_WAVES; w++) before += s_before[w];
-  __syncthreads();                                                    // every thread has read s_before before thread 0 reuses its first entry
-  int kept = 0;
-  if (threadIdx.x == 0) {                                             // exclusive prefix in input order: items, then waves, then lanes
-    int run = 0;
-#pragma unroll
-    for (int it = 0; it < AUG_ITEMS; it++)
-#pragma unroll
-      for (int w = 0; w < AUG_WAVES; w++) {
-        const int c = s_wave[it][w];
-        s_wave[it][w] = run;
-        run += c;
-      }
-    s_before[0] = run;
-  }
-  __syncthreads();
-  kept = (int)s_before[0];
-  const int pad = (int)((before * S) & 3);                            // destination float index modulo 4
-#pragma unroll
-  for (int it = 0; it < AUG_ITEMS; it++)
-    if (keep[it]) {
-      const float *row = in + (it * AUG_THREADS + threadIdx.x) * S;
-      float *dst = ob + pad + (s_wave[it][wave] + rank[it]) * S;
-      for (int c = 0; c < S; c++) dst[c] = row[c];
-    }
-  __syncthreads();
-  // before + kept <= rows in front of and inside this tile <= n: the stores stay inside the n rows of `out`
-  aug_stage_out(out + before * S - pad, ob, pad, pad + kept * S);
+  aug_tile_compact<AUG_THREADS>(before, keep, rank, in, ob, S, s_wave, s_before, out);
 }
 
 // one thread per box (k == 0) or per instance matrix (k >= 1) of object (b, m)
@@ -284,8 +213,7 @@ __global__ __launch_bounds__(256) void k_aug_boxes(pcp_world_aug_t a, const floa
           break;
       }
     }
-    // limit_period(h, 0.5, 2 pi) = h - floor(h / period + 0.5) * period, every operation rounded to float32 as torch-CPU does
-    if (!a.raw_heading) h = __fsub_rn(h, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(h, AUG_2PI), 0.5f)), AUG_2PI));
+    if (!a.raw_heading) h = aug_limit_period(h);
     box[0] = x;
     box[1] = y;
     box[2] = z;
@@ -357,26 +285,16 @@ bool aug_ok(const pcp_world_aug_t *a) {
 }  // namespace
 
 extern "C" size_t pcp_world_augment_points_workspace_bytes(int64_t n) {
-  if (n < 0) return 0;
-  const int64_t tiles = (n + PCP_AUG_TILE_ROWS - 1) / PCP_AUG_TILE_ROWS;
-  return pcp_align_up((size_t)(tiles > 0 ? tiles : 1) * 4, 256);
+  return aug_points_workspace_bytes(n);
 }
 
 extern "C" int pcp_world_augment_points(const pcp_world_aug_t *aug, const float *table, const float *points, int64_t n, int32_t row_stride,
                                         float *out, int32_t *frame_count, void *workspace, size_t workspace_bytes, void *stream_) {
-  if (!aug_ok(aug) || !table || n < 0 || row_stride < PCP_AUG_MIN_ROW_STRIDE || row_stride > PCP_AUG_MAX_ROW_STRIDE) return PCP_ERR_ARG;
-  if (aug->hd_map && row_stride != 13) return PCP_ERR_ARG;
-  if (n * row_stride >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;       // LDS and tile indices are ints
-  if ((((uintptr_t)points) | ((uintptr_t)out)) & 15) return PCP_ERR_ARG;
+  if (!aug_ok(aug) || !table || (aug->hd_map && row_stride != 13)) return PCP_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  if (aug->filter) {
-    if (!frame_count || !workspace || (((uintptr_t)frame_count) & 3)) return PCP_ERR_ARG;
-    if (workspace_bytes < pcp_world_augment_points_workspace_bytes(n)) return PCP_ERR_WORKSPACE;
-    if (n > 0 && points == out) return PCP_ERR_ARG;
-    if (pcp_zero_async(frame_count, (size_t)aug->batch * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
-  }
-  if (n == 0) return PCP_OK;
-  if (!points || !out) return PCP_ERR_ARG;
+  int st = aug_points_shape(n, row_stride);
+  if (st == PCP_OK) st = aug_points_buffers(points, n, out, aug->filter != 0, aug->batch, frame_count, workspace, workspace_bytes, stream);
+  if (st != PCP_OK || n == 0) return st;
   const int tiles = (int)((n + PCP_AUG_TILE_ROWS - 1) / PCP_AUG_TILE_ROWS);
   const size_t tile_bytes = (size_t)PCP_AUG_TILE_ROWS * row_stride * 4;
   if (aug->filter) {

@@ -21,6 +21,7 @@
 
 namespace {
 
+#include "aug_tile.h"
 #include "bev_geom.h"
 
 constexpr int GTS_THREADS = 256;
@@ -223,13 +224,8 @@ __global__ __launch_bounds__(GTS_THREADS) void k_gts_paste(const float *__restri
     r += len;
   }
   __syncthreads();
-  const int count = (int)(r - o0) * S;                                // r <= total output rows: the stores stay inside them
-  float *dst = out + o0 * S;                                          // 16-byte aligned: PCP_AUG_TILE_ROWS * 4 * S bytes per tile
-  const int n4 = count >> 2;
-  f32x4 *d4 = reinterpret_cast<f32x4 *>(dst);
-  const f32x4 *t4 = reinterpret_cast<const f32x4 *>(tile);
-  for (int i = threadIdx.x; i < n4; i += GTS_THREADS) d4[i] = t4[i];
-  for (int i = (n4 << 2) + threadIdx.x; i < count; i += GTS_THREADS) dst[i] = tile[i];
+  // r <= total output rows: the stores stay inside them; out + o0 * S is 16-byte aligned (PCP_AUG_TILE_ROWS * 4 * S bytes per tile)
+  aug_stage_out<GTS_THREADS>(out + o0 * S, tile, 0, (int)(r - o0) * S);
 }
 
 // The plain form of the same paste (option PCP_OPT_GTS_PASTE_FORM = 1; tools/bench_augment.py --gt-sampling times both): one thread per
@@ -317,7 +313,7 @@ __global__ __launch_bounds__(256) void k_gts_boxes(const float *__restrict__ gt_
     const float *s = db_tf + ((size_t)a[1] * n_sweeps + (k - 1)) * 16;   // the first R rows of the stored 4 x 4
     for (int c = 0; c < R * 4; c++) o[c] = s[c];
   } else {
-    for (int c = 0; c < R * 4; c++) o[c] = (c >> 2) == (c & 3) && (c >> 2) < 3 ? 1.f : 0.f;   // collate_batch's padding: identity 3 x 3
+    for (int c = 0; c < R * 4; c++) o[c] = aug_identity_pad(c);
   }
 }
 

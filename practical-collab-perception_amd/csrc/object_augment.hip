@@ -17,6 +17,8 @@
 
 namespace {
 
+#include "aug_tile.h"
+
 constexpr int OBJ_THREADS = 256;
 constexpr int OBJ_ITEMS = PCP_AUG_TILE_ROWS / OBJ_THREADS;
 constexpr int OBJ_WAVES = OBJ_THREADS / PCP_WAVE;
@@ -30,7 +32,6 @@ static_assert(2 * (PCP_AUG_TILE_ROWS * PCP_AUG_MAX_ROW_STRIDE + 4) * 4 + OBJ_STA
 static_assert(SS % 4 == 0, "a box record is whole 16-byte words");
 static_assert(PCP_AUG_MAX_BATCH <= 64, "the frames of a tile are one 64-bit mask");
 
-constexpr float OBJ_2PI = 6.28318548202514648f;                  // float32(2 * np.pi)
 constexpr float OBJ_MARGIN = 0.1f;                               // get_points_in_box MARGIN, as float32
 
 __device__ __forceinline__ bool obj_is_drop(int st) { return st >= PCP_OBJ_DROP_TOP; }
@@ -68,26 +69,6 @@ __device__ __forceinline__ void obj_apply(int st, const float *s, ObjRow &r) {
     case PCP_OBJ_DROP_RIGHT: r.dead = r.y <= s[8]; break;
     default: break;
   }
-}
-
-// `count` floats from src (16-byte aligned) into LDS: 16-byte loads, the last count % 4 floats one by one
-__device__ __forceinline__ void obj_stage_in(float *lds, const float *__restrict__ src, int count) {
-  const int n4 = count >> 2;
-  const f32x4 *s4 = reinterpret_cast<const f32x4 *>(src);
-  f32x4 *d4 = reinterpret_cast<f32x4 *>(lds);
-  for (int i = threadIdx.x; i < n4; i += OBJ_THREADS) d4[i] = s4[i];
-  for (int i = (n4 << 2) + threadIdx.x; i < count; i += OBJ_THREADS) lds[i] = src[i];
-}
-
-// LDS floats [lo, hi) to dst0[lo .. hi), dst0 16-byte aligned: 16-byte stores over the aligned middle, single floats at both ends
-__device__ __forceinline__ void obj_stage_out(float *__restrict__ dst0, const float *lds, int lo, int hi) {
-  int alo = (lo + 3) & ~3, ahi = hi & ~3;
-  if (alo > ahi) alo = ahi = hi;
-  for (int i = lo + threadIdx.x; i < alo; i += OBJ_THREADS) dst0[i] = lds[i];
-  f32x4 *d4 = reinterpret_cast<f32x4 *>(dst0);
-  const f32x4 *s4 = reinterpret_cast<const f32x4 *>(lds);
-  for (int i = (alo >> 2) + threadIdx.x; i < (ahi >> 2); i += OBJ_THREADS) d4[i] = s4[i];
-  for (int i = ahi + threadIdx.x; i < hi; i += OBJ_THREADS) dst0[i] = lds[i];
 }
 
 // the rows of this thread through every sub-stage.  Every loop bound is the same for the whole workgroup (the frame mask, the stage list,
@@ -138,7 +119,7 @@ __device__ __forceinline__ void obj_walk(const float *in, int rows, int S, const
       for (int c0 = 0; c0 < nb; c0 += PCP_OBJ_LDS_BOXES) {
         const int cnt = min(PCP_OBJ_LDS_BOXES, nb - c0);
         __syncthreads();                                         // the previous chunk has been read by every thread
-        obj_stage_in(sbox, src + (size_t)c0 * SS, cnt * SS);
+        aug_stage_in<OBJ_THREADS>(sbox, src + (size_t)c0 * SS, cnt * SS);
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < OBJ_ITEMS; it++)
@@ -167,14 +148,11 @@ __global__ __launch_bounds__(OBJ_THREADS) void k_obj_points(const float *__restr
   const long long base = (long long)blockIdx.x * PCP_AUG_TILE_ROWS;
   const int rows = (int)((n - base) < PCP_AUG_TILE_ROWS ? (n - base) : PCP_AUG_TILE_ROWS);
   if (!PLACE && threadIdx.x <= PCP_AUG_MAX_BATCH) s_frame[threadIdx.x] = 0;
-  obj_stage_in(in, points + base * S, rows * S);
-  long long before = 0;
-  if (PLACE && compact)
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += OBJ_THREADS) before += tile_cnt[i];
+  aug_stage_in<OBJ_THREADS>(in, points + base * S, rows * S);
+  const long long before = PLACE && compact ? aug_tile_before<OBJ_THREADS>(tile_cnt) : 0;
   __syncthreads();
   ObjRow r[OBJ_ITEMS];
   obj_walk(in, rows, S, a, states, n_boxes, M, frame_thr, sbox, &s_mask, r);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   bool keep[OBJ_ITEMS];
   int rank[OBJ_ITEMS];
 #pragma unroll
@@ -188,62 +166,19 @@ __global__ __launch_bounds__(OBJ_THREADS) void k_obj_points(const float *__restr
       row[3] = r[it].z;
     }
     if (!PLACE && keep[it]) atomicAdd(&s_frame[r[it].frame >= 0 ? r[it].frame : a.batch], 1);
-    const unsigned long long bal = __ballot(keep[it]);
-    rank[it] = __popcll(bal & ((1ULL << lane) - 1ULL));
-    if (lane == 0) s_wave[it][wave] = __popcll(bal);
+    rank[it] = aug_tile_rank<OBJ_THREADS>(keep[it], it, s_wave);
   }
   if (!PLACE) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int tot = 0;
-#pragma unroll
-      for (int it = 0; it < OBJ_ITEMS; it++)
-#pragma unroll
-        for (int w = 0; w < OBJ_WAVES; w++) tot += s_wave[it][w];
-      tile_cnt[blockIdx.x] = tot;
-    }
-    if ((int)threadIdx.x <= a.batch && s_frame[threadIdx.x]) atomicAdd(&frame_count[threadIdx.x], s_frame[threadIdx.x]);
+    aug_tile_count_finish<OBJ_THREADS>(s_wave, s_frame, a.batch + 1, tile_cnt, frame_count);
     return;
   }
   if (!compact) {                                                // same place, same alignment: the tile goes back as it came
     __syncthreads();
-    obj_stage_out(out + base * S, in, 0, rows * S);
+    aug_stage_out<OBJ_THREADS>(out + base * S, in, 0, rows * S);
     return;
   }
   float *ob = in + PCP_AUG_TILE_ROWS * S;                        // second buffer: 4 floats longer than a tile
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
-  if (lane == 0) s_before[wave] = before;
-  __syncthreads();
-  before = 0;
-#pragma unroll
-  for (int w = 0; w < OBJ_WAVES; w++) before += s_before[w];
-  __syncthreads();                                               // every thread has read s_before before thread 0 reuses its first entry
-  if (threadIdx.x == 0) {                                        // exclusive prefix in input order: items, then waves, then lanes
-    int run = 0;
-#pragma unroll
-    for (int it = 0; it < OBJ_ITEMS; it++)
-#pragma unroll
-      for (int w = 0; w < OBJ_WAVES; w++) {
-        const int c = s_wave[it][w];
-        s_wave[it][w] = run;
-        run += c;
-      }
-    s_before[0] = run;
-  }
-  __syncthreads();
-  const int kept = (int)s_before[0];
-  const int pad = (int)((before * S) & 3);                       // destination float index modulo 4
-#pragma unroll
-  for (int it = 0; it < OBJ_ITEMS; it++)
-    if (keep[it]) {
-      const float *row = in + (it * OBJ_THREADS + threadIdx.x) * S;
-      float *dst = ob + pad + (s_wave[it][wave] + rank[it]) * S;
-      for (int c = 0; c < S; c++) dst[c] = row[c];
-    }
-  __syncthreads();
-  // before + kept <= rows in front of and inside this tile <= n: the stores stay inside the n rows of `out`
-  obj_stage_out(out + before * S - pad, ob, pad, pad + kept * S);
+  aug_tile_compact<OBJ_THREADS>(before, keep, rank, in, ob, S, s_wave, s_before, out);
 }
 
 // one workgroup per frame, a thread per box row: the box through every sub-stage, its record written in front of each
@@ -291,7 +226,7 @@ __global__ __launch_bounds__(256) void k_obj_boxes(pcp_object_aug_t a, const flo
       else if (st == PCP_OBJ_ROTATE) h = __fadd_rn(h, p[0]);
     }
     if (!real) continue;
-    if (a.limit_heading) h = __fsub_rn(h, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(h, OBJ_2PI), 0.5f)), OBJ_2PI));
+    if (a.limit_heading) h = aug_limit_period(h);
     for (int i = 0; i < 3; i++) {
       box[i] = c[i];
       box[3 + i] = d[i];
@@ -416,7 +351,7 @@ __global__ __launch_bounds__(256) void k_obj_drop_boxes(const float *__restrict_
   for (int i = threadIdx.x; i < M * per; i += 256) {
     const int m = i / per, d = s_dst[m], c = (i - m * per) % (R * 4);
     if (d >= 0) to[d * per + (i - m * per)] = t[i];
-    if (m >= kept) to[i] = (c >> 2) == (c & 3) && (c >> 2) < 3 ? 1.f : 0.f;   // collate_batch's padding: identity 3 x 3
+    if (m >= kept) to[i] = aug_identity_pad(c);
   }
 }
 
@@ -446,18 +381,16 @@ extern "C" int pcp_object_augment_boxes(const pcp_object_aug_t *aug, const float
 }
 
 extern "C" size_t pcp_object_augment_points_workspace_bytes(int64_t n) {
-  if (n < 0) return 0;
-  const int64_t tiles = (n + PCP_AUG_TILE_ROWS - 1) / PCP_AUG_TILE_ROWS;
-  return pcp_align_up((size_t)(tiles > 0 ? tiles : 1) * 4, 256);
+  return aug_points_workspace_bytes(n);
 }
 
 extern "C" int pcp_object_augment_points(const pcp_object_aug_t *aug, const float *box_states, const int32_t *n_boxes, int32_t max_boxes,
                                          const float *frame_thr, const float *points, int64_t n, int32_t row_stride, float *out,
                                          int32_t *frame_count, void *workspace, size_t workspace_bytes, void *stream_) {
-  if (!obj_ok(aug, true) || n < 0 || max_boxes < 0 || row_stride < PCP_AUG_MIN_ROW_STRIDE || row_stride > PCP_AUG_MAX_ROW_STRIDE)
-    return PCP_ERR_ARG;
+  if (!obj_ok(aug, true) || max_boxes < 0) return PCP_ERR_ARG;
+  int st = aug_points_shape(n, row_stride);
+  if (st != PCP_OK) return st;
   if (max_boxes > PCP_OBJ_MAX_BOXES) return PCP_ERR_UNSUPPORTED;
-  if (n * row_stride >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;       // LDS and tile indices are ints
   bool drop = false, world = false, local = false;
   for (int k = 0; k < aug->n_stages; k++) {
     drop |= aug->stage[k] >= PCP_OBJ_DROP_TOP;
@@ -466,16 +399,10 @@ extern "C" int pcp_object_augment_points(const pcp_object_aug_t *aug, const floa
   }
   if (world && !frame_thr) return PCP_ERR_ARG;
   if (local && max_boxes > 0 && (!box_states || !n_boxes)) return PCP_ERR_ARG;
-  if ((((uintptr_t)points) | ((uintptr_t)out) | ((uintptr_t)box_states)) & 15) return PCP_ERR_ARG;
+  if (((uintptr_t)box_states) & 15) return PCP_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  if (drop) {
-    if (!frame_count || !workspace || (((uintptr_t)frame_count) & 3)) return PCP_ERR_ARG;
-    if (workspace_bytes < pcp_object_augment_points_workspace_bytes(n)) return PCP_ERR_WORKSPACE;
-    if (n > 0 && points == out) return PCP_ERR_ARG;
-    if (pcp_zero_async(frame_count, (size_t)(aug->batch + 1) * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
-  }
-  if (n == 0) return PCP_OK;
-  if (!points || !out) return PCP_ERR_ARG;
+  st = aug_points_buffers(points, n, out, drop, aug->batch + 1, frame_count, workspace, workspace_bytes, stream);
+  if (st != PCP_OK || n == 0) return st;
   const int M = local ? (int)max_boxes : 0;                            // no box is read by a world dropout
   const int tiles = (int)((n + PCP_AUG_TILE_ROWS - 1) / PCP_AUG_TILE_ROWS);
   const size_t tile_bytes = (size_t)PCP_AUG_TILE_ROWS * row_stride * 4;

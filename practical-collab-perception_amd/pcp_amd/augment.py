@@ -10,7 +10,8 @@ is collated and on the GPU already, so DeviceWorldAugmentor
     skipped with one logged line; object_stages=True also takes the per-object entries (random_local_translation / _rotation / _scaling,
     random_local_frustum_dropout, random_world_frustum_dropout: pcp_amd/object_augment.py) in list order;
   * draw(): draws, frame by frame, exactly the numpy calls the reference makes for consecutive samples;
-  * apply(): two launches on the current stream (points; gt_boxes + instances_tf) and the float64 se3_from_ego update on the host.
+  * apply(): the launches of self.steps on the current stream (a list of world transforms is one step of two launches: points; gt_boxes +
+    instances_tf) and the float64 se3_from_ego update on the host.
 
 There is no CPU path: apply() needs CUDA tensors.
 """
@@ -23,20 +24,13 @@ import torch
 
 from . import lib as _lib
 from . import object_augment as _obj
+from .aug_common import BOX_WIDTHS, _get, check_instances_tf, check_rows, points_call
 from .lib import check
 from .ops import _need_cuda, _p, _stream
 
 WORLD_TRANSFORMS = ('random_world_flip', 'random_world_rotation', 'random_world_scaling', 'random_world_translation')
 RANGE_FILTER = 'mask_points_and_boxes_outside_range'
 GT_SAMPLING = 'gt_sampling'
-BOX_WIDTHS = (8, 10)                 # [x y z dx dy dz heading class] / [.. heading vx vy class]
-TF_ROWS = (3, 4)                     # instances_tf (B, M, S, 3 | 4, 4)
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
 
 
 def rotation_cos_sin(noise_rot):
@@ -144,12 +138,15 @@ class DeviceWorldAugmentor:
                  'random_world_translation': _lib.AUG_TRANSLATE}[name]]
 
     def _plan(self):
-        """with object stages: the launches in list order.  self.steps: dicts(kind 'gt' | 'world' | 'local' | 'wdrop', q: queue indices,
-        stages).  Consecutive world entries share one call of the world kernels, consecutive local entries one of the object kernels.
-        self.splits: queue indices in front of which the per-frame box counts must be read back before the draws go on, i.e. the first
-        object entry behind an enabled gt_sampling or a world frustum dropout."""
+        """the launches in list order.  self.steps: dicts(kind 'gt' | 'world' | 'local' | 'wdrop', q: queue indices, stages).  Consecutive
+        world entries share one call of the world kernels, consecutive local entries one of the object kernels.  self.splits: queue
+        indices in front of which the per-frame box counts must be read back before the draws go on, i.e. the first object entry behind
+        an enabled gt_sampling or a world frustum dropout."""
         self.steps, self.splits = [], []
-        if not self.has_object_stages:
+        if not self.has_object_stages:                  # the paste, then every world entry in one call of the world kernels
+            world = [qi for qi, (name, _) in enumerate(self.queue) if name != GT_SAMPLING]
+            self.steps = [{'kind': 'gt', 'q': [qi], 'stages': []} for qi in range(len(self.queue)) if qi not in world]
+            self.steps.append({'kind': 'world', 'q': world, 'stages': list(self.stages)})
             return
         changed = False                                 # a device stage has changed the box counts since the last read
         for qi, (name, cur) in enumerate(self.queue):
@@ -278,34 +275,13 @@ class DeviceWorldAugmentor:
         """points (N, 1 + C) float32 CUDA -> (rows, per-frame kept counts as a numpy array or None).  Filter on: a new tensor holding the
         kept rows in input order (one host read of 4 B bytes); filter off: a new tensor of all N rows, nothing read back."""
         _need_cuda(points, table_dev)
-        if points.dim() != 2 or not _lib.AUG_MIN_ROW_STRIDE <= points.shape[1] <= _lib.AUG_MAX_ROW_STRIDE:
-            raise ValueError('points of shape %s: the augmentation kernel takes (N, 1 + C) rows of %d (frame index, x y z) up to %d columns'
-                             % (tuple(points.shape), _lib.AUG_MIN_ROW_STRIDE, _lib.AUG_MAX_ROW_STRIDE))
-        if points.dtype != torch.float32:
-            raise ValueError('points are %s: the augmentation kernel reads float32 rows' % points.dtype)
+        points = check_rows(points, batch_size, 'the augmentation kernel')
         if self.hd_map and points.shape[1] != 13:
             raise ValueError('HD-map rows have 1 + 12 columns, got %d' % points.shape[1])
-        if not 0 < batch_size <= _lib.AUG_MAX_BATCH:
-            raise ValueError('batch of %d frames: the augmentation kernels take 1 to %d' % (batch_size, _lib.AUG_MAX_BATCH))
         a = self.descriptor(batch_size, stages, filter)
         L = _lib.load()
-        points = points.contiguous()
-        if points.data_ptr() % 16:
-            points = points.clone()
-        n, stride = int(points.shape[0]), int(points.shape[1])
-        out = torch.empty_like(points)
-        counts = ws = None
-        ws_bytes = 0
-        if a.filter:
-            ws_bytes = int(L.pcp_world_augment_points_workspace_bytes(n))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=points.device)
-            counts = torch.empty(batch_size, dtype=torch.int32, device=points.device)
-        check(L.pcp_world_augment_points(ctypes.byref(a), _p(table_dev), _p(points), n, stride, _p(out), _p(counts), _p(ws), ws_bytes, _stream()),
-              'pcp_world_augment_points')
-        if not a.filter:
-            return out, None
-        kept = counts.cpu().numpy()
-        return out[:int(kept.sum())], kept
+        return points_call(L.pcp_world_augment_points, L.pcp_world_augment_points_workspace_bytes, (ctypes.byref(a), _p(table_dev)), points,
+                           batch_size if a.filter else 0)
 
     def augment_boxes(self, gt_boxes, instances_tf, table_dev, stages=None, raw_heading=False):
         """gt_boxes (B, M, 8 | 10), instances_tf (B, M, S, 3 | 4, 4) or None -> new tensors; one launch.  raw_heading: no limit_period at the
@@ -319,10 +295,7 @@ class DeviceWorldAugmentor:
             raise ValueError('batch of %d frames: the augmentation kernels take 1 to %d' % (B, _lib.AUG_MAX_BATCH))
         n_sweeps = tf_rows = 0
         if instances_tf is not None:
-            if instances_tf.dim() != 5 or tuple(instances_tf.shape[:2]) != (B, M) or instances_tf.shape[3] not in TF_ROWS or instances_tf.shape[4] != 4:
-                raise ValueError('instances_tf of shape %s: the augmentation kernel takes (B, M, S, R, 4) with R in %s and (B, M) = (%d, %d) '
-                                 'of gt_boxes' % (tuple(instances_tf.shape), TF_ROWS, B, M))
-            n_sweeps, tf_rows = int(instances_tf.shape[2]), int(instances_tf.shape[3])
+            n_sweeps, tf_rows = check_instances_tf(instances_tf, B, M)
             instances_tf = instances_tf.float().contiguous().clone()
         gt_boxes = gt_boxes.float().contiguous().clone()
         a = self.descriptor(B, stages, False, raw_heading)
@@ -338,43 +311,31 @@ class DeviceWorldAugmentor:
         assert len(params['flip_x']) == B, (len(params['flip_x']), B)
         if self.gt_sampler is not None:                      # the paste first: pasted points and boxes go through the transforms and the mask
             self.gt_sampler.apply(batch_dict, params['gt_sampled'])
-        points = batch_dict['points']
-        if self.has_object_stages:
-            self.check_plan(batch_dict, self.steps)
-        _need_cuda(points)
-        table_dev = torch.from_numpy(self.table(params)).to(points.device)
-        if self.has_object_stages:
-            self.run_steps(batch_dict, params, [s for s in self.steps if s['kind'] != 'gt'], table_dev)
-            return self._finish(batch_dict, params)
-        batch_dict['points'], kept = self.augment_points(points, table_dev, B)
-        if kept is not None:
-            batch_dict['aug_points_kept'] = kept
-        if batch_dict.get('gt_boxes', None) is not None:
-            batch_dict['gt_boxes'], tf = self.augment_boxes(batch_dict['gt_boxes'], batch_dict.get('instances_tf', None), table_dev)
-            if tf is not None:
-                batch_dict['instances_tf'] = tf
-        elif batch_dict.get('instances_tf', None) is not None:
-            raise ValueError('instances_tf without gt_boxes: the class column of gt_boxes tells the real objects from the padding')
+        self.run_steps(batch_dict, params, [s for s in self.steps if s['kind'] != 'gt'])
         return self._finish(batch_dict, params)
 
-    def run_steps(self, batch_dict, params, steps, table_dev=None):
+    def run_steps(self, batch_dict, params, steps):
         """the launches of `steps` (self.steps entries other than the paste) on batch_dict, in order"""
         B = int(batch_dict['batch_size'])
         self.check_plan(batch_dict, steps)
-        if table_dev is None:
-            table_dev = torch.from_numpy(self.table(params)).to(batch_dict['points'].device)
+        _need_cuda(batch_dict['points'])
+        table_dev = torch.from_numpy(self.table(params)).to(batch_dict['points'].device)
         for step in steps:
             final = step is self.steps[-1]
             if step['kind'] == 'world':
                 filt = self.filter and final
-                if step['stages'] or filt:
+                # a list without object stages always launches: the caller gets a new tensor, never its own
+                if step['stages'] or filt or not self.has_object_stages:
                     batch_dict['points'], kept = self.augment_points(batch_dict['points'], table_dev, B, stages=step['stages'], filter=filt)
                     if kept is not None:
                         batch_dict['aug_points_kept'] = kept
-                batch_dict['gt_boxes'], tf = self.augment_boxes(batch_dict['gt_boxes'], batch_dict.get('instances_tf', None), table_dev,
-                                                                stages=step['stages'], raw_heading=not final)
-                if tf is not None:
-                    batch_dict['instances_tf'] = tf
+                if batch_dict.get('gt_boxes', None) is not None:
+                    batch_dict['gt_boxes'], tf = self.augment_boxes(batch_dict['gt_boxes'], batch_dict.get('instances_tf', None), table_dev,
+                                                                    stages=step['stages'], raw_heading=not final)
+                    if tf is not None:
+                        batch_dict['instances_tf'] = tf
+                elif batch_dict.get('instances_tf', None) is not None:
+                    raise ValueError('instances_tf without gt_boxes: the class column of gt_boxes tells the real objects from the padding')
             elif step['kind'] == 'local':
                 if not step['stages']:
                     continue
@@ -402,7 +363,7 @@ class DeviceWorldAugmentor:
             raise ValueError('object stages need gt_boxes: they move the points inside each box')
         gt, pts = batch_dict['gt_boxes'], batch_dict['points']
         _obj._check_boxes(gt.float(), stages)                    # run_steps hands the boxes over as float32
-        _obj._check_points(pts, int(batch_dict['batch_size']))
+        check_rows(pts, int(batch_dict['batch_size']), _obj.WHAT)
 
     def _finish(self, batch_dict, params):
         if self.gt_sampler is not None or self.has_object_stages:
@@ -433,20 +394,18 @@ class DeviceWorldAugmentor:
     def __call__(self, batch_dict, rng=None):
         rng = self.rng if rng is None else rng
         classes = self.gt_sampler.frame_gt_classes(batch_dict['gt_boxes']) if self.gt_sampler is not None else None
-        if not self.has_object_stages:
-            return self.apply(batch_dict, self.draw(batch_dict['batch_size'], rng, classes))
         B = int(batch_dict['batch_size'])
-        n_boxes = [len(c) for c in classes] if classes is not None else self.box_counts(batch_dict)
-        if not self.splits:
-            return self.apply(batch_dict, self.draw(B, rng, classes, n_boxes))
-        # the box counts change on the device in the middle of the list: draw up to there, run, read the counts back (once per such place), go on
+        n_boxes = None
+        if self.has_object_stages:
+            n_boxes = [len(c) for c in classes] if classes is not None else self.box_counts(batch_dict)
+        # where the box counts change on the device in the middle of the list: draw up to there, run, read the counts back (once per such place), go on
         bounds = [0] + self.splits + [len(self.queue)]
         params = None
         for lo, hi in zip(bounds[:-1], bounds[1:]):
             if lo > 0:
                 batch_dict.pop('num_gt_boxes', None)
                 n_boxes = self.box_counts(batch_dict)
-            params = self.draw(B, rng, classes, n_boxes, entries=(lo, hi)) if params is None else self.draw(B, rng, classes, n_boxes, (lo, hi), params)
+            params = self.draw(B, rng, classes, n_boxes, (lo, hi), params)
             if lo == 0 and self.gt_sampler is not None:
                 self.gt_sampler.apply(batch_dict, params['gt_sampled'])
             steps = [s for s in self.steps if s['kind'] != 'gt' and (all(lo <= q < hi for q in s['q']) if s['q'] else hi == len(self.queue))]

@@ -20,16 +20,11 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .aug_common import _get
 from .lib import check
 from .ops import _need_cuda, _p, _stream
 
 REFUSED_KEYS = ('IMG_AUG_TYPE', 'USE_ROAD_PLANE', 'DATABASE_WITH_FAKELIDAR')
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
 
 
 class DeviceGtDatabase:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .aug_common import _get, check_instances_tf, check_rows, points_call
 from .lib import check
 from .ops import _need_cuda, _p, _stream
 
@@ -24,12 +25,7 @@ _TRANSLATE = {'x': _lib.OBJ_TRANSLATE_X, 'y': _lib.OBJ_TRANSLATE_Y, 'z': _lib.OB
 _LOCAL_DROP = dict(zip(DIRECTIONS, (_lib.OBJ_DROP_TOP, _lib.OBJ_DROP_BOTTOM, _lib.OBJ_DROP_LEFT, _lib.OBJ_DROP_RIGHT)))
 _WORLD_DROP = dict(zip(DIRECTIONS, (_lib.OBJ_WORLD_DROP_TOP, _lib.OBJ_WORLD_DROP_BOTTOM, _lib.OBJ_WORLD_DROP_LEFT, _lib.OBJ_WORLD_DROP_RIGHT)))
 _DROPS = set(_LOCAL_DROP.values()) | set(_WORLD_DROP.values())
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
+WHAT = 'the object augmentation'                        # how check_rows names this module in its refusals
 
 
 def sub_stages(name, cur):
@@ -97,20 +93,6 @@ def param_table(stages, values, max_boxes):
     return t
 
 
-def _check_points(points, batch_size):
-    if points.dim() != 2 or not _lib.AUG_MIN_ROW_STRIDE <= points.shape[1] <= _lib.AUG_MAX_ROW_STRIDE:
-        raise ValueError('points of shape %s: the object augmentation takes (N, 1 + C) rows of %d (frame index, x y z) up to %d columns'
-                         % (tuple(points.shape), _lib.AUG_MIN_ROW_STRIDE, _lib.AUG_MAX_ROW_STRIDE))
-    if points.dtype != torch.float32:
-        raise ValueError('points are %s: the object augmentation reads float32 rows' % points.dtype)
-    if not 0 < batch_size <= _lib.AUG_MAX_BATCH:
-        raise ValueError('batch of %d frames: the augmentation kernels take 1 to %d' % (batch_size, _lib.AUG_MAX_BATCH))
-    if not points.is_cuda:
-        return points                                   # the caller's _need_cuda refuses it once every argument has been looked at
-    points = points.contiguous()
-    return points.clone() if points.data_ptr() % 16 else points
-
-
 def _check_boxes(gt_boxes, stages=()):
     if gt_boxes.dim() != 3 or gt_boxes.shape[2] not in (8, 10):
         raise ValueError('gt_boxes of shape %s: the object augmentation takes (B, M, 8 | 10)' % (tuple(gt_boxes.shape),))
@@ -126,22 +108,12 @@ def _check_boxes(gt_boxes, stages=()):
 
 def _points_call(a, states, n_boxes, max_boxes, frame_thr, points):
     """-> (rows, per-frame kept counts as numpy or None)"""
-    L = _lib.load()
-    n, stride = int(points.shape[0]), int(points.shape[1])
-    out = torch.empty_like(points)
     drop = any(a.stage[i] in _DROPS for i in range(a.n_stages))
-    counts = ws = None
-    ws_bytes = 0
-    if drop:
-        ws_bytes = int(L.pcp_object_augment_points_workspace_bytes(n))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=points.device)
-        counts = torch.empty(a.batch + 1, dtype=torch.int32, device=points.device)    # [batch]: rows of a frame outside [0, batch), kept
-    check(L.pcp_object_augment_points(ctypes.byref(a), _p(states), _p(n_boxes), int(max_boxes), _p(frame_thr), _p(points), n, stride, _p(out),
-                                      _p(counts), _p(ws), ws_bytes, _stream()), 'pcp_object_augment_points')
-    if not drop:
-        return out, None
-    kept = counts.cpu().numpy()
-    return out[:int(kept.sum())], kept[:a.batch]
+    head = (ctypes.byref(a), _p(states), _p(n_boxes), int(max_boxes), _p(frame_thr))
+    L = _lib.load()
+    # counter [batch]: rows of a frame outside [0, batch), kept
+    out, kept = points_call(L.pcp_object_augment_points, L.pcp_object_augment_points_workspace_bytes, head, points, a.batch + 1 if drop else 0)
+    return out, None if kept is None else kept[:a.batch]
 
 
 def local_stages(points, gt_boxes, stages, values, limit_heading=False):
@@ -149,7 +121,7 @@ def local_stages(points, gt_boxes, stages, values, limit_heading=False):
     (n_sub, n_b) array.  -> (points, gt_boxes, per-frame kept counts or None): new tensors, the inputs are not written."""
     _check_boxes(gt_boxes, stages)
     B, M, W = (int(v) for v in gt_boxes.shape)
-    points = _check_points(points, B)
+    points = check_rows(points, B, WHAT)
     _need_cuda(points, gt_boxes)
     if len(values) != B:
         raise ValueError('parameters for %d frames, gt_boxes has %d' % (len(values), B))
@@ -167,7 +139,7 @@ def local_stages(points, gt_boxes, stages, values, limit_heading=False):
 
 def frame_extent(points, batch_size, col):
     """(B, 2) float32 CUDA: min, max of column `col` per frame; +inf, -inf for a frame without rows"""
-    points = _check_points(points, batch_size)
+    points = check_rows(points, batch_size, WHAT)
     _need_cuda(points)
     L = _lib.load()
     n = int(points.shape[0])
@@ -183,7 +155,7 @@ def world_dropout(points, gt_boxes, instances_tf, direction, intensity):
     -> (points, gt_boxes, instances_tf, per-frame kept rows, per-frame box counts as a CUDA int32 tensor)"""
     _check_boxes(gt_boxes)
     B, M, W = (int(v) for v in gt_boxes.shape)
-    points = _check_points(points, B)
+    points = check_rows(points, B, WHAT)
     _need_cuda(points, gt_boxes)
     dev = points.device
     col = 3 if direction in (_lib.OBJ_WORLD_DROP_TOP, _lib.OBJ_WORLD_DROP_BOTTOM) else 2
@@ -197,10 +169,8 @@ def world_dropout(points, gt_boxes, instances_tf, direction, intensity):
     tf_out = None
     if instances_tf is not None:
         _need_cuda(instances_tf)
-        if instances_tf.dim() != 5 or tuple(instances_tf.shape[:2]) != (B, M) or instances_tf.shape[3] not in (3, 4) or instances_tf.shape[4] != 4:
-            raise ValueError('instances_tf of shape %s: expected (%d, %d, S, 3 | 4, 4)' % (tuple(instances_tf.shape), B, M))
+        n_sweeps, tf_rows = check_instances_tf(instances_tf, B, M)
         instances_tf = instances_tf.float().contiguous()
-        n_sweeps, tf_rows = int(instances_tf.shape[2]), int(instances_tf.shape[3])
         tf_out = torch.empty_like(instances_tf) if n_sweeps > 0 else instances_tf
     check(_lib.load().pcp_object_augment_drop_boxes(_p(gt_boxes), B, M, W, _p(instances_tf) if n_sweeps else None, n_sweeps, tf_rows, _p(extent),
                                                     _p(inten), int(direction), _p(thr), _p(gt_out), _p(tf_out) if n_sweeps else None,

@@ -30,7 +30,8 @@ def test_default_still_skips_and_opt_in_queues(caplog):
     cfg = META['cases']['full']['cfg'] + [{'NAME': 'random_local_pyramid_aug'}, {'NAME': 'random_image_flip'}]
     with caplog.at_level(logging.INFO):
         off = DeviceWorldAugmentor(cfg, META['pc_range'])
-    assert [n for n, _ in off.queue] == ['random_world_rotation', 'random_world_flip'] and not off.has_object_stages and off.steps == []
+    assert [n for n, _ in off.queue] == ['random_world_rotation', 'random_world_flip'] and not off.has_object_stages
+    assert off.steps == [{'kind': 'world', 'q': [0, 1], 'stages': off.stages}]          # one world step carrying every stage
     assert set(off.skipped) == set(oar.OBJECT_NAMES) | {'random_local_pyramid_aug', 'random_image_flip'}
     assert sum('skipped' in r.message for r in caplog.records) == len(off.skipped)
     on = DeviceWorldAugmentor(cfg, META['pc_range'], object_stages=True)
@@ -40,7 +41,7 @@ def test_default_still_skips_and_opt_in_queues(caplog):
     assert on.steps[1]['stages'] == [1, 2, 3, 5, 4, 6, 8] and on.steps[2]['stages'] == [11, 13]
     # without object entries in the list the switch changes nothing
     a, b = DeviceWorldAugmentor(cfg[:1] + cfg[-3:-2], META['pc_range']), DeviceWorldAugmentor(cfg[:1] + cfg[-3:-2], META['pc_range'], object_stages=True)
-    assert a.queue == b.queue and a.stages == b.stages and b.steps == []
+    assert a.queue == b.queue and a.stages == b.stages and a.steps == b.steps and [s['kind'] for s in b.steps] == ['world']
     pa, pb = a.draw(3, np.random.RandomState(4)), b.draw(3, np.random.RandomState(4))
     assert all(np.array_equal(pa[k], pb[k]) for k in pa) and set(pa) == set(pb)
 
