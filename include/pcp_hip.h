@@ -615,6 +615,45 @@ typedef struct {
 int pcp_gather_detections_ext(const pcp_det_head_ext_t *heads, int32_t n_heads, int32_t batch, int32_t out_max, float *out_boxes,
                               float *out_scores, int64_t *out_labels, int32_t *out_count, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Detection evaluation by the nuScenes protocol (csrc/det_eval.hip; host side pcp_amd/det_eval.py).
+ * Replaces: the matching and curve arithmetic nuscenes-devkit does on the host behind pcdet/datasets/v2x_sim/v2x_sim_eval_utils.py
+ *           and pcdet/datasets/nuscenes/nuscenes_eval_utils.py (greedy centre-distance matching per class, 101-point curves).
+ *
+ * The match entry: one workgroup per (frame, class) and one wave per distance threshold.  boxes (B, K, box_width 7 | 9) float32
+ * [x y z dx dy dz heading (vx vy)], scores (B, K), labels (B, K) int64 in 1 .. n_classes, count (B,): only the first count[b] slots of a
+ * frame are read.  gt_boxes (B, M, gt_width 8 | 10), class in the last column, 0 = padding.  At most PCP_EVAL_MAX_BOXES predictions and
+ * as many ground-truth rows per (frame, class): the host refuses more (the kernel would pass over the surplus).  dist_ths: the
+ * PCP_EVAL_THRESHOLDS distances as host values; tp_index names the one whose errors are recorded.  orient_period (n_classes,) float32 and
+ * class_flags (n_classes,) int32 (PCP_EVAL_NAN_ORIENT | PCP_EVAL_NAN_VEL) are device arrays.
+ * records: PCP_EVAL_RECORD_WORDS 32-bit words per slot, the one of prediction k of frame b at slot (frame_base + b) * K + k:
+ *   [score f32 | class i32 (0: no prediction in this slot) | TP mask i32, bit t = threshold t | gt row matched at tp_index, -1 = none |
+ *    trans_err | scale_err | orient_err | vel_err] (float32, 0 without a match at tp_index).
+ * gt_count[(frame_base + b) * n_classes + c - 1]: ground-truth rows of class c in the frame.  Every word of both ranges is written by
+ * plain 16- and 4-byte stores; a call repeats bit for bit.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_EVAL_MAX_BOXES 512
+#define PCP_EVAL_THRESHOLDS 4
+#define PCP_EVAL_RECORD_WORDS 8
+#define PCP_EVAL_POINTS 101
+#define PCP_EVAL_NAN_ORIENT 1
+#define PCP_EVAL_NAN_VEL 2
+int pcp_det_eval_match(const float *boxes, const float *scores, const int64_t *labels, const int32_t *count, int32_t batch, int32_t k,
+                       int32_t box_width, const float *gt_boxes, int32_t m, int32_t gt_width, int32_t n_classes, const float *dist_ths_host,
+                       int32_t tp_index, const float *orient_period, const int32_t *class_flags, int64_t frame_base, void *records,
+                       int32_t *gt_count, void *stream);
+
+/* The curve entry: one workgroup per (class, threshold) over an epoch's records.  sorted: n records ordered by class ascending, inside a
+ * class by score descending (ties: the lower slot); class_start (n_classes + 2,) int32: first record of class c at [c], c = 0 .. n_classes
+ * + 1 (class 0 = empty slots); npos (n_classes,) int32; rec_interp (PCP_EVAL_POINTS,) float64 recall grid.  workspace_bytes:
+ * the byte count the match list and the running TP counts need for n records.  out (n_classes, pcp_det_eval_curves_stride()) float64 per
+ * class: precision [4][101] | confidence [4][101] | trans, scale, orient, vel error curves [4][101] at tp_index | npos | TP count [4] |
+ * predictions | 0 | 0.  All float64 arithmetic, evaluated as numpy.interp evaluates it. */
+size_t pcp_det_eval_curves_workspace_bytes(int64_t n);
+int32_t pcp_det_eval_curves_stride(void);
+int pcp_det_eval_curves(const void *sorted, int64_t n, const int32_t *class_start, const int32_t *npos, int32_t n_classes, int32_t tp_index,
+                        const double *rec_interp, void *workspace, size_t workspace_bytes, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

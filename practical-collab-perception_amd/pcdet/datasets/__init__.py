@@ -37,6 +37,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
             self.points_per_agent = int(syn.get('POINTS_PER_FRAME', self.points_per_agent))   # the nuScenes configs size the frame
         self.xy_half = float(syn.get('XY_HALF', 52.0))
         self.gt_boxes_max = int(syn.get('GT_BOXES', 40))      # boxes of a training frame before the index-dependent cut
+        self.eval_gt = bool(syn.get('EVAL_GT', False))        # evaluation items carry gt_boxes too (pcp_amd/det_eval.py scores against them)
 
     @property
     def mode(self):
@@ -83,6 +84,9 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
                 # configs 1 / 2 train HunterJr: foreground points carry (sweep, instance) and every instance its per-sweep motion
                 fg, item['instances_tf'] = self.synthetic_foreground(index, item['gt_boxes'])
                 item['points'] = np.concatenate([item['points'], fg], 0)
+        elif self.eval_gt:
+            # the boxes a training item of this index carries; without EVAL_GT an evaluation item keeps its keys (and its batch its bytes)
+            item['gt_boxes'] = self.synthetic_gt_boxes_velocity(index) if self.layout == 'nusc_map' else self.synthetic_gt_boxes(index)
         return item
 
     def synthetic_foreground(self, index, gt, n_sweeps=11, per_local=12):
@@ -165,6 +169,15 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
 
     def evaluation(self, det_annos, class_names, **kwargs):
         n = sum(len(a['score']) for a in det_annos)
+        if kwargs.get('device_eval', None) is not None:
+            # (metrics, text) of pcp_amd.det_eval.DeviceDetectionEval.result(): the nuScenes-protocol report against the synthetic boxes
+            metrics, text = kwargs['device_eval']
+            out = {'num_detections': n, 'mAP': metrics['mean_ap']}
+            out.update(metrics['tp_errors'])
+            if 'nd_score' in metrics:
+                out['NDS'] = metrics['nd_score']
+            out['metrics'] = metrics
+            return text + 'mAP line: mean_ap %.6f over %d detections, %d frames\n' % (metrics['mean_ap'], n, len(det_annos)), out
         return 'synthetic data: %d detections over %d frames (no ground truth, no mAP)\n' % (n, len(det_annos)), {'num_detections': n}
 
 

@@ -157,6 +157,9 @@ AUG_MIN_ROW_STRIDE, AUG_MAX_ROW_STRIDE, AUG_TILE_ROWS = 4, 15, 512
 GTS_MAX_GROUPS, GTS_MAX_CAND, GTS_MAX_BOXES, GTS_CAND_STRIDE, GTS_ACC_STRIDE = 16, 64, 512, 10, 4      # PCP_GTS_* (include/pcp_hip_train.h)
 
 
+EVAL_MAX_BOXES, EVAL_THRESHOLDS, EVAL_RECORD_WORDS, EVAL_POINTS, EVAL_NAN_ORIENT, EVAL_NAN_VEL = 512, 4, 8, 101, 1, 2     # PCP_EVAL_* (include/pcp_hip.h)
+
+
 class WorldAug(ctypes.Structure):
     """pcp_world_aug_t (include/pcp_hip_train.h)"""
     _fields_ = [('n_stages', c_i32), ('stage', c_i32 * AUG_MAX_STAGES), ('batch', c_i32), ('hd_map', c_i32), ('filter', c_i32),
@@ -292,6 +295,10 @@ SYMBOLS = {
     'pcp_modar_ingest_batched_workspace_bytes': (c_sz, [c_i32, c_i64]),
     'pcp_modar_ingest_batched': (c_i32, [vp, vp, vp, vp, c_i32, c_i32, vp, c_i32, vp, vp, c_i64, vp, vp, vp, vp, c_sz, vp, vp]),
     'pcp_modar_ingest': (c_i32, [vp, c_i32, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), c_f, vp, vp]),
+    'pcp_det_eval_match': (c_i32, [vp, vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_f), c_i32, vp, vp, c_i64, vp, vp, vp]),
+    'pcp_det_eval_curves_workspace_bytes': (c_sz, [c_i64]),
+    'pcp_det_eval_curves_stride': (c_i32, []),
+    'pcp_det_eval_curves': (c_i32, [vp, c_i64, vp, vp, c_i32, c_i32, vp, vp, c_sz, vp, vp]),
 }
 
 # include/pcp_hip_train.h

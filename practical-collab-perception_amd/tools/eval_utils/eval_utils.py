@@ -27,6 +27,19 @@ def eval_one_epoch(cfg, args, model, dataloader, epoch_id, logger, dist_test=Fal
             # device-side data refreshed per batch, so one capture per (batch size, set of agents) serves the whole epoch
             pipe = PipelinedDetector(model, replicas=2, graph=capacity > 0)
             padded = PaddedPoints(capacity) if capacity > 0 else None
+    # --device_eval: detections scored against the batch's gt_boxes where both lie (pcp_amd/det_eval.py: nuScenes-protocol mAP and TP
+    # errors); the evaluator is built on the first batch that carries gt_boxes and fed the device tensors of both loops below
+    dev_eval = None
+
+    def score(batch, preds):
+        nonlocal dev_eval
+        if not getattr(args, 'device_eval', False) or 'gt_boxes' not in batch:
+            return
+        if dev_eval is None:
+            from pcp_amd.det_eval import DeviceDetectionEval
+            dev_eval = DeviceDetectionEval(class_names, capacity_frames=max(len(dataset), 1))
+        dev_eval.add(preds, batch['gt_boxes'], frame_ids=batch.get('frame_id', None))
+
     for batch_dict in dataloader:
         load_data_to_gpu(batch_dict)
         if pipe is not None:
@@ -39,6 +52,7 @@ def eval_one_epoch(cfg, args, model, dataloader, epoch_id, logger, dist_test=Fal
                 pts = padded.fill(pts)
             prev = pipe.submit(pts, batch_dict['batch_size'], batch_dict.get('metadata', None), extra=batch_dict)
             if prev is not None:
+                score(waiting, prev)
                 det_annos += dataset.generate_prediction_dicts(waiting, prev, class_names)
             waiting = batch_dict
             continue
@@ -50,9 +64,12 @@ def eval_one_epoch(cfg, args, model, dataloader, epoch_id, logger, dist_test=Fal
         if getattr(args, 'infer_time', False):
             torch.cuda.synchronize()
             infer_meter.update((time.time() - t0) * 1000)
+        score(batch_dict, pred_dicts)
         det_annos += dataset.generate_prediction_dicts(batch_dict, pred_dicts, class_names)
     if pipe is not None and waiting is not None:
-        det_annos += dataset.generate_prediction_dicts(waiting, pipe.flush(), class_names)
+        last = pipe.flush()
+        score(waiting, last)
+        det_annos += dataset.generate_prediction_dicts(waiting, last, class_names)
     if dist_test:
         det_annos = common_utils.merge_results_dist(det_annos, len(dataset))
     rank, _ = common_utils.get_dist_info()
@@ -63,7 +80,10 @@ def eval_one_epoch(cfg, args, model, dataloader, epoch_id, logger, dist_test=Fal
     logger.info('Generate label finished (sec_per_example: %.4f second).' % (sec / max(len(dataset), 1)))
     if getattr(args, 'infer_time', False):
         logger.info('Average infer time per batch: %.3f ms' % infer_meter.avg)
-    result_str, result_dict = dataset.evaluation(det_annos, class_names)
+    if dev_eval is not None:
+        result_str, result_dict = dataset.evaluation(det_annos, class_names, device_eval=dev_eval.result())
+    else:
+        result_str, result_dict = dataset.evaluation(det_annos, class_names)
     logger.info(result_str)
     result_dict['infer_time_ms'] = infer_meter.avg
     return result_dict

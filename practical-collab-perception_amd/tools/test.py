@@ -41,9 +41,15 @@ def parse_config():
     p.add_argument('--fast_capacity', type=int, default=0, help='with --fast: pad every batch to this many rows (frame index -1 behind the real '
                    'ones) and replay each model replica\'s forward as one hipGraph per batch (host cost ~0.3 ms per batch instead of ~200 kernel '
                    'launches); the agents\' poses stay per-batch data.  0 = eager launches')
+    p.add_argument('--device_eval', action='store_true', default=False, help='score the detections against the batch\'s gt_boxes on the device '
+                   '(nuScenes protocol: mAP, translation / scale / orientation / velocity errors); needs DATA_CONFIG.SYNTHETIC.EVAL_GT True')
     args = p.parse_args()
     cfg_from_yaml_file(args.cfg_file, cfg)
     cfg.TAG = Path(args.cfg_file).stem
+    if 'SYNTHETIC' not in cfg.DATA_CONFIG:
+        cfg.DATA_CONFIG.SYNTHETIC = {}
+    if 'EVAL_GT' not in cfg.DATA_CONFIG.SYNTHETIC:
+        cfg.DATA_CONFIG.SYNTHETIC.EVAL_GT = False              # present before --set, which only takes keys that exist
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
     return args, cfg
