@@ -654,6 +654,45 @@ int32_t pcp_det_eval_curves_stride(void);
 int pcp_det_eval_curves(const void *sorted, int64_t n, const int32_t *class_start, const int32_t *npos, int32_t n_classes, int32_t tp_index,
                         const double *rec_interp, void *workspace, size_t workspace_bytes, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Hard voxelisation and the one-layer PillarVFE: the classic PointPillar front end (inference).
+ * Replaces: pcdet/datasets/processor/data_processor.py:116-144 (transform_points_to_voxels over spconv's CPU point-to-voxel generator)
+ *           and pcdet/models/backbones_3d/vfe/pillar_vfe.py:94-123.
+ * points: (n, row_stride) float32 rows [b, x, y, z, f...], grouped by ascending frame index b (an integer of [0, batch_size)).  Per frame,
+ * in input order: c = floor((p - range_min) / voxel) (float32 subtract, IEEE divide), the point is skipped unless 0 <= c < grid on x, y and
+ * z (nz must be 1); a cell not seen before becomes the frame's next voxel unless the frame already has max_voxels (the point is skipped,
+ * later points of numbered voxels are still taken); the point takes the next slot of its voxel unless that holds max_points already.
+ * The result is a function of the input alone (voxel numbers = first appearance, slots = input order; no float atomics, nothing depends on
+ * the arrival order of an atomic).  Two calls around the single host read of M:
+ *   pcp_hard_voxelize         voxel_coords (cap, 4) int32 [b, 0, y, x] and voxel_num_points (cap,) int32 for the first M voxels, frames
+ *                             concatenated in frame order, cap = min(batch_size * max_voxels, max(n, 1));  counters (PCP_HARD_VOXEL_COUNTERS,)
+ *                             int32: [0] M, [1] error word (bit 0: a frame index that is no integer of [0, batch_size), bit 1: frames not in
+ *                             ascending order; the outputs are meaningless then), [4 .. 4 + 64) voxels per frame, the rest internal
+ *   pcp_hard_voxelize_gather  voxels (M, max_points, num_features) float32, every element written (unused slots 0.0); same points, grid,
+ *                             workspace and stream as the first call, num_features = columns 1 .. num_features of a row
+ * Limits: nz == 1, 1 <= max_points <= 128, 3 <= num_features <= 16, batch_size <= 64 (PCP_ERR_ARG outside them).
+ * pcp_pillar_vfe: pillar_features (M, out_channels) = max over all max_points slots of ReLU(w . feature + b), feature = [raw columns (all
+ * with PCP_PFN_ABSOLUTE_XYZ, else columns 3 ..), xyz - mean, xyz - (coord * voxel + offset), |xyz| with PCP_PFN_WITH_DISTANCE], rows past
+ * voxel_num_points are zero rows (their ReLU(b) takes part in the max).  w (out_channels, K) row-major with BatchNorm folded, b
+ * (out_channels,); voxel_size3 / offset3: three HOST floats each (offset = voxel / 2 + range_min).  out_channels % 16 == 0, <= 128.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_HARD_VOXEL_MAX_T 128
+#define PCP_HARD_VOXEL_MIN_FEATURES 3
+#define PCP_HARD_VOXEL_MAX_FEATURES 16
+#define PCP_HARD_VOXEL_MAX_BATCH 64
+#define PCP_HARD_VOXEL_COUNTERS 132
+#define PCP_PILLAR_VFE_MAX_OUT 128
+size_t pcp_hard_voxelize_workspace_bytes(const pcp_grid_t *grid, int64_t max_points);
+int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_stride, const pcp_grid_t *grid, int32_t nz, int32_t max_points,
+                      int64_t max_voxels, void *workspace, size_t workspace_bytes, int32_t *voxel_coords, int32_t *voxel_num_points,
+                      int32_t *counters, void *stream);
+int pcp_hard_voxelize_gather(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid,
+                             int32_t max_points, const void *workspace, size_t workspace_bytes, int64_t num_voxels,
+                             const int32_t *voxel_num_points, float *voxels, void *stream);
+int pcp_pillar_vfe(const float *voxels, const int32_t *voxel_num_points, const int32_t *voxel_coords, int64_t num_voxels, int32_t max_points,
+                   int32_t num_features, uint32_t flags, const float *voxel_size3, const float *offset3, const float *w, const float *b,
+                   int32_t out_channels, float *pillar_features, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ class SyntheticV2XDataset(DatasetInfo, Dataset):
     def __init__(self, dataset_cfg, class_names, training=False, root_path=None, logger=None):
         vs = [p.VOXEL_SIZE for p in dataset_cfg.DATA_PROCESSOR if 'VOXEL_SIZE' in p][0]
         enc = dataset_cfg.POINT_FEATURE_ENCODING
-        DatasetInfo.__init__(self, class_names, dataset_cfg.POINT_CLOUD_RANGE, vs, len(enc.used_feature_list))
+        DatasetInfo.__init__(self, class_names, dataset_cfg.POINT_CLOUD_RANGE, vs, len(enc.used_feature_list), dataset_cfg.DATA_PROCESSOR)
         self.dataset_cfg = dataset_cfg
         self.training = training
         self.logger = logger

@@ -45,13 +45,20 @@ class DatasetInfo:
     reference), derived from the config the way DatasetTemplate / DataProcessor derive them (dataset.py:25-46,
     data_processor.py:106-114).  Lets a model be built without any dataset on disk."""
 
-    def __init__(self, class_names, point_cloud_range, voxel_size, num_point_features):
+    def __init__(self, class_names, point_cloud_range, voxel_size, num_point_features, data_processor=None):
         self.class_names = list(class_names)
         self.point_cloud_range = np.array(point_cloud_range, dtype=np.float32)
         self.voxel_size = list(voxel_size)
         self.grid_size = np.round((self.point_cloud_range[3:6] - self.point_cloud_range[0:3]) / np.array(voxel_size)).astype(np.int64)
         self.point_feature_encoder = types.SimpleNamespace(num_point_features=int(num_point_features))
         self.depth_downsample_factor = None
+        # the hard voxeliser's limits, where DATA_PROCESSOR has a transform_points_to_voxels entry (data_processor.py:116-144); PillarVFE
+        # voxelises `points` with them.  None: no such entry (every DynPillarVFE config)
+        self.hard_voxel = None
+        for p in (data_processor or []):
+            if p.get('NAME', None) == 'transform_points_to_voxels':
+                self.hard_voxel = {'MAX_POINTS_PER_VOXEL': int(p['MAX_POINTS_PER_VOXEL']),
+                                   'MAX_NUMBER_OF_VOXELS': {k: int(v) for k, v in dict(p['MAX_NUMBER_OF_VOXELS']).items()}}
 
 
 def build_network_from_meta(meta):
@@ -65,5 +72,5 @@ def build_network_from_meta(meta):
     # point columns without the batch index: 'nusc' = the 7-column nuScenes cloud of pointpillar_jr_nomap, 'nusc_map' = the 12-column
     # cloud of pointpillar_jr_withmap (five HD-map layers after the timestamp)
     n_feat = {'car': 7, 'early': 7, 'lately': 13, 'disco': 6, 'nusc': 7, 'nusc_map': 12}.get(meta.get('layout', 'car'), 7)
-    ds = DatasetInfo(meta['class_names'], meta['pc_range'], meta['voxel_size'], n_feat)
+    ds = DatasetInfo(meta['class_names'], meta['pc_range'], meta['voxel_size'], n_feat, meta.get('data_processor', None))
     return build_network(cfg, len(meta['class_names']), ds)

@@ -77,7 +77,8 @@ class Detector3DTemplate(nn.Module):
         module = vfe.__all__[self.model_cfg.VFE.NAME](
             model_cfg=self.model_cfg.VFE, num_point_features=model_info_dict['num_rawpoint_features'],
             point_cloud_range=model_info_dict['point_cloud_range'], voxel_size=model_info_dict['voxel_size'],
-            grid_size=model_info_dict['grid_size'], depth_downsample_factor=model_info_dict['depth_downsample_factor'])
+            grid_size=model_info_dict['grid_size'], depth_downsample_factor=model_info_dict['depth_downsample_factor'],
+            hard_voxel=getattr(self.dataset, 'hard_voxel', None))
         model_info_dict['num_point_features'] = module.get_output_feature_dim()
         model_info_dict['module_list'].append(module)
         return module, model_info_dict

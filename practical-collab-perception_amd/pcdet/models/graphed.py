@@ -15,6 +15,9 @@ import torch
 class GraphedDetector:
     def __init__(self, model, points, batch_size, metadata, warmup=3):
         assert points.is_cuda and not model.training
+        if any(type(m).__name__ == 'PillarVFE' for m in model.modules()):
+            raise NotImplementedError('GraphedDetector: PillarVFE reads the voxel count back to size its tensors and cannot be captured; '
+                                      'run the model batch by batch')
         self.model = model
         self.batch_size = batch_size
         self.metadata = metadata

@@ -102,7 +102,12 @@ class PipelinedDetector:
         head = getattr(model, 'dense_head', None)
         return (hasattr(model, '_run_modules') and not PipelinedDetector._corrector_with_makers(model) and head is not None
                 and hasattr(head, 'gather_pending') and hasattr(head, 'device_postprocess')
-                and not PipelinedDetector._head_writes_exchange_data(head))
+                and not PipelinedDetector._head_writes_exchange_data(head) and not PipelinedDetector._hard_voxel(model))
+
+    @staticmethod
+    def _hard_voxel(model):
+        # PillarVFE sizes its voxel tensors from a host read of the voxel count in the middle of the forward
+        return any(type(m).__name__ == 'PillarVFE' for m in model.modules())
 
     @staticmethod
     def _head_writes_exchange_data(head):
@@ -129,6 +134,8 @@ class PipelinedDetector:
         assert not model.training
         if self._corrector_with_makers(model):
             raise NotImplementedError('PipelinedDetector: a point corrector beside BEV makers runs batch by batch')
+        if self._hard_voxel(model):
+            raise NotImplementedError('PipelinedDetector: PillarVFE (hard voxelisation reads the voxel count back) runs batch by batch')
         if self._head_writes_exchange_data(model.dense_head):
             raise NotImplementedError('PipelinedDetector: a head that writes exchange data (MoDAR) runs batch by batch')
         self.model = model

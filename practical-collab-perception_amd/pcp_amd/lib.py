@@ -415,6 +415,12 @@ SYMBOLS.update({
     'pcp_mp_pointwise_wgrad_workspace_bytes': (c_sz, [c_i64, c_i32, c_i32]),
     'pcp_mp_pointwise_wgrad': (c_i32, [ctypes.POINTER(MpRowMap), ctypes.POINTER(MpRowMap), c_i64, vp, c_sz, vp, c_i32, c_i32, vp]),
 })
+SYMBOLS.update({
+    'pcp_hard_voxelize_workspace_bytes': (c_sz, [ctypes.POINTER(Grid), c_i64]),
+    'pcp_hard_voxelize': (c_i32, [vp, c_i64, c_i32, ctypes.POINTER(Grid), c_i32, c_i32, c_i64, vp, c_sz, vp, vp, vp, vp]),
+    'pcp_hard_voxelize_gather': (c_i32, [vp, c_i64, c_i32, c_i32, ctypes.POINTER(Grid), c_i32, vp, c_sz, c_i64, vp, vp, vp]),
+    'pcp_pillar_vfe': (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, ctypes.c_uint32, ctypes.POINTER(c_f), ctypes.POINTER(c_f), vp, vp, c_i32, vp, vp]),
+})
 
 # PCP_OPT_* of include/pcp_hip.h.  The C library never reads the environment; the PCP_* variables of earlier rounds are mapped onto the option
 # table ONCE, here, when the library is loaded (set_option() changes an option later, e.g. from a test)

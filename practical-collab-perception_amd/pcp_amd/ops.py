@@ -1103,3 +1103,105 @@ def topk_boxes(keys, labels, boxes, k):
     cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
     check(L.pcp_topk_boxes(_p(keys), _p(labels), _p(boxes), B, N, k, _p(ob), _p(os_), _p(ol), _p(oi), _p(cnt), _stream()), 'pcp_topk_boxes')
     return ob, os_, ol, oi, cnt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# hard voxelisation + one-layer PillarVFE: the classic PointPillar front end (csrc/hard_voxel.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+
+HARD_VOXEL_MAX_T, HARD_VOXEL_MIN_FEATURES, HARD_VOXEL_MAX_FEATURES, HARD_VOXEL_MAX_BATCH = 128, 3, 16, 64
+HARD_VOXEL_COUNTERS = 132
+PILLAR_VFE_MAX_OUT = 128
+PFN_ABSOLUTE_XYZ, PFN_WITH_DISTANCE = 1, 2
+
+
+class HardVoxelResult:
+    """voxels (M, T, C) float32, voxel_coords (M, 4) int32 [b, z, y, x], voxel_num_points (M,) int32 on the device; voxels_per_frame: a
+    python list of batch_size ints (from the call's one host read)"""
+    __slots__ = ('voxels', 'voxel_coords', 'voxel_num_points', 'voxels_per_frame', 'workspace')
+
+
+def hard_voxel_nz(grid, z_max):
+    """cells along z of a range [grid.min_z, z_max], as DataProcessor rounds it (data_processor.py:111-113)"""
+    import numpy as np
+    return int(np.round((np.float32(z_max) - np.float32(grid.min_z)) / np.float32(grid.voxel_z)))
+
+
+def hard_voxelize(points, grid, z_max, max_points_per_voxel, max_voxels, workspace=None):
+    """spconv's CPU point-to-voxel generator on the device (include/pcp_hip.h: pcp_hard_voxelize), pillar case.  points: (N, 1 + C) float32
+    CUDA rows [b, x, y, z, f...] grouped by ascending frame (ValueError otherwise); grid: make_grid(...) whose z extent [min_z, z_max] is ONE
+    cell; per frame at most max_voxels voxels of at most max_points_per_voxel points.  One host read (M, the error word and the per-frame
+    counts travel together).  The result is a function of the input alone, bit for bit."""
+    _need_cuda(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
+        raise ValueError('hard_voxelize: points must be a contiguous (N, 1 + C) float32 tensor, got %s %s' % (tuple(points.shape), points.dtype))
+    n, stride = int(points.shape[0]), int(points.shape[1])
+    C, T, B = stride - 1, int(max_points_per_voxel), int(grid.batch_size)
+    nz = hard_voxel_nz(grid, z_max)
+    if nz != 1:
+        raise NotImplementedError('hard_voxelize: the pillar case only (one cell along z); this range and voxel size give nz = %d' % nz)
+    if not 1 <= T <= HARD_VOXEL_MAX_T:
+        raise ValueError('hard_voxelize: MAX_POINTS_PER_VOXEL must lie in [1, %d], got %d' % (HARD_VOXEL_MAX_T, T))
+    if not HARD_VOXEL_MIN_FEATURES <= C <= HARD_VOXEL_MAX_FEATURES:
+        raise ValueError('hard_voxelize: %d to %d feature columns behind the frame index, got %d'
+                         % (HARD_VOXEL_MIN_FEATURES, HARD_VOXEL_MAX_FEATURES, C))
+    if not 1 <= B <= HARD_VOXEL_MAX_BATCH:
+        raise ValueError('hard_voxelize: at most %d frames per call, got %d' % (HARD_VOXEL_MAX_BATCH, B))
+    if int(max_voxels) < 1:
+        raise ValueError('hard_voxelize: MAX_NUMBER_OF_VOXELS must be positive, got %d' % int(max_voxels))
+    L = _lib.load()
+    dev = points.device
+    need = L.pcp_hard_voxelize_workspace_bytes(ctypes.byref(grid), n)
+    if need == 0:
+        raise _lib.PcpError('pcp_hard_voxelize: unsupported grid')
+    if workspace is None or workspace.numel() < need or workspace.device != dev:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    cap = max(min(B * int(max_voxels), n), 1)
+    coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    num = torch.empty((cap,), dtype=torch.int32, device=dev)
+    counters = torch.empty((HARD_VOXEL_COUNTERS,), dtype=torch.int32, device=dev)
+    check(L.pcp_hard_voxelize(_p(points), n, stride, ctypes.byref(grid), nz, T, int(max_voxels), _p(workspace), workspace.numel(), _p(coords),
+                              _p(num), _p(counters), _stream()), 'pcp_hard_voxelize')
+    host = counters[:4 + B].tolist()                     # the one host read
+    M, err = host[0], host[1]
+    if err:
+        raise ValueError('hard_voxelize: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (B, err))
+    res = HardVoxelResult()
+    res.workspace = workspace
+    res.voxels_per_frame = host[4:4 + B]
+    res.voxel_coords = coords[:M]
+    res.voxel_num_points = num[:M]
+    res.voxels = torch.empty((M, T, C), dtype=torch.float32, device=dev)
+    check(L.pcp_hard_voxelize_gather(_p(points), n, stride, C, ctypes.byref(grid), T, _p(workspace), workspace.numel(), M, _p(num),
+                                     _p(res.voxels), _stream()), 'pcp_hard_voxelize_gather')
+    return res
+
+
+def pillar_vfe(voxels, voxel_num_points, voxel_coords, voxel_size, offset, w, b, use_absolute_xyz=True, with_distance=False):
+    """one PFN layer of the reference's PillarVFE (include/pcp_hip.h: pcp_pillar_vfe): voxels (M, T, C) float32, voxel_num_points (M,) int32,
+    voxel_coords (M, 4) int32 [b, z, y, x], voxel_size / offset: three floats each (offset = voxel / 2 + range_min), w (out, K) and b (out,)
+    with BatchNorm folded.  Returns pillar_features (M, out)."""
+    _need_cuda(voxels, voxel_num_points, voxel_coords, w, b)
+    _need_f32('pcp_pillar_vfe', voxels, w, b)
+    if voxel_num_points.dtype != torch.int32 or voxel_coords.dtype != torch.int32:
+        raise _lib.PcpError('pcp_pillar_vfe reads int32 voxel_num_points / voxel_coords, got %s / %s' % (voxel_num_points.dtype, voxel_coords.dtype))
+    for t in (voxels, voxel_num_points, voxel_coords, w, b):
+        assert t.is_contiguous()
+    M, T, C = (int(v) for v in voxels.shape)
+    out = int(w.shape[0])
+    K = (C if use_absolute_xyz else C - 3) + 6 + (1 if with_distance else 0)
+    assert tuple(w.shape) == (out, K) and tuple(b.shape) == (out,), (tuple(w.shape), (out, K))
+    assert tuple(voxel_coords.shape) == (M, 4) and tuple(voxel_num_points.shape) == (M,)
+    if out % 16 or not 16 <= out <= PILLAR_VFE_MAX_OUT:
+        raise NotImplementedError('pcp_pillar_vfe: the output width is a multiple of 16 up to %d, got %d' % (PILLAR_VFE_MAX_OUT, out))
+    if not 1 <= T <= HARD_VOXEL_MAX_T or not HARD_VOXEL_MIN_FEATURES <= C <= HARD_VOXEL_MAX_FEATURES:
+        raise NotImplementedError('pcp_pillar_vfe: 1 to %d points per voxel and %d to %d columns, got (T, C) = (%d, %d)'
+                                  % (HARD_VOXEL_MAX_T, HARD_VOXEL_MIN_FEATURES, HARD_VOXEL_MAX_FEATURES, T, C))
+    L = _lib.load()
+    pf = torch.empty((M, out), dtype=torch.float32, device=voxels.device)
+    vs = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
+    off = (ctypes.c_float * 3)(*[float(v) for v in offset])
+    flags = (PFN_ABSOLUTE_XYZ if use_absolute_xyz else 0) | (PFN_WITH_DISTANCE if with_distance else 0)
+    check(L.pcp_pillar_vfe(_p(voxels), _p(voxel_num_points), _p(voxel_coords), M, T, C, flags, vs, off, _p(w), _p(b), out, _p(pf), _stream()),
+          'pcp_pillar_vfe')
+    return pf
