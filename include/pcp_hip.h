@@ -693,6 +693,72 @@ int pcp_pillar_vfe(const float *voxels, const int32_t *voxel_num_points, const i
                    int32_t num_features, uint32_t flags, const float *voxel_size3, const float *offset3, const float *w, const float *b,
                    int32_t out_channels, float *pillar_features, void *stream);
 
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The SECOND family (inference): per-voxel mean, sparse 3D convolution, HeightCompression.  csrc/spconv3d.hip.
+ * Replaces: pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py:53-79 (range mask on x, y and z, merged id
+ *           b*nx*ny*nz + cx*ny*nz + cy*nz + cz, torch.unique, torch_scatter.scatter_mean), spconv's SubMConv3d / SparseConv3d as
+ *           pcdet/models/backbones_3d/spconv_backbone.py uses them, and map_to_bev/height_compression.py (dense() + view).
+ *
+ * Mean VFE.  points: (n, row_stride) float32 rows [b, x, y, z, f...] grouped by ascending frame index.  Two calls around the single host
+ * read of M:
+ *   the first call      voxel_coords (max(n, 1), 4) int32 [b, z, y, x] for the first M voxels, numbered in ascending merged id;  counters
+ *                       (PCP_MEAN_VFE_COUNTERS,) int32: [0] M, [1] error word (bit 0: a frame index that is no integer of [0, batch_size),
+ *                       bit 1: frames not in ascending order), [2] rows kept
+ *   the features call   voxel_features (M, num_features) float32 = mean of columns 1 .. num_features over the voxel's rows, summed in a
+ *                       fixed order in float32 (four interleaved partial sums in input-row order, (s0 + s1) + (s2 + s3)) and divided by the
+ *                       count; same points, grid, nz, workspace and stream as the first call
+ * No float atomics: a call repeats bit for bit and a frame's voxels have the same bits alone or inside a batch.
+ * Limits (PCP_ERR_ARG outside them): 1 <= nz <= 64, batch_size <= 64, 3 <= num_features <= 16.
+ *
+ * Index tables.  A coordinate set over a (batch, d, h, w) grid is a bitmap with one bit per site plus an exclusive popcount prefix per
+ * 64-bit word; the rank of a site is its position in ascending linear (b, z, y, x) order.  A table of the byte size the size query returns,
+ * 256-byte aligned.  coords are (n, 4) int32 [b, z, y, x], 16-byte aligned.
+ *   table build         the table of `coords`; perm (n,) int32 with perm[rank] = row (fill it with -1 first: a duplicated site leaves
+ *                       entries unwritten);  counters (4,) int32: [0] distinct sites, [1] != 0 when a coordinate lies outside the grid
+ *   subm build          nbr (27, n) int32 for SubMConv3d(3, padding 1): nbr[(dz * 3 + dy) * 3 + dx][p] = the row at p + (dz, dy, dx) - 1 or -1
+ *   strided sites       marks in out_table every output site of SparseConv3d(kernel3, stride3, pad3) (each three HOST ints, z y x; kernel
+ *                       and stride 1 .. 3, padding 0 .. 2; output extent (in + 2 p - k) / s + 1) some input reaches, and finishes that
+ *                       table; counters[0] = the number of output rows (the one host read of a strided layer)
+ *   strided build       out_coords (n_out, 4) in ascending linear order and nbr (kz*ky*kx, n_out): nbr[d][o] = the input row at
+ *                       o * s - p + d or -1.  in_perm NULL: the input rows are in rank order (the output of a strided layer)
+ * Integer atomicOr on the bitmap only: neither a row number nor a table entry depends on arrival order.
+ *
+ * Convolution: out (n_out, cout) = relu?(sum over offsets k ascending, cin ascending of features[nbr[k][row]] . w[k] + bias + residual?).
+ * features (n_in, ld_in) float32 with cin real columns; w_packed [num_offsets][cout][cin_pad] float32 (cin contiguous, BatchNorm folded,
+ * cin_pad = 16 for cin <= 16), 16-byte aligned; bias (cout,); residual NULL or (n_out, cout).  (cin_pad, cout) one of (16, 16), (16, 32),
+ * (32, 32), (32, 64), (64, 64), (64, 128), (128, 128), cin >= 3 (PCP_ERR_UNSUPPORTED otherwise).  fp32 products and sums on
+ * v_mfma_f32_16x16x4_f32, no scatter, no float atomics; a row's bits depend on its own neighbour list only.
+ *
+ * Dense: out (batch, h, w, channels * d) float32, EVERY element written: channel c * d_extent + z of pixel (b, y, x) is feature c of site
+ * (b, z, y, x) or 0.  d <= 64.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PCP_MEAN_VFE_MAX_NZ 64
+#define PCP_MEAN_VFE_MAX_BATCH 64
+#define PCP_MEAN_VFE_MIN_FEATURES 3
+#define PCP_MEAN_VFE_MAX_FEATURES 16
+#define PCP_MEAN_VFE_COUNTERS 4
+size_t pcp_mean_vfe_workspace_bytes(const pcp_grid_t *grid, int64_t max_points);
+int pcp_mean_vfe(const float *points, int64_t n, int32_t row_stride, const pcp_grid_t *grid, int32_t nz, void *workspace, size_t workspace_bytes,
+                 int32_t *voxel_coords, int32_t *counters, void *stream);
+int pcp_mean_vfe_features(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
+                          const void *workspace, size_t workspace_bytes, int64_t num_voxels, float *voxel_features, void *stream);
+size_t pcp_spconv_table_bytes(int32_t batch, int32_t d, int32_t h, int32_t w);
+int pcp_spconv_table_build(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, void *table, size_t table_bytes,
+                           int32_t *perm, int32_t *counters, void *stream);
+int pcp_spconv_build_subm(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table, size_t table_bytes,
+                          const int32_t *perm, int32_t *nbr, void *stream);
+int pcp_spconv_strided_sites(const int32_t *in_coords, int64_t n_in, int32_t batch, int32_t d, int32_t h, int32_t w, const int32_t *kernel3,
+                             const int32_t *stride3, const int32_t *pad3, void *out_table, size_t out_table_bytes, int32_t *counters,
+                             void *stream);
+int pcp_spconv_build_strided(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes, const int32_t *in_perm,
+                             const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, const void *out_table, size_t out_table_bytes,
+                             int64_t n_out, int32_t *out_coords, int32_t *nbr, void *stream);
+int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, int32_t ld_in, const int32_t *nbr, int32_t num_offsets, int64_t n_out,
+                 const float *w_packed, const float *bias, const float *residual, int32_t relu, int32_t cout, float *out, void *stream);
+int pcp_spconv_dense(const float *features, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table,
+                     size_t table_bytes, const int32_t *perm, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@
 //     a cell not seen before becomes voxel nvox++ unless nvox == max_voxels (then the point is skipped, later points go on)
 //     the point takes the next slot of its voxel unless the voxel already holds T points
 // so voxels are numbered by FIRST APPEARANCE and slots by input order.  No step here depends on the arrival order of an atomic:
-//   k_hv_cells     cell id per row (z range too), integer histogram, frame column validated        (the only atomics: integer adds)
+//   k_cells_z      (csrc/vox_cells_z.h, shared with the mean VFE) cell id per row (z range too), integer histogram, frame column validated        (the only atomics: integer adds)
 //   pcp_voxelize_cells_ready + pcp_voxelize_sort_pillar_rows (csrc/voxelize.hip, called, not changed): rows grouped by cell, every cell's
 //                  rows in ascending row index -- the first entry of a run is the cell's first point, entry j its slot-j point; a cell
 //                  of thousands of rows is ranked by a whole workgroup there
@@ -16,13 +16,14 @@
 //                  kept if < max_voxels; voxel number = kept voxels of the frames in front + rank.  Writes coords, num_points, counters
 //   k_hv_gather    (after the host read M) one thread per (voxel, slot): the row of slot j < min(count, T), zeros behind
 #include "pcp_common.h"
+#include "vox_cells_z.h"
 
 namespace {
 
 constexpr int HV_THREADS = 256;
 constexpr int HV_ITEMS = 4;
 constexpr int HV_TILE = HV_THREADS * HV_ITEMS;       // 1024 rows per workgroup
-constexpr int HV_HT = 2048;                          // LDS hash table of k_hv_cells
+static_assert(HV_TILE == CZ_TILE, "k_cells_z and the tile passes below walk the same 1024-row tiles");
 constexpr int HV_MAX_B = PCP_HARD_VOXEL_MAX_BATCH;   // 64: one wave scans the per-frame counts
 
 // counters (int32, PCP_HARD_VOXEL_COUNTERS of them): [0] M, [1] error word, [4 .. 4 + 64) voxels kept per frame, [68 .. 68 + 64) cells hit per frame
@@ -45,70 +46,6 @@ inline HvLayout hv_layout(int64_t cells, int64_t n) {
   L.dense_coords = take((size_t)n * 16);
   L.total = off;
   return L;
-}
-
-// -1: outside the range (x, y or z), NaN, or a frame index that is no integer of [0, B)
-__device__ __forceinline__ int hv_point_to_cell(const float *row, const pcp_grid_t g, int nz) {
-  const float fb = row[0];
-  const float cx = floorf(__fdiv_rn(__fsub_rn(row[1], g.min_x), g.voxel_x));
-  const float cy = floorf(__fdiv_rn(__fsub_rn(row[2], g.min_y), g.voxel_y));
-  const float cz = floorf(__fdiv_rn(__fsub_rn(row[3], g.min_z), g.voxel_z));
-  const bool ok = (cx >= 0.0f) && (cx < (float)g.nx) && (cy >= 0.0f) && (cy < (float)g.ny) && (cz >= 0.0f) && (cz < (float)nz) &&
-                  (fb >= 0.0f) && (fb < (float)g.batch_size);
-  if (!ok) return -1;
-  return (int)fb * (g.nx * g.ny) + (int)cx * g.ny + (int)cy;
-}
-
-// Pass 1 (the z-checking twin of voxelize.hip's k_point_cells<true>): a workgroup counts its 1024 rows in an LDS hash table keyed by cell and
-// reserves the slots of each distinct cell with ONE global integer atomic, so the 5 000 rows under the sensor do not queue on one address.
-// The slots it hands out are arrival order; pcp_voxelize_sort_pillar_rows replaces them by row order before anything reads them.
-__global__ __launch_bounds__(HV_THREADS) void k_hv_cells(const float *__restrict__ points, long long n, int stride, pcp_grid_t g, int nz,
-                                                         int *__restrict__ cell_count, int *__restrict__ point_cell,
-                                                         int *__restrict__ point_rank, int *__restrict__ counters) {
-  __shared__ int h_key[HV_HT], h_cnt[HV_HT];
-  const long long base = (long long)blockIdx.x * HV_TILE;
-  for (int e = threadIdx.x; e < HV_HT; e += HV_THREADS) {
-    h_key[e] = -1;
-    h_cnt[e] = 0;
-  }
-  __syncthreads();
-  int hslot[HV_ITEMS], hloc[HV_ITEMS];
-  int err = 0;
-#pragma unroll
-  for (int i = 0; i < HV_ITEMS; i++) {
-    const long long r = base + i * HV_THREADS + threadIdx.x;
-    hslot[i] = -1;
-    hloc[i] = 0;
-    if (r < n) {
-      const float *row = points + r * stride;
-      const float fb = row[0];
-      // rows are grouped by ascending frame: an integer of [0, B), never below the row in front
-      if (!(fb >= 0.0f && fb < (float)g.batch_size && fb == floorf(fb))) err |= 1;
-      if (r > 0 && !(points[(r - 1) * stride] <= fb)) err |= 2;
-      const int c = (err == 0) ? hv_point_to_cell(row, g, nz) : -1;
-      point_cell[r] = c;
-      if (c >= 0) {
-        unsigned h = ((unsigned)c * 2654435761u) >> 21;                    // 11 bits
-        while (true) {
-          const int prev = atomicCAS(&h_key[h], -1, c);
-          if (prev == -1 || prev == c) break;
-          h = (h + 1) & (HV_HT - 1);
-        }
-        hslot[i] = (int)h;
-        hloc[i] = atomicAdd(&h_cnt[h], 1);
-      }
-    }
-  }
-  if (err) atomicOr(&counters[HV_CNT_ERR], err);
-  __syncthreads();
-  for (int e = threadIdx.x; e < HV_HT; e += HV_THREADS) {
-    const int c = h_key[e];
-    if (c >= 0) h_cnt[e] = atomicAdd(&cell_count[c], h_cnt[e]);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < HV_ITEMS; i++)
-    if (hslot[i] >= 0) point_rank[base + i * HV_THREADS + threadIdx.x] = h_cnt[hslot[i]] + hloc[i];
 }
 
 // is row r the first point of its cell?  The cell's run in the sorted bucket order starts with its smallest row index.
@@ -292,8 +229,8 @@ extern "C" int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_str
   if (pcp_zero_async(cell_count, (size_t)cells * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (pcp_zero_async(counters, (size_t)PCP_HARD_VOXEL_COUNTERS * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(k_hv_cells, dim3(n_tiles), dim3(HV_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
-                       point_cell, point_rank, counters);
+    hipLaunchKernelGGL(k_cells_z<false>, dim3(n_tiles), dim3(CZ_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
+                       point_cell, point_rank, (int *)nullptr, counters + HV_CNT_ERR);
     PCP_CHECK_LAUNCH();
   }
   // cells -> pillars in cell order, rows grouped by pillar; then every pillar's rows in ascending row index

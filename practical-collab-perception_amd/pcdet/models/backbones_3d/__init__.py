@@ -1,3 +1,7 @@
-"""3-D backbones are out of scope for the PointPillars hot path; the registry exists so that
-Detector3DTemplate.build_backbone_3d can report a clear error for configs that name one."""
-__all__ = {}
+"""3-D backbones: the residual sparse backbone of the SECOND models (inference).  Detector3DTemplate.build_backbone_3d reports a clear error
+for a config that names another one."""
+from .spconv_backbone import VoxelResBackBone8x
+
+__all__ = {
+    'VoxelResBackBone8x': VoxelResBackBone8x,
+}

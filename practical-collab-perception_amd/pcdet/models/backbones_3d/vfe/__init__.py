@@ -1,3 +1,4 @@
+from .dynamic_mean_vfe import DynamicMeanVFE
 from .dynamic_pillar_vfe import DynamicPillarVFE, PFNLayerV2
 from .pillar_vfe import PillarVFE
 from .vfe_template import VFETemplate
@@ -6,5 +7,6 @@ from .vfe_template import VFETemplate
 __all__ = {
     'VFETemplate': VFETemplate,
     'DynPillarVFE': DynamicPillarVFE,
+    'DynMeanVFE': DynamicMeanVFE,
     'PillarVFE': PillarVFE,
 }

@@ -15,6 +15,7 @@ from ..bev_layers.bev_maker import BEVMaker
 from ..bev_layers.hunter_jr import HunterJr
 from ..bev_layers.v2x_fusion_disco import V2XMidFusionDisco
 from ...ops.iou3d_nms import iou3d_nms_utils
+from ...utils.spconv_utils import find_all_spconv_keys
 
 
 class Detector3DTemplate(nn.Module):
@@ -139,9 +140,18 @@ class Detector3DTemplate(nn.Module):
         return None, model_info_dict
 
     def build_backbone_3d(self, model_info_dict):
-        if self.model_cfg.get('BACKBONE_3D', None) is not None and self.model_cfg.BACKBONE_3D.NAME in backbones_3d.__all__:
-            raise NotImplementedError
-        return self._off_path('BACKBONE_3D', model_info_dict)
+        if self.model_cfg.get('BACKBONE_3D', None) is None:
+            return None, model_info_dict
+        if self.model_cfg.BACKBONE_3D.NAME not in backbones_3d.__all__:
+            return self._off_path('BACKBONE_3D', model_info_dict)
+        module = backbones_3d.__all__[self.model_cfg.BACKBONE_3D.NAME](
+            model_cfg=self.model_cfg.BACKBONE_3D, input_channels=model_info_dict['num_point_features'],
+            grid_size=model_info_dict['grid_size'], voxel_size=model_info_dict['voxel_size'],
+            point_cloud_range=model_info_dict['point_cloud_range'])
+        model_info_dict['module_list'].append(module)
+        model_info_dict['num_point_features'] = module.num_point_features
+        model_info_dict['backbone_channels'] = getattr(module, 'backbone_channels', None)
+        return module, model_info_dict
 
     def build_pfe(self, model_info_dict):
         return self._off_path('PFE', model_info_dict)
@@ -215,7 +225,22 @@ class Detector3DTemplate(nn.Module):
     # ---- checkpoints: {'model_state', 'epoch', 'it', 'optimizer_state', 'version'} (reference :391-476) ---------------------
     def _load_state_dict(self, model_state_disk, *, strict=True):
         state_dict = self.state_dict()
-        update = {k: v for k, v in model_state_disk.items() if k in state_dict and state_dict[k].shape == v.shape}
+        spconv_keys = find_all_spconv_keys(self)
+        update = {}
+        for k, v in model_state_disk.items():
+            if k in spconv_keys and k in state_dict and state_dict[k].shape != v.shape:
+                # a sparse conv weight saved by spconv 1.x, (kz, ky, kx, Cin, Cout): to (kz, ky, kx, Cout, Cin) or to the 2.x layout
+                # (Cout, kz, ky, kx, Cin), whichever this model holds (reference :394-409)
+                swapped = v.transpose(-1, -2)
+                if swapped.shape == state_dict[k].shape:
+                    v = swapped.contiguous()
+                else:
+                    assert v.dim() == 5, 'only 3D sparse conv weights are adapted'
+                    moved = v.permute(4, 0, 1, 2, 3)
+                    if moved.shape == state_dict[k].shape:
+                        v = moved.contiguous()
+            if k in state_dict and state_dict[k].shape == v.shape:
+                update[k] = v
         if strict:
             self.load_state_dict(update)
         else:

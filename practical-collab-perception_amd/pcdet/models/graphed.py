@@ -18,6 +18,9 @@ class GraphedDetector:
         if any(type(m).__name__ == 'PillarVFE' for m in model.modules()):
             raise NotImplementedError('GraphedDetector: PillarVFE reads the voxel count back to size its tensors and cannot be captured; '
                                       'run the model batch by batch')
+        if any(type(m).__name__ == 'VoxelResBackBone8x' for m in model.modules()):
+            raise NotImplementedError('GraphedDetector: VoxelResBackBone8x reads the row count of every strided sparse conv back and cannot be '
+                                      'captured; run the model batch by batch')
         self.model = model
         self.batch_size = batch_size
         self.metadata = metadata

@@ -102,12 +102,17 @@ class PipelinedDetector:
         head = getattr(model, 'dense_head', None)
         return (hasattr(model, '_run_modules') and not PipelinedDetector._corrector_with_makers(model) and head is not None
                 and hasattr(head, 'gather_pending') and hasattr(head, 'device_postprocess')
-                and not PipelinedDetector._head_writes_exchange_data(head) and not PipelinedDetector._hard_voxel(model))
+                and not PipelinedDetector._head_writes_exchange_data(head) and not PipelinedDetector._hard_voxel(model) and not PipelinedDetector._sparse_backbone(model))
 
     @staticmethod
     def _hard_voxel(model):
         # PillarVFE sizes its voxel tensors from a host read of the voxel count in the middle of the forward
         return any(type(m).__name__ == 'PillarVFE' for m in model.modules())
+
+    @staticmethod
+    def _sparse_backbone(model):
+        # VoxelResBackBone8x reads the row count of each strided sparse conv back (and DynMeanVFE its voxel count) in the middle of the forward
+        return any(type(m).__name__ == 'VoxelResBackBone8x' for m in model.modules())
 
     @staticmethod
     def _head_writes_exchange_data(head):
@@ -136,6 +141,8 @@ class PipelinedDetector:
             raise NotImplementedError('PipelinedDetector: a point corrector beside BEV makers runs batch by batch')
         if self._hard_voxel(model):
             raise NotImplementedError('PipelinedDetector: PillarVFE (hard voxelisation reads the voxel count back) runs batch by batch')
+        if self._sparse_backbone(model):
+            raise NotImplementedError('PipelinedDetector: VoxelResBackBone8x (every strided sparse conv reads its row count back) runs batch by batch')
         if self._head_writes_exchange_data(model.dense_head):
             raise NotImplementedError('PipelinedDetector: a head that writes exchange data (MoDAR) runs batch by batch')
         self.model = model

@@ -421,6 +421,20 @@ SYMBOLS.update({
     'pcp_hard_voxelize_gather': (c_i32, [vp, c_i64, c_i32, c_i32, ctypes.POINTER(Grid), c_i32, vp, c_sz, c_i64, vp, vp, vp]),
     'pcp_pillar_vfe': (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, ctypes.c_uint32, ctypes.POINTER(c_f), ctypes.POINTER(c_f), vp, vp, c_i32, vp, vp]),
 })
+SYMBOLS.update({
+    'pcp_mean_vfe_workspace_bytes': (c_sz, [ctypes.POINTER(Grid), c_i64]),
+    'pcp_mean_vfe': (c_i32, [vp, c_i64, c_i32, ctypes.POINTER(Grid), c_i32, vp, c_sz, vp, vp, vp]),
+    'pcp_mean_vfe_features': (c_i32, [vp, c_i64, c_i32, c_i32, ctypes.POINTER(Grid), c_i32, vp, c_sz, c_i64, vp, vp]),
+    'pcp_spconv_table_bytes': (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    'pcp_spconv_table_build': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, c_sz, vp, vp, vp]),
+    'pcp_spconv_build_subm': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, c_sz, vp, vp, vp]),
+    'pcp_spconv_strided_sites': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                         ctypes.POINTER(c_i32), vp, c_sz, vp, vp]),
+    'pcp_spconv_build_strided': (c_i32, [c_i32, c_i32, c_i32, c_i32, vp, c_sz, vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                         ctypes.POINTER(c_i32), vp, c_sz, c_i64, vp, vp, vp]),
+    'pcp_spconv3d': (c_i32, [vp, c_i64, c_i32, c_i32, vp, c_i32, c_i64, vp, vp, vp, c_i32, c_i32, vp, vp]),
+    'pcp_spconv_dense': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_sz, vp, vp, vp]),
+})
 
 # PCP_OPT_* of include/pcp_hip.h.  The C library never reads the environment; the PCP_* variables of earlier rounds are mapped onto the option
 # table ONCE, here, when the library is loaded (set_option() changes an option later, e.g. from a test)

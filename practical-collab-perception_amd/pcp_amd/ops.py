@@ -1205,3 +1205,178 @@ def pillar_vfe(voxels, voxel_num_points, voxel_coords, voxel_size, offset, w, b,
     check(L.pcp_pillar_vfe(_p(voxels), _p(voxel_num_points), _p(voxel_coords), M, T, C, flags, vs, off, _p(w), _p(b), out, _p(pf), _stream()),
           'pcp_pillar_vfe')
     return pf
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the SECOND family: per-voxel mean, sparse 3D convolution index tables, the convolution, dense() (csrc/spconv3d.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+MEAN_VFE_MAX_NZ, MEAN_VFE_MAX_BATCH, MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, MEAN_VFE_COUNTERS = 64, 64, 3, 16, 4
+SPCONV_CHANNEL_PAIRS = ((16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128))       # (cin padded to 16, cout)
+
+
+def mean_vfe(points, grid, num_features, *, nz, workspace=None):
+    """the reference's DynamicMeanVFE on the device (include/pcp_hip.h: pcp_mean_vfe).  points: (N, >= 1 + num_features) float32 CUDA rows
+    [b, x, y, z, f...] grouped by ascending frame (ValueError otherwise); grid: make_grid(...), which carries the x / y extent and the z
+    origin and cell height only, hence the keyword nz = cells along z (grid_size[2]).  Returns voxel_features
+    (M, num_features), voxel_coords (M, 4) int32 [b, z, y, x] in ascending merged id, M.  One host read."""
+    _need_cuda(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
+        raise ValueError('mean_vfe: points must be a contiguous (N, 1 + C) float32 tensor, got %s %s' % (tuple(points.shape), points.dtype))
+    n, stride = int(points.shape[0]), int(points.shape[1])
+    C, B, nz = int(num_features), int(grid.batch_size), int(nz)
+    if not MEAN_VFE_MIN_FEATURES <= C <= MEAN_VFE_MAX_FEATURES:
+        raise ValueError('mean_vfe: %d to %d feature columns behind the frame index, got %d' % (MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, C))
+    if stride < 1 + C:
+        raise ValueError('mean_vfe: rows of %d columns cannot hold the frame index and %d features' % (stride, C))
+    if not 1 <= B <= MEAN_VFE_MAX_BATCH:
+        raise ValueError('mean_vfe: at most %d frames per call, got %d' % (MEAN_VFE_MAX_BATCH, B))
+    if not 1 <= nz <= MEAN_VFE_MAX_NZ:
+        raise ValueError('mean_vfe: 1 to %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, nz))
+    L = _lib.load()
+    dev = points.device
+    need = L.pcp_mean_vfe_workspace_bytes(ctypes.byref(grid), n)
+    if need == 0:
+        raise _lib.PcpError('pcp_mean_vfe: unsupported grid')
+    if workspace is None or workspace.numel() < need or workspace.device != dev:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    coords = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
+    counters = torch.empty((MEAN_VFE_COUNTERS,), dtype=torch.int32, device=dev)
+    check(L.pcp_mean_vfe(_p(points), n, stride, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(coords), _p(counters), _stream()),
+          'pcp_mean_vfe')
+    M, err = counters[:2].tolist()                     # the one host read
+    if err:
+        raise ValueError('mean_vfe: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (B, err))
+    feats = torch.empty((M, C), dtype=torch.float32, device=dev)
+    check(L.pcp_mean_vfe_features(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), M, _p(feats), _stream()),
+          'pcp_mean_vfe_features')
+    return feats, coords[:M], M
+
+
+def _i3(v):
+    v = [int(v)] * 3 if isinstance(v, int) else [int(x) for x in v]
+    assert len(v) == 3, v
+    return v
+
+
+class SpconvTable:
+    """the lookup structure of one coordinate set (bitmap + popcount prefix, include/pcp_hip.h); perm None: rows in ascending linear order"""
+
+    def __init__(self, shape4, mem, perm):
+        self.shape4, self.mem, self.perm = tuple(int(v) for v in shape4), mem, perm
+
+
+def _spconv_table_mem(shape4, dev):
+    need = _lib.load().pcp_spconv_table_bytes(*shape4)
+    if need == 0:
+        raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % (tuple(shape4),))
+    return torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def spconv_table(coords, batch_size, spatial_shape, check_input=True):
+    """the table of coords (N, 4) int32 [b, z, y, x] on a (batch_size, *spatial_shape) grid.  check_input reads the distinct-site count and the
+    range flag back (ValueError on a duplicated or outside coordinate); a producer that guarantees both (mean_vfe) passes False."""
+    _need_cuda(coords)
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4 or not coords.is_contiguous():
+        raise ValueError('sparse conv tables: indices must be a contiguous (N, 4) int32 tensor, got %s %s' % (tuple(coords.shape), coords.dtype))
+    shape4 = (int(batch_size),) + tuple(int(v) for v in spatial_shape)
+    n, dev = int(coords.shape[0]), coords.device
+    mem = _spconv_table_mem(shape4, dev)
+    perm = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+    counters = torch.empty((4,), dtype=torch.int32, device=dev)
+    check(_lib.load().pcp_spconv_table_build(_p(coords), n, *shape4, _p(mem), mem.numel(), _p(perm), _p(counters), _stream()),
+          'pcp_spconv_table_build')
+    if check_input:
+        distinct, bad = counters[:2].tolist()
+        if bad or distinct != n:
+            raise ValueError('sparse conv tables: %d rows name %d distinct sites%s of the grid %s'
+                             % (n, distinct, ' and some lie outside' if bad else '', shape4))
+    return SpconvTable(shape4, mem, perm)
+
+
+def spconv_build_subm(coords, table):
+    """neighbour table (27, N) int32 of SubMConv3d(3, padding 1) over the set `table` describes"""
+    n = int(coords.shape[0])
+    nbr = torch.empty((27, n), dtype=torch.int32, device=coords.device)
+    check(_lib.load().pcp_spconv_build_subm(_p(coords), n, *table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), _p(nbr), _stream()),
+          'pcp_spconv_build_subm')
+    return nbr
+
+
+def spconv_out_shape(spatial_shape, kernel, stride, padding):
+    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
+    return tuple((int(spatial_shape[a]) + 2 * p[a] - k[a]) // s[a] + 1 for a in range(3))
+
+
+def spconv_build_strided(coords, table, kernel, stride, padding):
+    """SparseConv3d's index: -> (out_coords (N_out, 4) int32 in ascending linear order, nbr (K, N_out) int32, out_table).  One host read."""
+    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
+    for name, v, lo, hi in (('kernel', k, 1, 3), ('stride', s, 1, 3), ('padding', p, 0, 2)):
+        if not all(lo <= x <= hi for x in v):
+            raise NotImplementedError('sparse conv: %s %s outside [%d, %d]' % (name, tuple(v), lo, hi))
+    B = table.shape4[0]
+    out_sp = spconv_out_shape(table.shape4[1:], k, s, p)
+    if min(out_sp) < 1:
+        raise ValueError('sparse conv: kernel %s stride %s padding %s leaves no output on the grid %s' % (k, s, p, table.shape4[1:]))
+    L = _lib.load()
+    dev = coords.device
+    n_in = int(coords.shape[0])
+    out_mem = _spconv_table_mem((B,) + out_sp, dev)
+    counters = torch.empty((4,), dtype=torch.int32, device=dev)
+    k3, s3, p3 = (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*s), (ctypes.c_int32 * 3)(*p)
+    check(L.pcp_spconv_strided_sites(_p(coords), n_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), _p(counters), _stream()),
+          'pcp_spconv_strided_sites')
+    n_out = int(counters[0].item())                  # the one host read of a strided layer
+    K = k[0] * k[1] * k[2]
+    out_coords = torch.empty((n_out, 4), dtype=torch.int32, device=dev)
+    nbr = torch.empty((K, n_out), dtype=torch.int32, device=dev)
+    check(L.pcp_spconv_build_strided(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), k3, s3, p3, _p(out_mem), out_mem.numel(),
+                                     n_out, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided')
+    return out_coords, nbr, SpconvTable((B,) + out_sp, out_mem, None)
+
+
+def spconv_pack_weight(weight, cin_pad=None):
+    """(Cout, kz, ky, kx, Cin) -> [K][Cout][cin_pad] float32 contiguous, zero columns behind Cin"""
+    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
+    cin_pad = cin_pad or (16 if cin <= 16 else cin)
+    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 0, 2)
+    if cin_pad != cin:
+        w = torch.nn.functional.pad(w, (0, cin_pad - cin))
+    return w.contiguous()
+
+
+def spconv3d(features, nbr, w_packed, bias, residual=None, relu=False):
+    """out (N_out, Cout) = relu?(sum_k features[nbr[k]] . w_packed[k]^T + bias + residual?) (include/pcp_hip.h: pcp_spconv3d)"""
+    _need_cuda(features, nbr, w_packed, bias, residual)
+    _need_f32('pcp_spconv3d', features, w_packed, bias, residual)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise _lib.PcpError('pcp_spconv3d reads an int32 (K, N_out) neighbour table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
+    for t in (nbr, w_packed, bias, residual):
+        assert t is None or t.is_contiguous()
+    assert features.dim() == 2 and features.stride(1) == 1
+    n_in, cin, ld_in = int(features.shape[0]), int(features.shape[1]), int(features.stride(0)) if features.shape[0] > 1 else int(features.shape[1])
+    K, n_out = int(nbr.shape[0]), int(nbr.shape[1])
+    cout, cin_pad = int(w_packed.shape[1]), int(w_packed.shape[2])
+    if cin < 3 or (16 if cin <= 16 else cin) != cin_pad or (cin_pad, cout) not in SPCONV_CHANNEL_PAIRS:
+        raise NotImplementedError('pcp_spconv3d: the channel pair (Cin, Cout) = (%d, %d) has no kernel; supported: Cin 3..16 -> 16, and %s'
+                                  % (cin, cout, ', '.join('%d -> %d' % p for p in SPCONV_CHANNEL_PAIRS)))
+    assert int(w_packed.shape[0]) == K and tuple(bias.shape) == (cout,), (tuple(w_packed.shape), K, tuple(bias.shape))
+    assert residual is None or tuple(residual.shape) == (n_out, cout)
+    out = torch.empty((n_out, cout), dtype=torch.float32, device=features.device)
+    check(_lib.load().pcp_spconv3d(_p(features), n_in, cin, ld_in, _p(nbr), K, n_out, _p(w_packed), _p(bias), _p(residual), 1 if relu else 0, cout,
+                                   _p(out), _stream()), 'pcp_spconv3d')
+    return out
+
+
+def spconv_dense(features, table):
+    """the NHWC canvas (B, H, W, C * D), channel c * D + d: HeightCompression's dense() + view, every element written by the kernel"""
+    _need_cuda(features)
+    _need_f32('pcp_spconv_dense', features)
+    assert features.is_contiguous() and features.dim() == 2
+    B, D, H, W = table.shape4
+    if D > MEAN_VFE_MAX_NZ:
+        raise NotImplementedError('pcp_spconv_dense: at most %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, D))
+    n, C = int(features.shape[0]), int(features.shape[1])
+    out = torch.empty((B, H, W, C * D), dtype=torch.float32, device=features.device)
+    check(_lib.load().pcp_spconv_dense(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()),
+          'pcp_spconv_dense')
+    return out
