@@ -457,7 +457,7 @@ class _HeadBranches:
         # data gradient of the n stage-1 convs in one launch: weights concatenated along the contraction axis
         w1t = torch.cat([s[0][0].weight.detach().flip(2, 3).transpose(0, 1) for s in self.seqs], 1).contiguous()   # (c, n*c, 3, 3)
         z = torch.zeros(c, dtype=torch.float32, device=dev)
-        bw1 = dict(direct=pack.pack_conv3x3(w1t, z), wino=pack.pack_conv3x3_winograd(w1t, z))
+        bw1 = tl.ConvForms(direct=tl.Form(*pack.pack_conv3x3(w1t, z)), wino=tl.Form(*pack.pack_conv3x3_winograd(w1t, z)))
         self._forms = dict(grouped=grouped, bw2=bw, bw1=bw1)
         self._step = tl.StepClock.step
         return self._forms
@@ -500,7 +500,7 @@ class _HeadBranches:
         for i, layer in enumerate(self.stage1):
             layer.backward(Act(dmid, c * i, c), need_dx=False)                  # BN+ReLU backward in place, wgrad
         ds = _empty(sv['shape'], dev)
-        ConvBNAct._run3x3(f['bw1'], dmid, n * c, c, 1, ds, 0, 0)
+        tl.launch_conv3x3(f['bw1'], dmid, n * c, c, 1, ds, 0, 0)
         return ds
 
 

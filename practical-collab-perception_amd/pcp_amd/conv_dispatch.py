@@ -1,10 +1,12 @@
 """Which kernel a 3x3 convolution runs on -- the one statement of the rule, for inference (pcdet/models/convnet.py::PackedConv.run) and for
-the training step (train_layers.fused_f4_choice).  Plain ints in, a name out: no tensors, nothing that needs a GPU.
+the training step (train_layers.fused_f4_choice at pack time, train_layers.launch_conv3x3 at the launch).  Plain ints in, a name out: no
+tensors, nothing that needs a GPU.
 
-  conv_algo()        the PCP_CONV_ALGO switch (the only reader of the variable)
-  forms_for()        pack time: which weight forms a layer gets
-  choose_conv3x3()   launch time: one of KERNELS for a layer on a map
-  choose_fused_f4()  the fused F(4x4) part of that rule, which the training step shares
+  conv_algo()             the PCP_CONV_ALGO switch (the only reader of the variable)
+  forms_for()             pack time: which weight forms a layer gets
+  choose_conv3x3()        launch time: one of KERNELS for a layer on a map
+  choose_fused_f4()       the fused F(4x4) part of that rule, which the training step shares
+  choose_train_conv3x3()  launch time in the training step: the fused kernel was named at pack time, the rest is decided per launch
 """
 import os
 from collections import namedtuple
@@ -189,6 +191,22 @@ def choose_conv3x3(algo, cin, cout, stride, forms, B, H, W, ld_in, in_ch_off=0, 
                                    and winograd4_items(B, H, W) * (forms.w4 // 128) >= WINOGRAD4_MIN_WORKGROUPS):
             return 'winograd4'
     if forms.wino is not None and algo != 'direct':
+        if algo == 'winograd' or winograd_items(B, H, W) * (forms.wino // 64) >= WINOGRAD_MIN_WORKGROUPS:
+            return 'winograd'
+    return 'direct'
+
+
+def choose_train_conv3x3(algo, stride, forms, fused, B, H, W, ld_in, in_ch_off, out_ld, out_ch_off):
+    """'bf16x3' | 'winograd4f' | 'winograd4h' | 'winograd' | 'direct' for a 3x3 conv of the training step (forward, or the stride-1 data-gradient
+    conv) on a (B, H, W, ld_in) fp32 map.  forms: Forms with the cout_pad of the b3 and wino forms the layer has.  fused: None | 'winograd4f' |
+    'winograd4h', the kernel train_layers.fused_f4_choice named when the fused form was packed (from the LAYER's input map); only that
+    kernel's own limits -- 16-byte windows, 32-bit buffer offsets -- are left to test here."""
+    if forms.b3 is not None and algo in ('bf16x3', 'bf16') and bf16x3_items(B, H, W, stride) * (forms.b3 // 64) >= B3_MIN_WORKGROUPS:
+        return 'bf16x3'
+    if (fused is not None and stride == 1 and ld_in % 4 == 0 and in_ch_off % 4 == 0 and out_ld % 4 == 0 and out_ch_off % 4 == 0
+            and B * H * W * ld_in * 4 <= WINOGRAD4F_MAX_INPUT_BYTES):
+        return fused
+    if forms.wino is not None and stride == 1 and algo != 'direct':
         if algo == 'winograd' or winograd_items(B, H, W) * (forms.wino // 64) >= WINOGRAD_MIN_WORKGROUPS:
             return 'winograd'
     return 'direct'

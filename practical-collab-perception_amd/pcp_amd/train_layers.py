@@ -2,27 +2,31 @@
 backward needs, `backward(dout)` writes parameter gradients straight into `param.grad` and returns the input gradient.
 
 A conv layer of the trainable branch is  y = conv(x) [+ bias];  a = relu?(bn_train?(y)).
-  forward   conv    -> pcp_conv3x3 / pcp_conv3x3_winograd / pcp_pointwise with the RAW weights (no BN folding, relu = 0)
+  forward   conv    -> with the RAW weights (no BN folding, relu = 0).  3x3, fp32: the kernel conv_dispatch.choose_train_conv3x3 names --
+                       pcp_conv3x3_bf16x3 (opt-in), the fused F(4x4) kernels pcp_conv3x3_winograd4f / _winograd4h (stride 1, chosen at pack
+                       time by fused_f4_choice), pcp_conv3x3_winograd (fused F(2x2), stride 1) or pcp_conv3x3;  3x3 in the bf16 loop
+                       (PCP_CONV_ALGO=bf16, mp_mode()): pcp_mp_conv3x3;  1x1 / k2 s2 kinds: pcp_pointwise, or pcp_mp_pointwise where a
+                       bf16 map arrives in the bf16 loop
             bn      -> pcp_bn_train_stats (batch statistics, running stats updated) + pcp_scale_shift_act
   backward  bn+relu -> pcp_bn_act_backward (in place on the incoming gradient)
             bias    -> pcp_colsum
-            wgrad   -> pcp_conv3x3_wgrad / pcp_pointwise_wgrad (pixel-contraction MFMA GEMMs)
-            dgrad   -> the FORWARD kernels again with flipped / transposed weights (stride-2 3x3: on the zero-dilated gradient)
+            wgrad   -> pcp_conv3x3_wgrad / pcp_mp_conv3x3_wgrad / pcp_pointwise_wgrad (pixel-contraction MFMA GEMMs)
+            dgrad   -> the FORWARD kernels again with flipped / transposed weights (stride-2 3x3: on the zero-dilated gradient, pcp_dilate2x)
+  weights   TrainForms: packed once per optimizer step -- per layer at its first step (pcp_pack_conv3x3, pcp_pack_conv3x3_winograd4,
+            pcp_mp_pack_conv3x3), afterwards every 3x3 layer by ONE launch (pcp_pack_conv3x3_group / pcp_mp_pack_conv3x3_group)
 
 Reference modules these stand for: nn.Conv2d / nn.ConvTranspose2d + nn.BatchNorm2d + nn.ReLU stacks of
 pcdet/models/backbones_2d/base_bev_backbone.py:30-69, dense_heads/center_head.py:24-29,75-82, bev_layers/v2x_fusion_disco.py:11-17,51-63.
 """
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
 from . import lib, ops, pack
 from . import train_ops as tops
-from .conv_dispatch import bf16x3_items, choose_fused_f4, conv_algo, fused_f4_shape, winograd_items
-
-
-B3_MIN_WORKGROUPS = 256        # the bf16 / bf16x3 conv kernels are used where a launch fills the chip (tests lower it)
+from .conv_dispatch import Forms, choose_fused_f4, choose_train_conv3x3, conv_algo, fused_f4_shape
 
 
 def fused_f4_choice(B, H, W, cin, cout):
@@ -134,15 +138,209 @@ class Act:
         return self.t.numel() // self.t.shape[-1]
 
 
-def _zeros_like_cache(cache, key, n, device):
-    z = cache.get(key)
-    if z is None or z.numel() < n or z.device != device:
-        z = torch.zeros(n, dtype=torch.float32, device=device)
-        cache[key] = z
-    return z
+def _bf16_window(a):
+    """the Act as the bf16 kernels read it: bf16 storage, window and row pitch multiples of 8 channels (16 bytes) -- itself where it already
+    is one, else ONE cast into a contiguous copy of the window"""
+    if a.t.dtype != torch.bfloat16 or a.off % 8 or a.t.shape[-1] % 8:
+        return Act(as_bf16(a.t, a.off, a.c), 0, a.c)
+    return a
 
 
 _ZERO_BIAS = {}
+
+
+def _zero_bias(device):
+    z = _ZERO_BIAS.get(device)
+    if z is None:
+        z = _ZERO_BIAS[device] = torch.zeros(2048, dtype=torch.float32, device=device)
+    return z
+
+
+Form = namedtuple('Form', 'w b cout_pad')          # one packed weight form: (weights, bias, cout_pad)
+
+
+class ConvForms:
+    """the packed forms of ONE direction of a conv (forward | data gradient), None where it has none.  3x3: direct (always), wino (fused
+    F(2x2)), b3 (split bf16), f4 (fused F(4x4), packed for the kernel f4_kernel names) -- or mp alone in the bf16 loop.  Pointwise kinds:
+    direct, and mp (its bf16 copy) in the bf16 loop."""
+    __slots__ = ('direct', 'wino', 'b3', 'f4', 'f4_kernel', 'mp')
+
+    def __init__(self, direct=None, wino=None, b3=None, f4=None, f4_kernel=None, mp=None):
+        self.direct, self.wino, self.b3, self.f4, self.f4_kernel, self.mp = direct, wino, b3, f4, f4_kernel, mp
+
+
+# kernel name of conv_dispatch.choose_train_conv3x3 -> (slot of ConvForms, function of pcp_amd.ops, looked up at every call: tests replace them)
+_LAUNCH3X3 = {'direct': ('direct', 'conv3x3'), 'winograd': ('wino', 'conv3x3_winograd'), 'winograd4f': ('f4', 'conv3x3_winograd4f'),
+              'winograd4h': ('f4', 'conv3x3_winograd4h'), 'bf16x3': ('b3', 'conv3x3_bf16x3')}
+
+
+def launch_conv3x3(forms, x, cin, cout, stride, out, in_off, out_off):
+    """the fp32 3x3 conv cin -> cout of a training step (a layer's forward, or a stride-1 data-gradient conv) from x[..., in_off:] into
+    out[..., out_off:], on the kernel conv_dispatch.choose_train_conv3x3 names, with the ConvForms `forms`"""
+    B, H, W, ld_in = x.shape
+    algo = conv_algo()
+    pads = Forms(wino=forms.wino and forms.wino.cout_pad, b3=forms.b3 and forms.b3.cout_pad)
+    name = choose_train_conv3x3(algo, stride, pads, forms.f4_kernel, B, H, W, ld_in, in_off, out.shape[-1], out_off)
+    slot, fn = _LAUNCH3X3[name]
+    w, b, cp = getattr(forms, slot)
+    extra = {}
+    if name in ('direct', 'bf16x3'):                       # the two kernels that also take stride 2
+        extra['stride'] = stride
+    if name == 'bf16x3':
+        extra['plain'] = algo == 'bf16'
+    return getattr(ops, fn)(x, w, b, cin, cout, cp, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off, **extra)
+
+
+class TrainForms:
+    """The packed weight forms of one conv module in the training step.  Cached ON THE MODULE (several layers may share one: the weightor
+    runs once per agent) and rebuilt once per optimizer step, by one of three packers.  The 3x3 forms live in persistent buffers: the first
+    pack of a layer writes them with its own launches and registers them with PACK_GROUP / MP_PACK_GROUP, and from the next step on ONE launch
+    per step rewrites the buffers of every registered layer through their raw pointers."""
+
+    def __init__(self, kind, cin, cout, stride):
+        self.kind, self.cin, self.cout, self.stride = kind, cin, cout, stride
+        self.step = -1                  # StepClock.step the forms were packed at
+        self.f4_key = None              # ((B, H, W), PCP_CONV_ALGO) self.f4 was chosen for
+        self.f4 = (None, None)          # fused_f4_choice of (the forward conv, the data-gradient conv)
+        self.fw = self.bw = None        # ConvForms
+        self.buf = {}                   # (transpose, slot) -> persistent buffer of a 3x3 form; slots direct, wino, b3, 4f, 4h, mp
+
+    def get(self, conv, bhw):
+        """(forward ConvForms, data-gradient ConvForms) of `conv`, current for this optimizer step.  bhw: (B, H, W) of the layer input -- decides
+        whether the fused F(4x4) forms are packed (forward: the conv on that map; data gradient: the stride-1 conv on the same map, for stride
+        2 on the zero-dilated gradient)"""
+        if self._stale(conv, bhw):
+            if self.kind != '3x3':
+                self._pack_pointwise(conv)
+            elif mp_mode() and self.cin % 16 == 0 and self.cout % 16 == 0:
+                self._pack_bf16_3x3(conv)
+            else:
+                self._pack_fp32_3x3(conv)
+            self.step = StepClock.step
+        return self.fw, self.bw
+
+    def _stale(self, conv, bhw):
+        """has the optimizer stepped, or has the fused-F(4x4) choice changed, since the forms were packed"""
+        if self.kind == '3x3' and self.f4_key != (bhw, conv_algo()):
+            self.f4_key = (bhw, conv_algo())
+            f4 = (fused_f4_choice(*bhw, self.cin, self.cout) if self.stride == 1 else None, fused_f4_choice(*bhw, self.cout, self.cin))
+            if f4 != self.f4:
+                # another fused form is needed (another batch / map shape, e.g. the last partial batch): pack per layer once, so that the new
+                # form is packed AND registered -- the group launch only rewrites the forms it was given
+                self.f4, self.step = f4, -1
+                PACK_GROUP.drop((id(conv), False))
+                PACK_GROUP.drop((id(conv), True))
+        return self.step != StepClock.step
+
+    @staticmethod
+    def _in_group(group, conv, w):
+        return group.has((id(conv), False), w.data_ptr()) and group.has((id(conv), True), w.data_ptr())
+
+    def _pack_bf16_3x3(self, conv):
+        """bf16 loop: the bf16 forms (forward + data gradient) from the fp32 master weights"""
+        w = conv.weight.detach()
+        wc = w if w.is_contiguous() else w.contiguous()
+        fo, bo = pack.round_up(self.cout, 64), pack.round_up(self.cin, 64)
+        fwp, bwp = self.buf.get((False, 'mp')), self.buf.get((True, 'mp'))
+        if fwp is not None and self._in_group(MP_PACK_GROUP, conv, w):
+            MP_PACK_GROUP.run_once(StepClock.step, w.device)
+        else:
+            fwp, fo = tops.mp_pack_conv3x3(wc, False, out=fwp)
+            bwp, bo = tops.mp_pack_conv3x3(wc, True, out=bwp)
+            self.buf[False, 'mp'], self.buf[True, 'mp'] = fwp, bwp
+            if PACK_GROUPING and wc.data_ptr() == w.data_ptr():       # the parameter's own storage: later steps go through the group launch
+                MP_PACK_GROUP.add((id(conv), False), conv, wc, False, fwp, fo)
+                MP_PACK_GROUP.add((id(conv), True), conv, wc, True, bwp, bo)
+        zeros = _zero_bias(w.device)
+        b = conv.bias.detach() if conv.bias is not None else None
+        fb = zeros if b is None else (b if fo == self.cout else pack.pad_bias(b, fo))
+        self.fw, self.bw = ConvForms(mp=Form(fwp, fb, fo)), ConvForms(mp=Form(bwp, zeros, bo))
+
+    def _alloc_fp32_3x3(self, dev):
+        """the persistent buffers of the fp32 forms a layer has whatever its map: direct; wino and b3 where the kernels take the shape"""
+        rp = lambda o: pack.round_up(o, 64 if o > 32 else 32)
+        for tr, i, o in ((False, self.cin, self.cout), (True, self.cout, self.cin)):
+            self.buf[tr, 'direct'] = torch.empty((i // 16, 9, rp(o), 16), dtype=torch.float32, device=dev)
+            if (tr or self.stride == 1) and i % pack.WINO_CK == 0 and o >= 48:
+                self.buf[tr, 'wino'] = torch.empty((i // 8, 16, pack.round_up(o, 64), 8), dtype=torch.float32, device=dev)
+            if conv_algo() in ('bf16x3', 'bf16') and i % 16 == 0 and o >= 48:      # opt-in split / plain bf16 arithmetic (conv_bf16x3.hip)
+                self.buf[tr, 'b3'] = torch.empty((i // 16) * pack.round_up(o, 64) * 9 * 16 * 2, dtype=torch.int16, device=dev)
+
+    def _pack_fp32_3x3(self, conv):
+        """the fp32 forms: pcp_pack_conv3x3 writes direct / wino / b3 (one launch per direction), pcp_pack_conv3x3_winograd4 the fused form"""
+        w = conv.weight.detach()
+        dev = w.device
+        if self.fw is not None and self.fw.direct is not None and self._in_group(PACK_GROUP, conv, w):
+            PACK_GROUP.run_once(StepClock.step, dev)         # the forms stay: their buffers were rewritten
+            return
+        buf = self.buf
+        if (False, 'direct') not in buf:
+            self._alloc_fp32_3x3(dev)
+        zeros = _zero_bias(dev)
+        b = conv.bias.detach() if conv.bias is not None else None
+        wc = w.contiguous()
+        dirs = ((False, self.cin, self.cout, self.f4[0]), (True, self.cout, self.cin, self.f4[1]))
+        pad = lambda t: t.shape[2] if t is not None else 0
+        for tr, i, o, _f4 in dirs:
+            d, wi = buf[tr, 'direct'], buf.get((tr, 'wino'))
+            tops.pack_conv3x3(wc, tr, d, pad(d), wi, pad(wi), buf.get((tr, 'b3')), pack.round_up(o, 64))
+        for tr, i, o, f4 in dirs:
+            if f4 is not None:
+                if (tr, f4) not in buf:
+                    buf[tr, f4] = torch.empty((i // 8) * 36 * pack.round_up(o, 64) * 8, dtype=torch.float32, device=dev)
+                tops.pack_conv3x3_winograd4(wc, tr, buf.get((tr, f4)) if f4 == '4f' else None, buf.get((tr, f4)) if f4 == '4h' else None,
+                                            pack.round_up(o, 64))
+        forms = []
+        for tr, i, o, f4 in dirs:
+            def bias(n_pad):                                 # forward: the conv bias, padded (a per-step copy); data gradient: none
+                return zeros if (tr or b is None) else (b if n_pad == o else pack.pad_bias(b, n_pad))
+            f, o64 = ConvForms(), pack.round_up(o, 64)
+            if f4 is not None:
+                f.f4, f.f4_kernel = Form(buf[tr, f4], bias(o64), o64), 'winograd' + f4
+            d, wi, b3 = buf[tr, 'direct'], buf.get((tr, 'wino')), buf.get((tr, 'b3'))
+            f.direct = Form(d, bias(pad(d)), pad(d))
+            if wi is not None:
+                f.wino = Form(wi, bias(pad(wi)), pad(wi))
+            if b3 is not None:
+                f.b3 = Form(b3, bias(o64), o64)
+            forms.append(f)
+        self.fw, self.bw = forms
+        if PACK_GROUPING and b is None and self.fw.b3 is None and self.bw.b3 is None and wc.data_ptr() == w.data_ptr():
+            # the buffers are persistent, no bias is copied and the weight tensor is the parameter's own storage: later steps repack through
+            # the group launch
+            for (tr, i, o, f4), f in zip(dirs, forms):
+                wi = buf.get((tr, 'wino'))
+                PACK_GROUP.add((id(conv), tr), conv, wc, tr, buf[tr, 'direct'], f.direct.cout_pad, wi, pad(wi),
+                               buf[tr, f4] if f4 == '4f' else None, buf[tr, f4] if f4 == '4h' else None, f.f4.cout_pad if f.f4 else 0)
+
+    def _pack_pointwise(self, conv):
+        """the four pointwise kinds: packed by torch (pack.py) every step; in the bf16 loop also as bf16 for pcp_mp_pointwise (used when the
+        layer's input arrives as bf16)"""
+        w = conv.weight.detach()
+        dev = w.device
+        cin, cout, k = self.cin, self.cout, self.kind
+        zeros = _zero_bias(dev)
+        fb = conv.bias.detach() if conv.bias is not None else zeros[:cout]
+        zb = zeros[:cin]
+        if k == 'plain':
+            m = w.reshape(cout, cin)
+            fw, bw = pack.pack_plain(m, fb), pack.pack_plain(m.t().contiguous(), zb)
+        elif k == 'plainT':
+            m = w.reshape(cin, cout)
+            fw, bw = pack.pack_plain(m.t().contiguous(), fb), pack.pack_plain(m.contiguous(), zb)
+        elif k == 's2d':
+            fw, bw = pack.pack_conv2x2_s2(w, fb), pack.pack_convT2x2_s2(w, zb)     # (cout, cin, 2, 2) read as a ConvTranspose2d weight
+        else:  # d2s
+            fw, bw = pack.pack_convT2x2_s2(w, fb), pack.pack_conv2x2_s2(w, zb)     # (cin, cout, 2, 2) read as a Conv2d weight
+        self.fw, self.bw = ConvForms(direct=Form(*fw)), ConvForms(direct=Form(*bw))
+        if mp_mode() and dev.type == 'cuda':
+            for f, i, o in ((self.fw, cin, cout), (self.bw, cout, cin)):
+                if tops.mp_pointwise_ok(None, i, o, f.direct.cout_pad, 8, 8):
+                    f.mp = Form(f.direct.w.to(torch.bfloat16), f.direct.b, f.direct.cout_pad)
+
+
+_PW_FORWARD = {'plain': lib.PW_PLAIN, 'plainT': lib.PW_PLAIN, 's2d': lib.PW_SPACE2DEPTH, 'd2s': lib.PW_DEPTH2SPACE}
+_PW_BACKWARD = {'plain': lib.PW_PLAIN, 'plainT': lib.PW_PLAIN, 's2d': lib.PW_DEPTH2SPACE, 'd2s': lib.PW_SPACE2DEPTH}
 
 
 class ConvBNAct:
@@ -161,195 +359,17 @@ class ConvBNAct:
         if self.kind is None:
             raise NotImplementedError('%s: conv k=%d s=%d has no training kernel' % (name, k, s))
         self.stride = s if self.kind == '3x3' else 1
-        self._fw = self._bw = None
-        self._fw_mp = self._bw_mp = None
+        self._fw = self._bw = None      # ConvForms of the current step
+        self._mpw = False               # a pointwise layer whose last forward ran in the bf16 loop
         self.saved = None
         self.vec = None
 
-    # ---- weight forms ----------------------------------------------------------------------------------------------------
-    # cached ON THE CONV MODULE (several layer instances may share one module: the weightor runs once per agent) and rebuilt
-    # once per optimizer step; 3x3 layouts are written by pcp_pack_conv3x3 into persistent buffers (one launch per direction)
-    def _repack(self, bhw=None):
-        """bhw: (B, H, W) of the layer input -- decides, once, whether the fused F(4x4) forms are packed (forward: the conv on that map;
-        backward: the data-gradient conv on the same map, for stride 2 on the zero-dilated gradient)"""
-        cache = getattr(self.conv, '_pcp_train_pack', None)
-        if cache is None:
-            cache = self.conv._pcp_train_pack = dict(step=-1)
-        f4_key = (tuple(bhw), conv_algo()) if bhw is not None and self.kind == '3x3' else None
-        if f4_key is not None and cache.get('f4_key') != f4_key:
-            cache['f4_key'] = f4_key
-            f4_new = (fused_f4_choice(*bhw, self.cin, self.cout) if self.stride == 1 else None, fused_f4_choice(*bhw, self.cout, self.cin))
-            if f4_new != cache.get('f4'):
-                # another fused-F(4x4) form is needed (another batch / map shape, e.g. the last partial batch): take the slow path once so
-                # the new form is packed AND registered -- the group launch only repacks the forms it was given
-                cache['f4'] = f4_new
-                cache['step'] = -1
-                if cache.get('grouped'):
-                    PACK_GROUP.drop((id(self.conv), False))
-                    PACK_GROUP.drop((id(self.conv), True))
-                    cache['grouped'] = False
-        if cache['step'] == StepClock.step:
-            self._fw, self._bw = cache['fw'], cache['bw']
-            self._fw_mp, self._bw_mp = cache.get('fw_mp'), cache.get('bw_mp')
-            return
-        self._fw_mp = self._bw_mp = None
-        if self.kind == '3x3' and mp_mode() and self.cin % 16 == 0 and self.cout % 16 == 0:
-            # bf16 weight forms (forward + data gradient) from the fp32 master weights, persistent buffers, two small launches per step
-            w = self.conv.weight.detach()
-            wc = w if w.is_contiguous() else w.contiguous()
-            mpb = cache.setdefault('mp', {})
-            grouped = (PACK_GROUPING and wc.data_ptr() == w.data_ptr() and 'fw' in mpb and MP_PACK_GROUP.has((id(self.conv), False), w.data_ptr())
-                       and MP_PACK_GROUP.has((id(self.conv), True), w.data_ptr()))
-            if grouped:
-                # steps after the first: ONE launch repacks every registered layer, issued by whichever layer asks first in a step
-                if MP_PACK_GROUP.step != StepClock.step:
-                    MP_PACK_GROUP.run(w.device)
-                    MP_PACK_GROUP.step = StepClock.step
-                fwp, bwp = mpb['fw'], mpb['bw']
-                fo, bo = pack.round_up(self.cout, 64), pack.round_up(self.cin, 64)
-            else:
-                fwp, fo = tops.mp_pack_conv3x3(wc, False, out=mpb.get('fw'))
-                bwp, bo = tops.mp_pack_conv3x3(wc, True, out=mpb.get('bw'))
-                mpb['fw'], mpb['bw'] = fwp, bwp
-                if PACK_GROUPING and wc.data_ptr() == w.data_ptr():          # the parameter's own storage: later steps go through the group launch
-                    MP_PACK_GROUP.add((id(self.conv), False), self.conv, wc, False, fwp, fo)
-                    MP_PACK_GROUP.add((id(self.conv), True), self.conv, wc, True, bwp, bo)
-            zeros = _zeros_like_cache(_ZERO_BIAS, w.device, 2048, w.device)
-            b = self.conv.bias.detach() if self.conv.bias is not None else None
-            fb = zeros if b is None else (b if fo == self.cout else pack.pad_bias(b, fo))
-            cache['fw'], cache['bw'], cache['step'] = dict(mp=(fwp, fb, fo)), dict(mp=(bwp, zeros, bo)), StepClock.step
-            self._fw, self._bw = cache['fw'], cache['bw']
-            return
-        if (self.kind == '3x3' and cache.get('grouped') and PACK_GROUP.has((id(self.conv), False))
-                and cache.get('w_ptr') == self.conv.weight.data_ptr()):
-            # steps after the first: ONE launch repacks every registered 3x3 layer, issued by whichever layer asks first in a step
-            if PACK_GROUP.step != StepClock.step:
-                PACK_GROUP.run(self.conv.weight.device)
-                PACK_GROUP.step = StepClock.step
-            cache['step'] = StepClock.step
-            self._fw, self._bw = cache['fw'], cache['bw']
-            return
-        w = self.conv.weight.detach()
-        dev = w.device
-        zeros = _zeros_like_cache(_ZERO_BIAS, dev, 2048, dev)
-        b = self.conv.bias.detach() if self.conv.bias is not None else None
-        k = self.kind
-
-        def bias_for(n_pad, n):
-            if b is None:
-                return zeros
-            return b if n_pad == n else pack.pad_bias(b, n_pad)
-        if k == '3x3':
-            if 'buf' not in cache:
-                rp = lambda o: pack.round_up(o, 64 if o > 32 else 32)
-                bufs = dict(fw_d=torch.empty((self.cin // 16, 9, rp(self.cout), 16), dtype=torch.float32, device=dev),
-                            bw_d=torch.empty((self.cout // 16, 9, rp(self.cin), 16), dtype=torch.float32, device=dev))
-                if self.stride == 1 and self.cin % pack.WINO_CK == 0 and self.cout >= 48:
-                    bufs['fw_w'] = torch.empty((self.cin // 8, 16, pack.round_up(self.cout, 64), 8), dtype=torch.float32, device=dev)
-                if self.cout % pack.WINO_CK == 0 and self.cin >= 48:
-                    bufs['bw_w'] = torch.empty((self.cout // 8, 16, pack.round_up(self.cin, 64), 8), dtype=torch.float32, device=dev)
-                if conv_algo() in ('bf16x3', 'bf16'):  # opt-in split / plain bf16 arithmetic (conv_bf16x3.hip)
-                    if self.cin % 16 == 0 and self.cout >= 48:
-                        bufs['fw_3'] = torch.empty((self.cin // 16) * pack.round_up(self.cout, 64) * 9 * 16 * 2, dtype=torch.int16, device=dev)
-                    if self.cout % 16 == 0 and self.cin >= 48:
-                        bufs['bw_3'] = torch.empty((self.cout // 16) * pack.round_up(self.cin, 64) * 9 * 16 * 2, dtype=torch.int16, device=dev)
-                cache['buf'] = bufs
-            bufs = cache['buf']
-            wc = w.contiguous()
-            fo, bo = bufs['fw_d'].shape[2], bufs['bw_d'].shape[2]
-            fww, bww = bufs.get('fw_w'), bufs.get('bw_w')
-            f3, b3 = bufs.get('fw_3'), bufs.get('bw_3')
-            tops.pack_conv3x3(wc, False, bufs['fw_d'], fo, fww, fww.shape[2] if fww is not None else 0, f3, pack.round_up(self.cout, 64))
-            tops.pack_conv3x3(wc, True, bufs['bw_d'], bo, bww, bww.shape[2] if bww is not None else 0, b3, pack.round_up(self.cin, 64))
-            f4 = cache.get('f4', (None, None))
-            f4fw = f4bw = None
-            for tag, kind, transpose, o in (('fw_4', f4[0], False, self.cout), ('bw_4', f4[1], True, self.cin)):
-                if kind is None:
-                    continue
-                i_ch = self.cin if not transpose else self.cout
-                op4 = pack.round_up(o, 64)
-                key = tag + kind
-                if key not in bufs:
-                    bufs[key] = torch.empty((i_ch // 8) * 36 * op4 * 8, dtype=torch.float32, device=dev)
-                tops.pack_conv3x3_winograd4(wc, transpose, bufs[key] if kind == '4f' else None, bufs[key] if kind == '4h' else None, op4)
-                form = (kind, bufs[key], bias_for(op4, self.cout) if not transpose else zeros, op4)
-                if transpose:
-                    f4bw = form
-                else:
-                    f4fw = form
-            fw = dict(direct=(bufs['fw_d'], bias_for(fo, self.cout), fo))
-            if fww is not None:
-                fw['wino'] = (fww, bias_for(fww.shape[2], self.cout), fww.shape[2])
-            if f3 is not None:
-                fw['b3'] = (f3, bias_for(pack.round_up(self.cout, 64), self.cout), pack.round_up(self.cout, 64))
-            cache['grouped'] = False
-            if f3 is None and b3 is None and b is None and wc.data_ptr() == w.data_ptr() and PACK_GROUPING:      # (a padded bias is a per-step copy)
-                # the buffers are persistent and the weight tensor is the parameter's own storage: later steps repack through the group launch
-                k4 = lambda form, kind: form[1] if (form is not None and form[0] == kind) else None
-                PACK_GROUP.add((id(self.conv), False), self.conv, wc, False, bufs['fw_d'], fo, fww, fww.shape[2] if fww is not None else 0,
-                               k4(f4fw, '4f'), k4(f4fw, '4h'), f4fw[3] if f4fw is not None else 0)
-                PACK_GROUP.add((id(self.conv), True), self.conv, wc, True, bufs['bw_d'], bo, bww, bww.shape[2] if bww is not None else 0,
-                               k4(f4bw, '4f'), k4(f4bw, '4h'), f4bw[3] if f4bw is not None else 0)
-                cache['grouped'] = True
-                cache['w_ptr'] = wc.data_ptr()
-            if f4fw is not None:
-                fw['f4'] = f4fw
-            bw = dict(direct=(bufs['bw_d'], zeros, bo))
-            if f4bw is not None:
-                bw['f4'] = f4bw
-            if bww is not None:
-                bw['wino'] = (bww, zeros, bww.shape[2])
-            if b3 is not None:
-                bw['b3'] = (b3, zeros, pack.round_up(self.cin, 64))
-        else:
-            zb = lambda n: zeros[:n]
-            fb = lambda n: (b if b is not None else zeros[:n])
-            if k == 'plain':
-                m = w.reshape(self.cout, self.cin)
-                fw = pack.pack_plain(m, fb(self.cout))
-                bw = pack.pack_plain(m.t().contiguous(), zb(self.cin))
-            elif k == 'plainT':
-                m = w.reshape(self.cin, self.cout)
-                fw = pack.pack_plain(m.t().contiguous(), fb(self.cout))
-                bw = pack.pack_plain(m.contiguous(), zb(self.cin))
-            elif k == 's2d':
-                fw = pack.pack_conv2x2_s2(w, fb(self.cout))
-                bw = pack.pack_convT2x2_s2(w, zb(self.cin))             # (cout, cin, 2, 2) read as a ConvTranspose2d weight
-            else:  # d2s
-                fw = pack.pack_convT2x2_s2(w, fb(self.cout))
-                bw = pack.pack_conv2x2_s2(w, zb(self.cin))              # (cin, cout, 2, 2) read as a Conv2d weight
-        cache['fw'], cache['bw'], cache['step'] = fw, bw, StepClock.step
-        self._fw, self._bw = fw, bw
-        cache['fw_mp'] = cache['bw_mp'] = None
-        if k != '3x3' and mp_mode() and dev.type == 'cuda':
-            # bf16 loop: the same packed forms as bf16 for pcp_mp_pointwise (used when the layer's input arrives as bf16)
-            if tops.mp_pointwise_ok(None, self.cin, self.cout, fw[2], 8, 8):
-                cache['fw_mp'] = (fw[0].to(torch.bfloat16), fw[1], fw[2])
-            if tops.mp_pointwise_ok(None, self.cout, self.cin, bw[2], 8, 8):
-                cache['bw_mp'] = (bw[0].to(torch.bfloat16), bw[1], bw[2])
-        self._fw_mp, self._bw_mp = cache['fw_mp'], cache['bw_mp']
-
-    # ---- launches --------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _run3x3(forms, x, cin, cout, stride, out, in_off, out_off):
-        B, H, W, _ = x.shape
-        algo = conv_algo()                                              # auto | direct | winograd | bf16x3 | bf16 (same switch as inference)
-        if algo in ('bf16x3', 'bf16') and 'b3' in forms:
-            if bf16x3_items(B, H, W, stride) * (forms['b3'][2] // 64) >= B3_MIN_WORKGROUPS:
-                w3, b3, cp3 = forms['b3']
-                return ops.conv3x3_bf16x3(x, w3, b3, cin, cout, cp3, stride=stride, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off,
-                                          plain=(algo == 'bf16'))
-        if (stride == 1 and 'f4' in forms and x.shape[-1] % 4 == 0 and in_off % 4 == 0 and out.shape[-1] % 4 == 0 and out_off % 4 == 0
-                and x.numel() * 4 <= 0x7fffffff):           # the fused kernels' own limits (16-byte windows, 32-bit buffer offsets)
-            kind, u, ub, ucp = forms['f4']
-            run = ops.conv3x3_winograd4h if kind == '4h' else ops.conv3x3_winograd4f
-            return run(x, u, ub, cin, cout, ucp, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off)
-        big = winograd_items(B, H, W) * (forms['wino'][2] // 64) >= 256 if 'wino' in forms else False
-        if stride == 1 and 'wino' in forms and algo != 'direct' and (big or algo == 'winograd'):
-            u, ub, ucp = forms['wino']
-            return ops.conv3x3_winograd(x, u, ub, cin, cout, ucp, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off)
-        w, b, cp = forms['direct']
-        return ops.conv3x3(x, w, b, cin, cout, cp, stride=stride, relu=False, out=out, in_ch_off=in_off, out_ch_off=out_off)
+    def _current_forms(self, x):
+        """the weight forms of this step, for a layer input x (a tensor): self._fw, self._bw"""
+        forms = getattr(self.conv, '_pcp_train_forms', None)
+        if forms is None:
+            forms = self.conv._pcp_train_forms = TrainForms(self.kind, self.cin, self.cout, self.stride)
+        self._fw, self._bw = forms.get(self.conv, tuple(x.shape[:3]))
 
     def mp_pointwise_capable(self):
         """a pointwise layer whose forward AND data-gradient shapes pcp_mp_pointwise takes (it then reads and writes bf16 maps)"""
@@ -371,22 +391,20 @@ class ConvBNAct:
         """x: Act.  out: Act to write the activation into (a channel window of a wider buffer) or None.  Returns Act.
         Mixed-precision mode (mp_mode()): a 3x3 layer takes fp32 or bf16 input, keeps its conv output as bf16 and writes its activation
         as bf16 unless `out` / `out_dtype` say float32 (a consumer that is an fp32-only kernel); the other kinds compute in fp32."""
-        self._repack(tuple(x.t.shape[:3]))
+        self._current_forms(x.t)
+        fw = self._fw
         dev = x.t.device
         shp = self.out_shape(x)
         need_post = self.bn is not None or self.relu
         k = self.kind
-        mp = k == '3x3' and 'mp' in self._fw
+        mp = k == '3x3' and fw.mp is not None
         # a pointwise layer joins the bf16 loop when its input ARRIVES as bf16 (the up / down-sampling layers behind the bf16 3x3 blocks);
         # fp32 inputs (the fusion module's concatenated maps) keep the fp32 kernels
-        mpw = (k != '3x3' and self._fw_mp is not None and self._bw_mp is not None and x.t.dtype == torch.bfloat16 and x.off % 8 == 0
+        mpw = (k != '3x3' and fw.mp is not None and self._bw.mp is not None and x.t.dtype == torch.bfloat16 and x.off % 8 == 0
                and x.t.shape[-1] % 8 == 0 and (out is None or (out.off % 8 == 0 and out.t.shape[-1] % 8 == 0)))
-        if mp:
-            if x.t.dtype != torch.bfloat16 or x.off % 8 or x.t.shape[-1] % 8:
-                x = Act(as_bf16(x.t, x.off, x.c).contiguous(), 0, x.c)   # one cast; the fast kernel and the weight gradient both read the bf16 copy
-            act_dtype = out.t.dtype if out is not None else (out_dtype or torch.bfloat16)
-            y_dtype = torch.bfloat16 if need_post else act_dtype
-        elif mpw:
+        if mp or mpw:
+            if mp:
+                x = _bf16_window(x)                                      # the fast kernel and the weight gradient both read the bf16 copy
             act_dtype = out.t.dtype if out is not None else (out_dtype or torch.bfloat16)
             y_dtype = torch.bfloat16 if need_post else act_dtype
         else:
@@ -398,18 +416,13 @@ class ConvBNAct:
         y_t = torch.empty(shp + (self.cout,), dtype=y_dtype, device=dev) if (need_post or out is None) else None
         y = Act(y_t, 0, self.cout) if y_t is not None else out
         if mp:
-            wp, bp, cp = self._fw['mp']
+            wp, bp, cp = fw.mp
             tops.mp_conv3x3(x.t, wp, bp, self.cin, self.cout, cp, stride=self.stride, relu=False, out=y.t, in_ch_off=x.off, out_ch_off=y.off)
         elif k == '3x3':
-            self._run3x3(self._fw, x.t, self.cin, self.cout, self.stride, y.t, x.off, y.off)
+            launch_conv3x3(fw, x.t, self.cin, self.cout, self.stride, y.t, x.off, y.off)
         else:
-            mode = {'plain': lib.PW_PLAIN, 'plainT': lib.PW_PLAIN, 's2d': lib.PW_SPACE2DEPTH, 'd2s': lib.PW_DEPTH2SPACE}[k]
-            if mpw:
-                w, b, cp = self._fw_mp
-                tops.mp_pointwise(x.t, w, b, mode, self.cin, self.cout, cp, relu=False, out=y.t, in_ch_off=x.off, out_ch_off=y.off)
-            else:
-                w, b, cp = self._fw
-                ops.pointwise(x.t, w, b, mode, self.cin, self.cout, cp, relu=False, out=y.t, in_ch_off=x.off, out_ch_off=y.off)
+            (w, b, cp), run = (fw.mp, tops.mp_pointwise) if mpw else (fw.direct, ops.pointwise)
+            run(x.t, w, b, _PW_FORWARD[k], self.cin, self.cout, cp, relu=False, out=y.t, in_ch_off=x.off, out_ch_off=y.off)
         self._mpw = mpw
         if not need_post:
             self.saved = (x, y)
@@ -430,6 +443,29 @@ class ConvBNAct:
         self.saved = (x, y)
         return out
 
+    def _weight_grad(self, x, dy, mp, accumulate):
+        """dL/d conv.weight from the saved input x and the conv-output gradient dy (both Act), into conv.weight.grad"""
+        k, cin, cout = self.kind, self.cin, self.cout
+        gw = ensure_grad(self.conv.weight)
+        if k == '3x3':
+            wgrad = tops.mp_conv3x3_wgrad if mp else tops.conv3x3_wgrad
+            wgrad(x.t, dy.t, cin, cout, self.stride, gw, accumulate=accumulate, x_ch_off=x.off, dy_ch_off=dy.off)
+        elif k == 'plain':
+            tops.pointwise_wgrad(tops.rowmap(dy.t, cout, dy.off), tops.rowmap(x.t, cin, x.off), x.rows, gw.view(cout, cin), accumulate=accumulate)
+        elif k == 'plainT':
+            tops.pointwise_wgrad(tops.rowmap(x.t, cin, x.off), tops.rowmap(dy.t, cout, dy.off), x.rows, gw.view(cin, cout), accumulate=accumulate)
+        else:
+            # k2 s2: one GEMM per tap, between the coarse map and the tap's lattice of the fine one.  s2d: fine x, coarse dy, (cout, cin) taps;
+            # d2s: coarse x, fine dy, (cin, cout) taps
+            (n, fine), (m, coarse) = ((cin, x), (cout, dy)) if k == 's2d' else ((cout, dy), (cin, x))
+            H, W = coarse.t.shape[1], coarse.t.shape[2]
+            tmp = torch.empty((4, m, n), dtype=torch.float32, device=dy.t.device)
+            for tap in range(4):
+                tops.pointwise_wgrad(tops.rowmap(coarse.t, m, coarse.off), tops.rowmap(fine.t, n, fine.off, lattice=(H, W, tap // 2, tap % 2)),
+                                     coarse.rows, tmp[tap])
+            g = tmp.permute(1, 2, 0).reshape(m, n, 2, 2)
+            gw.add_(g) if accumulate else gw.copy_(g)
+
     def backward(self, dout, need_dx=True, accumulate=False, dx_out=None, dx_dtype=None):
         """dout: Act (gradient of the layer output; overwritten in place by the gradient of the conv output when the storage types allow).
         Returns Act dx (or None).  accumulate: add to param.grad instead of overwriting (a module applied several times).
@@ -438,79 +474,40 @@ class ConvBNAct:
         x, y = self.saved
         dev = dout.t.device
         k = self.kind
-        mp = (k == '3x3' and 'mp' in self._fw) or (k != '3x3' and getattr(self, '_mpw', False))     # bf16 operands for both gradient GEMMs
+        mp = self._fw.mp is not None if k == '3x3' else self._mpw       # bf16 operands for both gradient GEMMs
         if not mp and dout.t.dtype != torch.float32:
             dout = Act(as_f32(dout.t, dout.off, dout.c), 0, dout.c)
-        dy = dout
         if self.bn is not None:
             g_w, g_b = ensure_grad(self.bn.weight), ensure_grad(self.bn.bias)
             # in place on dout, whatever its storage type (callers rely on it: the CenterHead runs ONE data-gradient conv over the five
             # branch gradients it handed to five layers)
             tops.bn_act_backward(dout.t, y.t, self.cout, self.vec, self.relu, g_w, g_b, accumulate=accumulate, dout_ch_off=dout.off,
                                  x_ch_off=y.off)
-            if mp and (dout.t.dtype != torch.bfloat16 or dout.off % 8 or dout.t.shape[-1] % 8):
-                dy = Act(as_bf16(dout.t, dout.off, dout.c).contiguous(), 0, dout.c)
         elif self.relu:
             raise NotImplementedError('%s: ReLU without BatchNorm is handled by the fused fusion kernels' % self.name)
-        elif mp and (dout.t.dtype != torch.bfloat16 or dout.off % 8 or dout.t.shape[-1] % 8):
-            dy = Act(as_bf16(dout.t, dout.off, dout.c).contiguous(), 0, dout.c)
-        if mp and (dy.off % 8 or dy.t.shape[-1] % 8):
-            dy = Act(dy.t[..., dy.off:dy.off + dy.c].contiguous(), 0, dy.c)
+        dy = _bf16_window(dout) if mp else dout
         if self.conv.bias is not None:
             tops.colsum(dy.t, self.cout, ensure_grad(self.conv.bias), accumulate=accumulate, ch_off=dy.off)
-        gw = ensure_grad(self.conv.weight)
-        rows = x.rows
-        if mp and k == '3x3':
-            tops.mp_conv3x3_wgrad(x.t, dy.t, self.cin, self.cout, self.stride, gw, accumulate=accumulate, x_ch_off=x.off, dy_ch_off=dy.off)
-        elif k == '3x3':
-            tops.conv3x3_wgrad(x.t, dy.t, self.cin, self.cout, self.stride, gw, accumulate=accumulate, x_ch_off=x.off, dy_ch_off=dy.off)
-        elif k == 'plain':
-            tops.pointwise_wgrad(tops.rowmap(dy.t, self.cout, dy.off), tops.rowmap(x.t, self.cin, x.off), rows,
-                                 gw.view(self.cout, self.cin), accumulate=accumulate)
-        elif k == 'plainT':
-            tops.pointwise_wgrad(tops.rowmap(x.t, self.cin, x.off), tops.rowmap(dy.t, self.cout, dy.off), rows,
-                                 gw.view(self.cin, self.cout), accumulate=accumulate)
-        elif k == 's2d':
-            Ho, Wo = dy.t.shape[1], dy.t.shape[2]
-            tmp = torch.empty((4, self.cout, self.cin), dtype=torch.float32, device=dev)
-            for tap in range(4):
-                tops.pointwise_wgrad(tops.rowmap(dy.t, self.cout, dy.off),
-                                     tops.rowmap(x.t, self.cin, x.off, lattice=(Ho, Wo, tap // 2, tap % 2)), dy.rows, tmp[tap])
-            g = tmp.permute(1, 2, 0).reshape(self.cout, self.cin, 2, 2)
-            gw.add_(g) if accumulate else gw.copy_(g)
-        else:  # d2s
-            H, W = x.t.shape[1], x.t.shape[2]
-            tmp = torch.empty((4, self.cin, self.cout), dtype=torch.float32, device=dev)
-            for tap in range(4):
-                tops.pointwise_wgrad(tops.rowmap(x.t, self.cin, x.off),
-                                     tops.rowmap(dy.t, self.cout, dy.off, lattice=(H, W, tap // 2, tap % 2)), rows, tmp[tap])
-            g = tmp.permute(1, 2, 0).reshape(self.cin, self.cout, 2, 2)
-            gw.add_(g) if accumulate else gw.copy_(g)
+        self._weight_grad(x, dy, mp, accumulate)
         if not need_dx:
             return None
-        self._repack(tuple(x.t.shape[:3]))
+        self._current_forms(x.t)
+        bw = self._bw
         if dx_out is None:
             dt = (dx_dtype or torch.bfloat16) if mp else torch.float32
             dx_out = Act(torch.empty(tuple(x.t.shape[:-1]) + (self.cin,), dtype=dt, device=dev), 0, self.cin)
-        if mp and k != '3x3':
-            mode = {'plain': lib.PW_PLAIN, 'plainT': lib.PW_PLAIN, 's2d': lib.PW_DEPTH2SPACE, 'd2s': lib.PW_SPACE2DEPTH}[k]
-            w, b, cp = self._bw_mp
-            tops.mp_pointwise(dy.t, w, b, mode, self.cout, self.cin, cp, relu=False, out=dx_out.t, in_ch_off=dy.off, out_ch_off=dx_out.off)
-        elif mp:
-            src = dy
-            if self.stride == 2:
-                src = Act(tops.dilate2x(dy.t, self.cout, ch_off=dy.off), 0, self.cout)
-            wp, bp, cp = self._bw['mp']
-            tops.mp_conv3x3(src.t, wp, bp, self.cout, self.cin, cp, stride=1, relu=False, out=dx_out.t, in_ch_off=src.off, out_ch_off=dx_out.off)
-        elif k == '3x3':
-            src = dy
-            if self.stride == 2:
-                src = Act(tops.dilate2x(dy.t, self.cout, ch_off=dy.off), 0, self.cout)
-            self._run3x3(self._bw, src.t, self.cout, self.cin, 1, dx_out.t, src.off, dx_out.off)
+        if k == '3x3':
+            # the forward kernels again with flipped / transposed weights; stride 2: a stride-1 conv on the zero-dilated gradient
+            src = dy if self.stride == 1 else Act(tops.dilate2x(dy.t, self.cout, ch_off=dy.off), 0, self.cout)
+            if mp:
+                wp, bp, cp = bw.mp
+                tops.mp_conv3x3(src.t, wp, bp, self.cout, self.cin, cp, stride=1, relu=False, out=dx_out.t, in_ch_off=src.off,
+                                out_ch_off=dx_out.off)
+            else:
+                launch_conv3x3(bw, src.t, self.cout, self.cin, 1, dx_out.t, src.off, dx_out.off)
         else:
-            mode = {'plain': lib.PW_PLAIN, 'plainT': lib.PW_PLAIN, 's2d': lib.PW_DEPTH2SPACE, 'd2s': lib.PW_SPACE2DEPTH}[k]
-            w, b, cp = self._bw
-            ops.pointwise(dy.t, w, b, mode, self.cout, self.cin, cp, relu=False, out=dx_out.t, in_ch_off=dy.off, out_ch_off=dx_out.off)
+            (w, b, cp), run = (bw.mp, tops.mp_pointwise) if mp else (bw.direct, ops.pointwise)
+            run(dy.t, w, b, _PW_BACKWARD[k], self.cout, self.cin, cp, relu=False, out=dx_out.t, in_ch_off=dy.off, out_ch_off=dx_out.off)
         return dx_out
 
 

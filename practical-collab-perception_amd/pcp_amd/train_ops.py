@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the training half of the C ABI (include/pcp_hip_train.h).  Same rules as ops.py: CUDA tensors
 only, torch supplies memory and the stream, no eager fallback."""
 import ctypes
+import weakref
 
 import torch
 
@@ -23,6 +24,59 @@ class Scratch:
 
 _BN_WS = Scratch()
 _WG_WS = Scratch()
+
+
+class _RepackGroup:
+    """Per-step weight repacking of many layers by ONE launch from a device-side job table.  jobs: key -> (weak reference to the owner, job
+    struct, the tensors its raw pointers name, kept alive).  The owner is the conv module that caches the destination buffers: jobs of
+    collected modules are dropped before the next launch.  Subclasses name the job struct and the two library symbols, and build jobs in add()."""
+    JOB = BLOCKS = LAUNCH = None
+
+    def __init__(self):
+        self.jobs = {}
+        self.dirty = True           # the device table is behind the jobs
+        self.table = None
+        self.total = 0
+        self.step = -1              # the optimizer step the launch last ran in
+
+    def _register(self, key, owner, job, tensors):
+        if getattr(_lib.load(), self.BLOCKS)(ctypes.byref(job)) <= 0:
+            raise _lib.PcpError('%s: invalid job' % self.LAUNCH)
+        self.jobs[key] = (weakref.ref(owner), job, tensors)
+        self.dirty = True
+
+    def has(self, key, w_ptr):
+        """a live job under `key` that reads the weights at w_ptr"""
+        e = self.jobs.get(key)
+        return e is not None and e[0]() is not None and e[1].w == w_ptr
+
+    def drop(self, key):
+        if self.jobs.pop(key, None) is not None:
+            self.dirty = True
+
+    def run(self, device):
+        L = _lib.load()
+        for k in [k for k, e in self.jobs.items() if e[0]() is None]:
+            self.drop(k)
+        if not self.jobs:
+            return
+        if self.dirty or self.table is None or self.table.device != device:
+            arr = (self.JOB * len(self.jobs))()
+            start = 0
+            for i, (_o, j, _t) in enumerate(self.jobs.values()):
+                j.block_start = start
+                start += getattr(L, self.BLOCKS)(ctypes.byref(j))
+                arr[i] = j
+            self.total = start
+            self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+            self.dirty = False
+        check(getattr(L, self.LAUNCH)(_p(self.table), len(self.jobs), self.total, _stream()), self.LAUNCH)
+
+    def run_once(self, step, device):
+        """once per optimizer step, by whichever layer asks first"""
+        if self.step != step:
+            self.run(device)
+            self.step = step
 
 
 def _rows_c(x):
@@ -234,48 +288,14 @@ def mp_pack_conv3x3(w, transpose=False, out=None, fold_scale=None):
     return out, opad
 
 
-class MpPackGroup:
+class MpPackGroup(_RepackGroup):
     """the bf16 weight forms of every 3x3 layer (forward + data gradient) rebuilt by ONE launch per optimizer step (pcp_mp_pack_conv3x3_group:
-    55 four-microsecond launches per DiscoNet iteration otherwise).  Jobs hold weak references to their conv modules."""
-
-    def __init__(self):
-        self.jobs = {}
-        self.dirty = True
-        self.table = None
-        self.total = 0
-        self.step = -1
+    55 four-microsecond launches per DiscoNet iteration otherwise)."""
+    JOB, BLOCKS, LAUNCH = _lib.MpPackJob, 'pcp_mp_pack_conv3x3_group_blocks', 'pcp_mp_pack_conv3x3_group'
 
     def add(self, key, owner, w, transpose, packed, out_pad):
-        import weakref
         j = _lib.MpPackJob(w.data_ptr(), packed.data_ptr(), int(w.shape[0]), int(w.shape[1]), 1 if transpose else 0, int(out_pad), 0, 0)
-        if _lib.load().pcp_mp_pack_conv3x3_group_blocks(ctypes.byref(j)) <= 0:
-            raise _lib.PcpError('pcp_mp_pack_conv3x3_group: invalid job')
-        self.jobs[key] = (weakref.ref(owner), j, (w, packed))
-        self.dirty = True
-
-    def has(self, key, w_ptr):
-        e = self.jobs.get(key)
-        return e is not None and e[0]() is not None and e[1].w == w_ptr
-
-    def run(self, device):
-        L = _lib.load()
-        dead = [k for k, e in self.jobs.items() if e[0]() is None]
-        for k in dead:
-            del self.jobs[k]
-            self.dirty = True
-        if not self.jobs:
-            return
-        if self.dirty or self.table is None or self.table.device != device:
-            arr = (_lib.MpPackJob * len(self.jobs))()
-            start = 0
-            for i, (_o, j, _t) in enumerate(self.jobs.values()):
-                j.block_start = start
-                start += L.pcp_mp_pack_conv3x3_group_blocks(ctypes.byref(j))
-                arr[i] = j
-            self.total = start
-            self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-            self.dirty = False
-        check(L.pcp_mp_pack_conv3x3_group(_p(self.table), len(self.jobs), self.total, _stream()), 'pcp_mp_pack_conv3x3_group')
+        self._register(key, owner, j, (w, packed))
 
 
 def mp_conv3x3(x, packed, bias, cin, cout, cout_pad, stride=1, relu=False, out=None, out_dtype=torch.bfloat16, in_ch_off=0, out_ch_off=0):
@@ -721,55 +741,15 @@ def pack_conv3x3_winograd4(w, transpose, u4f=None, u4h=None, opad=0):
           'pcp_pack_conv3x3_winograd4')
 
 
-class PackGroup:
+class PackGroup(_RepackGroup):
     """every 3x3 layer of the trainable branch repacked by ONE launch per optimizer step (pcp_pack_conv3x3_group).  A job = (weight, direction)
-    with its persistent destination buffers; `owner` is weakly referenced (the conv module that caches the buffers): jobs of collected
-    modules are dropped before the next launch."""
-
-    def __init__(self):
-        self.jobs = {}              # key -> (weakref to owner, PackJob, tensors kept alive)
-        self.dirty = True
-        self.table = None
-        self.total = 0
-        self.step = -1
+    with its persistent destination buffers."""
+    JOB, BLOCKS, LAUNCH = _lib.PackJob, 'pcp_pack_conv3x3_group_blocks', 'pcp_pack_conv3x3_group'
 
     def add(self, key, owner, w, transpose, direct=None, direct_opad=0, wino=None, wino_opad=0, u4f=None, u4h=None, f4_opad=0):
-        import weakref
         j = _lib.PackJob(_p(w), w.shape[0], w.shape[1], 1 if transpose else 0, direct_opad, _p(direct), _p(wino), wino_opad, f4_opad,
                          _p(u4f), _p(u4h), 0, 0)
-        if _lib.load().pcp_pack_conv3x3_group_blocks(ctypes.byref(j)) <= 0:
-            raise _lib.PcpError('pcp_pack_conv3x3_group: invalid job')
-        self.jobs[key] = (weakref.ref(owner), j, (w, direct, wino, u4f, u4h))
-        self.dirty = True
-
-    def has(self, key):
-        e = self.jobs.get(key)
-        return e is not None and e[0]() is not None
-
-    def drop(self, key):
-        if self.jobs.pop(key, None) is not None:
-            self.dirty = True
-
-    def run(self, device):
-        L = _lib.load()
-        dead = [k for k, e in self.jobs.items() if e[0]() is None]
-        for k in dead:
-            del self.jobs[k]
-            self.dirty = True
-        if not self.jobs:
-            return
-        if self.dirty or self.table is None or self.table.device != device:
-            arr = (_lib.PackJob * len(self.jobs))()
-            start = 0
-            for i, (_o, j, _t) in enumerate(self.jobs.values()):
-                j.block_start = start
-                start += L.pcp_pack_conv3x3_group_blocks(ctypes.byref(j))
-                arr[i] = j
-            self.total = start
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            self.table = host.to(device)
-            self.dirty = False
-        check(L.pcp_pack_conv3x3_group(_p(self.table), len(self.jobs), self.total, _stream()), 'pcp_pack_conv3x3_group')
+        self._register(key, owner, j, (w, direct, wino, u4f, u4h))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

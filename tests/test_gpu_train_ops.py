@@ -241,6 +241,38 @@ def test_grouped_weight_repack_equals_the_per_layer_repack_over_several_steps(mo
     assert not torch.equal(a[0], a[4])                                   # the weights did move between the steps
 
 
+def test_grouped_weight_repack_follows_a_changing_fused_form(monkeypatch):
+    """PCP_CONV_ALGO changes at every optimizer step (winograd4f, winograd4h, direct, winograd4h), so the fused-F(4x4) choice of both layers
+    changes each time: their group jobs are dropped, the new form is packed per layer and registered again.  The same two-layer stack as
+    above gives bit-identical activations and gradients with the group switched off"""
+    from pcp_amd import train_layers as tl
+
+    def run(grouping):
+        monkeypatch.setattr(tl, 'PACK_GROUPING', grouping)
+        monkeypatch.setattr(tl, 'PACK_GROUP', tl.tops.PackGroup())
+        c1, c2 = _mk_conv('c3s1', 64, 64, False, 91).to(DEV), _mk_conv('c3s2', 64, 128, False, 92).to(DEV)
+        b1, b2 = _mk_bn(64, 93).to(DEV), _mk_bn(128, 94).to(DEV)
+        l1, l2 = tl.ConvBNAct(c1, b1, True, name='g1'), tl.ConvBNAct(c2, b2, True, name='g2')
+        x = _nhwc(_u(95, 1, (2, 64, 32, 48)).to(DEV))
+        outs = []
+        for algo in ('winograd4f', 'winograd4h', 'direct', 'winograd4h'):
+            monkeypatch.setenv('PCP_CONV_ALGO', algo)
+            tl.StepClock.tick()
+            y = l2.forward(l1.forward(tl.Act(x)))
+            g = l1.backward(l2.backward(tl.Act(torch.ones_like(y.t) * 0.01)))
+            outs += [y.t.clone(), g.t.clone(), c1.weight.grad.clone(), c2.weight.grad.clone()]
+            with torch.no_grad():
+                for c in (c1, c2):
+                    c.weight.add_(c.weight.grad, alpha=-0.05)               # in place: the packed forms are stale until the next repack
+        return outs, len(tl.PACK_GROUP.jobs)
+    a, n_a = run(True)
+    b, n_b = run(False)
+    assert n_a == 4 and n_b == 0                                         # two layers x (forward, data gradient) registered again
+    for i, (u, v) in enumerate(zip(a, b)):
+        assert torch.equal(u, v), i
+    assert not torch.equal(a[0], a[4])                                   # the weights did move between the steps
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a15: targets, losses
 # ---------------------------------------------------------------------------------------------------------------------

@@ -395,6 +395,29 @@ def test_conv_dispatch_table_is_the_recorded_one():
         assert got4[key] == want4[key], key
 
 
+def test_train_conv_table_is_the_recorded_one():
+    """tests/golden/train_conv_table.json was recorded at the commit before train_layers.TrainForms and conv_dispatch.choose_train_conv3x3
+    existed (the file names it), by tests/golden/make_train_conv_table.py: ConvBNAct and _HeadBranches driven through their public surface
+    over several optimizer steps with every ops / train_ops launch stubbed out and the group repack's library symbols faked.  The same
+    recorder on this code must give the same launches in the same order with the same arguments, packed forms and group jobs on every row."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('make_train_conv_table', os.path.join(GOLDEN, 'make_train_conv_table.py'))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(rec.TABLE) as f:
+        doc = json.load(f)
+    want, got = rec.decode(doc['table']), rec.record()
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], (key, [(i, w, g) for i, (w, g) in enumerate(zip(want[key], got[key])) if w != g][:3],
+                                       len(want[key]), len(got[key]))
+    # a table that pins nothing would pass the above: the five kernel choices, the bf16 loop, both group launches and the stride-2 data
+    # gradient are all in it
+    assert rec.function_names(want) >= {'conv3x3', 'conv3x3_winograd', 'conv3x3_winograd4f', 'conv3x3_winograd4h', 'conv3x3_bf16x3',
+                                        'mp_conv3x3', 'mp_pointwise', 'pack_conv3x3_group', 'mp_pack_conv3x3_group', 'dilate2x'}
+
+
 def test_auto_resume_validates_a_checkpoint_before_anything_is_loaded(tmp_path):
     """tools/train.py: the newest checkpoint that is readable AND holds every model tensor at its shape is chosen; a torn file and a
     checkpoint of another architecture are skipped without touching the model (ADVICE r2 / VERDICT r3 item 9)."""
