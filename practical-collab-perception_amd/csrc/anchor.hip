@@ -8,6 +8,7 @@
 // pcp_anchor_decode is a pure stream (reads the head map once, writes boxes / logits / score keys); pcp_topk_boxes is one workgroup
 // per frame: 3-pass radix select over the score keys (L2 resident) + bitonic sort of the K survivors in LDS.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -70,34 +71,6 @@ constexpr int TK_THREADS = 1024;
 constexpr int TK_KMAX = 4096;
 constexpr int TK_BINS = 2048;
 
-__device__ __forceinline__ int wave_incl_scan_i(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const int u = __shfl_up(v, s, 64);
-    if (lane >= s) v += u;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int block_excl_scan_i(int v, int *scratch, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = wave_incl_scan_i(v);
-  if (lane == 63) scratch[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int w = threadIdx.x < TK_THREADS / 64 ? scratch[threadIdx.x] : 0;
-    const int wi = wave_incl_scan_i(w);
-    if (threadIdx.x < TK_THREADS / 64) scratch[threadIdx.x] = wi - w;
-    if (threadIdx.x == TK_THREADS / 64 - 1) scratch[TK_THREADS / 64] = wi;
-  }
-  __syncthreads();
-  const int res = scratch[wave] + incl - v;
-  *total = scratch[TK_THREADS / 64];
-  __syncthreads();
-  return res;
-}
-
 __global__ __launch_bounds__(TK_THREADS) void k_topk_boxes(const unsigned *__restrict__ keys, const int *__restrict__ labels,
                                                           const float *__restrict__ boxes, long long n, int kmax, float *__restrict__ out_boxes,
                                                           float *__restrict__ out_scores, int *__restrict__ out_labels, int *__restrict__ out_idx,
@@ -112,7 +85,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_boxes(const unsigned *__res
   int local = 0;
   for (long long i = tid; i < n; i += TK_THREADS) local += kb[i] != 0u;
   int tot;
-  block_excl_scan_i(local, scratch, &tot);
+  block_excl_scan<TK_THREADS>(local, scratch, &tot);
   if (tid == 0) n_valid = tot;
   __syncthreads();
   const int K = min(kmax, n_valid);
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_boxes(const unsigned *__res
       const int top = TK_BINS - 1 - 32 * tid;
       int s = 0;
       for (int q = 0; q < 32; q++) s += hist[top - q];
-      const int incl = wave_incl_scan_i(s);
+      const int incl = wave_incl_scan(s, threadIdx.x & 63);
       const int before = incl - s;
       if (before < need && incl >= need) {
         int run = before;
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_boxes(const unsigned *__res
     const unsigned k = i < n ? kb[i] : 0u;
     const bool is_eq = k == kth;
     int chunk_total;
-    const int rank = block_excl_scan_i(is_eq ? 1 : 0, scratch, &chunk_total);
+    const int rank = block_excl_scan<TK_THREADS>(is_eq ? 1 : 0, scratch, &chunk_total);
     const bool take = k > kth || (is_eq && eq_seen + rank < need);
     eq_seen += chunk_total;
     if (take) {

@@ -14,6 +14,7 @@
 // so "this anchor holds a box's best overlap" is an exact equality against an order-independent atomic max.  Scalar losses are float64
 // block sums + atomics (order independent to ~1e-16); the labels are integers and bit exact.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -205,23 +206,13 @@ __global__ __launch_bounds__(AT_THREADS) void k_assign_labels(pcp_anchor_assign_
 
 // ---- losses ---------------------------------------------------------------------------------------------------------------
 // workspace (double): [0] cls sum  [1] loc sum  [2] dir sum  [3] unused  [4 + b] positives of frame b
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  double t = 0;
-  if (threadIdx.x == 0) for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) t += sh[w];
-  return t;   // valid on thread 0
-}
 
 __global__ __launch_bounds__(AT_THREADS) void k_count_positives(int n, const int *__restrict__ labels, double *acc) {
   __shared__ double sh[AT_THREADS / 64];
   const int b = blockIdx.y;
   double c = 0;
   for (int i = blockIdx.x * AT_THREADS + threadIdx.x; i < n; i += gridDim.x * AT_THREADS) c += labels[(long long)b * n + i] > 0 ? 1.0 : 0.0;
-  const double s = block_sum(c, sh);
+  const double s = block_sum_lane0(c, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 4 + b, s);
 }
 
@@ -330,11 +321,11 @@ __global__ __launch_bounds__(AT_THREADS) void k_anchor_loss(pcp_anchor_loss_t d,
       for (int ch = used; ch < d.ld_d; ++ch) gp[ch] = 0.f;
     }
   }
-  double s = block_sum(l_cls, sh);
+  double s = block_sum_lane0(l_cls, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 0, s);
-  s = block_sum(l_loc, sh);
+  s = block_sum_lane0(l_loc, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 1, s);
-  s = block_sum(l_dir, sh);
+  s = block_sum_lane0(l_dir, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 2, s);
 }
 

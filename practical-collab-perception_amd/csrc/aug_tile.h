@@ -86,7 +86,7 @@ __device__ __forceinline__ void aug_tile_compact(long long before, const bool (&
   constexpr int ITEMS = PCP_AUG_TILE_ROWS / THREADS, WAVES = THREADS / PCP_WAVE;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);     // open-coded: the wave_ops.h call changes the schedule of k_aug_place and k_obj_points
   if (lane == 0) s_before[wave] = before;
   __syncthreads();
   before = 0;

@@ -9,6 +9,7 @@
 // (torch.topk leaves tie order unspecified).  Per-class top-K followed by a cross-class top-K
 // (centernet_utils.py:137-143) selects the same set as one top-K over all (class, cell) pairs.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -27,35 +28,6 @@ struct DecParams {
   float *boxes, *scores;
   int *labels, *cell, *count;
 };
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    int u = __shfl_up(v, s, 64);
-    if (lane >= s) v += u;
-  }
-  return v;
-}
-
-// exclusive scan over the 1024 threads of the block; *total receives the block sum. scratch: >= 17 ints of LDS.
-__device__ __forceinline__ int block_excl_scan(int v, int *scratch, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = wave_incl_scan(v);
-  if (lane == 63) scratch[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    int w = threadIdx.x < DEC_THREADS / 64 ? scratch[threadIdx.x] : 0;
-    int wi = wave_incl_scan(w);
-    if (threadIdx.x < DEC_THREADS / 64) scratch[threadIdx.x] = wi - w;
-    if (threadIdx.x == DEC_THREADS / 64 - 1) scratch[DEC_THREADS / 64] = wi;
-  }
-  __syncthreads();
-  int res = scratch[wave] + incl - v;
-  *total = scratch[DEC_THREADS / 64];
-  __syncthreads();
-  return res;
-}
 
 // Optional parts of the velocity decode (pcp_centerhead_decode_ext); ch_vel / ch_iou < 0 = absent (pcp_centerhead_decode)
 struct DecExt {
@@ -120,7 +92,7 @@ __device__ __forceinline__ void decode_frame(const pcp_decode_t &d, const float 
       int top = HIST_BINS - 1 - 32 * tid;
       int s = 0;
       for (int q = 0; q < 32; q++) s += hist[top - q];
-      int incl = wave_incl_scan(s);
+      int incl = wave_incl_scan(s, tid & 63);
       int before = incl - s;                    // elements in strictly higher bins owned by lower lanes
       bool mine = (before < need) && (incl >= need);
       if (mine) {
@@ -149,7 +121,7 @@ __device__ __forceinline__ void decode_frame(const pcp_decode_t &d, const float 
 #pragma unroll
   for (int i = 0; i < IPT; i++) eq_local += (key[i] == kth && kth != 0u) ? 1 : 0;
   int eq_total;
-  block_excl_scan(eq_local, scratch, &eq_total);
+  block_excl_scan<DEC_THREADS>(eq_local, scratch, &eq_total);
   if (tid == 0) cand_count = 0;
   for (int i = tid; i < DEC_KMAX; i += DEC_THREADS) cand[i] = 0ULL;
   __syncthreads();
@@ -162,7 +134,7 @@ __device__ __forceinline__ void decode_frame(const pcp_decode_t &d, const float 
       take = take || is_eq;
     } else {                        // rare: more equals than needed -> rank them in index order (item-major, thread-minor)
       int item_total;
-      int rank_in_item = block_excl_scan(is_eq ? 1 : 0, scratch, &item_total);
+      int rank_in_item = block_excl_scan<DEC_THREADS>(is_eq ? 1 : 0, scratch, &item_total);
       if (is_eq && eq_before_item + rank_in_item < need) take = true;
       eq_before_item += item_total;
     }
@@ -216,7 +188,7 @@ __device__ __forceinline__ void decode_frame(const pcp_decode_t &d, const float 
     if (d.use_score_thresh) ok = ok && (score > d.score_thresh);
   }
   int n_ok;
-  int pos = block_excl_scan(ok ? 1 : 0, scratch, &n_ok);
+  int pos = block_excl_scan<DEC_THREADS>(ok ? 1 : 0, scratch, &n_ok);
   if (ok) {
     long long o = (long long)b * d.k + pos;
 #pragma unroll

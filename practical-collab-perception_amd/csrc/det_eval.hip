@@ -14,6 +14,7 @@
 //                  not above x, the sample itself on equality, one slope product otherwise).
 // Neither kernel is near a roofline: the point is that the boxes never leave the device and an epoch ends with one read.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -58,16 +59,6 @@ __device__ __forceinline__ int ev_compact(bool f, int &base, int *s_wave) {
   base += tot;
   __syncthreads();
   return off + within;
-}
-
-__device__ __forceinline__ u64 ev_wave_min(u64 v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), d, 64), hi = __shfl_xor((unsigned)(v >> 32), d, 64);
-    const u64 o = ((u64)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
 }
 
 __device__ __forceinline__ float ev_orient_err(float yaw_gt, float yaw_pred, float period) {
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_match(const float *__restri
         best = kk < best ? kk : best;
       }
     }
-    best = ev_wave_min(best);
+    best = wave_min_u64(best);
     const float d = __uint_as_float((unsigned)(best >> 32));
     const int j = (int)(best & 0xffffffffull);
     const bool tp = best != ~0ull && d < th;                          // a NaN distance never matches
@@ -219,16 +210,6 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_match(const float *__restri
     rec[2 * k + 1] = make_uint4(__float_as_uint(s_err[0][p]), __float_as_uint(s_err[1][p]), __float_as_uint(s_err[2][p]),
                                 __float_as_uint(s_err[3][p]));
   }
-}
-
-template <typename T>
-__device__ __forceinline__ T ev_wave_scan(T v, int lane) {              // inclusive, in lane order
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
 }
 
 // numpy.interp on samples xp[j] = tpc[j] / npos (non-decreasing), right = 0
@@ -308,7 +289,7 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_curves(const unsigned *__re
     const bool valid = i < N;
     const unsigned *r = rec + (size_t)min(i, N - 1) * EV_RW;
     const int f = valid && ((r[2] >> tt) & 1u);
-    const int tp_w = ev_wave_scan<int>(f, lane);
+    const int tp_w = wave_incl_scan<int>(f, lane);
     int cnt_w[4] = {0, 0, 0, 0};
     double sum_w[4] = {0.0, 0.0, 0.0, 0.0};
     if (errs) {
@@ -316,8 +297,8 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_curves(const unsigned *__re
       for (int m = 0; m < 4; m++) {
         const float e = __uint_as_float(r[4 + m]);
         const bool ok = f && e == e;
-        cnt_w[m] = ev_wave_scan<int>(ok ? 1 : 0, lane);
-        sum_w[m] = ev_wave_scan<double>(ok ? (double)e : 0.0, lane);
+        cnt_w[m] = wave_incl_scan<int>(ok ? 1 : 0, lane);
+        sum_w[m] = wave_incl_scan<double>(ok ? (double)e : 0.0, lane);
       }
     }
     if (lane == 63) {

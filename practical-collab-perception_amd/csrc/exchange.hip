@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_modar_ingest(const float *__restrict__ 
   float v[4] = {sx, sy, sz, cnt};
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o);
+    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o);     // open-coded: the wave_ops.h call changes this kernel's schedule
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v[q];
   }
   __syncthreads();
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_modar_ingest_batched(const float *__res
   float v[4] = {sx, sy, sz, cnt};
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    for (int of = 32; of > 0; of >>= 1) v[q] += __shfl_down(v[q], of);
+    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o);     // open-coded: the wave_ops.h call changes this kernel's schedule
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v[q];
   }
   __syncthreads();

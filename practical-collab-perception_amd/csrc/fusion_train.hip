@@ -7,6 +7,7 @@
 // One wavefront per pixel: the C = 128 channel dot products <dfused, map_a> are wave reductions, the per-agent scalars live in
 // registers, conv1_4's 17 parameter gradients are accumulated per lane and reduced once per block in float64.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -28,11 +29,6 @@ __global__ __launch_bounds__(256) void k_weight_logits(Ptrs h2, int n_agents, in
 #pragma unroll
   for (int j = 0; j < H2; ++j) acc = fmaf(row[j], w4[j], acc);
   logits[pix * ld_w + a] = fmaxf(acc, 0.f);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 struct VPtrs { const void *p[FT_MAX_AGENTS]; };

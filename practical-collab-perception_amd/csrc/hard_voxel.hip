@@ -16,6 +16,7 @@
 //                  kept if < max_voxels; voxel number = kept voxels of the frames in front + rank.  Writes coords, num_points, counters
 //   k_hv_gather    (after the host read M) one thread per (voxel, slot): the row of slot j < min(count, T), zeros behind
 #include "pcp_common.h"
+#include "wave_ops.h"
 #include "vox_cells_z.h"
 
 namespace {
@@ -39,12 +40,11 @@ struct HvLayout {
 inline HvLayout hv_layout(int64_t cells, int64_t n) {
   HvLayout L;
   L.v = pcp_vox_layout(cells, n);
-  size_t off = L.v.total;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
-  L.tile_sums = take((size_t)((n + HV_TILE - 1) / HV_TILE + 1) * 4);
-  L.vox_pillar = take((size_t)n * 4);
-  L.dense_coords = take((size_t)n * 16);
-  L.total = off;
+  PcpCarver ws(L.v.total);
+  L.tile_sums = ws.take((size_t)((n + HV_TILE - 1) / HV_TILE + 1) * 4);
+  L.vox_pillar = ws.take((size_t)n * 4);
+  L.dense_coords = ws.take((size_t)n * 16);
+  L.total = ws.total();
   return L;
 }
 
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_number(long long n, pcp_grid_
     const int kept = min(hit, max_voxels);
     int ih = hit, ik = kept;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
+    for (int d = 1; d < 64; d <<= 1) {                                   // a pair in one loop: two wave_incl_scan calls change the schedule
       const int uh = __shfl_up(ih, d, 64), uk = __shfl_up(ik, d, 64);
       if (lane >= d) {
         ih += uh;
@@ -127,8 +127,7 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_number(long long n, pcp_grid_
   // flags of the tiles in front of this one
   int pre = 0;
   for (int i = threadIdx.x; i < tile && i < n_tiles; i += HV_THREADS) pre += tile_sums[i];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) pre += __shfl_xor(pre, d, 64);
+  pre = wave_sum(pre);
   if (lane == 0) red[wave] = pre;
   // exclusive scan of this tile's flags; a thread's items are CONSECUTIVE rows
   const long long base = (long long)tile * HV_TILE + (long long)threadIdx.x * HV_ITEMS;
@@ -140,12 +139,7 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_number(long long n, pcp_grid_
     excl[i] = local;
     local += first ? 1 : 0;
   }
-  int incl = local;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
+  const int incl = wave_incl_scan(local, lane);
   if (lane == 63) lds_wave[wave] = incl;
   __syncthreads();
   int before = incl - local;
@@ -319,7 +313,7 @@ __global__ __launch_bounds__(256) void k_pillar_vfe(const float *__restrict__ vo
       sz += vrow[r * C + 2];
     }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
+    for (int d = 32; d >= 1; d >>= 1) {                                  // a triple in one loop: three wave_sum calls change the schedule
       sx += __shfl_xor(sx, d, 64);
       sy += __shfl_xor(sy, d, 64);
       sz += __shfl_xor(sz, d, 64);

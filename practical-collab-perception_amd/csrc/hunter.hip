@@ -62,15 +62,14 @@ struct ScLayout {
 constexpr int SC_BIG = 256;                 // cells of more rows than this are listed by the scan and summed by k_sc_mean_big
 inline ScLayout sc_layout(long long cells, long long n) {
   ScLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
-  L.cell_count = take((size_t)cells * 4);
-  L.cell_fill = take((size_t)cells * 4);
-  L.cell_start = take((size_t)(cells + 1) * 4);
-  L.point_cell = take((size_t)(n > 0 ? n : 1) * 4);
-  L.bucket = take((size_t)(n > 0 ? n : 1) * 4);
-  L.big_list = take((size_t)((n > 0 ? n : 1) / SC_BIG + 2) * 4);          // [0] = count, then the cells
-  L.total = off;
+  PcpCarver ws;
+  L.cell_count = ws.take((size_t)cells * 4);
+  L.cell_fill = ws.take((size_t)cells * 4);
+  L.cell_start = ws.take((size_t)(cells + 1) * 4);
+  L.point_cell = ws.take((size_t)(n > 0 ? n : 1) * 4);
+  L.bucket = ws.take((size_t)(n > 0 ? n : 1) * 4);
+  L.big_list = ws.take((size_t)((n > 0 ? n : 1) / SC_BIG + 2) * 4);          // [0] = count, then the cells
+  L.total = ws.total();
   return L;
 }
 
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(1024) void k_sc_scan(const int *__restrict__ cell_c
     int incl = local;
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
-      int u = __shfl_up(incl, s, 64);
+      int u = __shfl_up(incl, s, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
       if (lane >= s) incl += u;
     }
     if (lane == 63) wave_sum[wave] = incl;

@@ -16,6 +16,7 @@
 // the sorted order of torch.unique is the key order.  Scalar losses are float64 sums.  The only library call is hipCUB's radix sort for the
 // three descending error orders of the Lovasz extension.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -24,17 +25,6 @@
 namespace {
 
 constexpr int HT = 256;
-
-__device__ __forceinline__ double block_sum_d(double v, double *sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  double t = 0;
-  if (threadIdx.x == 0) for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) t += sh[w];
-  return t;   // valid on thread 0
-}
 
 __device__ __forceinline__ float sl1(float d) { const float a = fabsf(d); return a < 1.f ? 0.5f * d * d : a - 0.5f; }
 __device__ __forceinline__ float sl1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
@@ -95,7 +85,7 @@ __device__ int wg_exclusive_scan(int *data, long long len, int *sh) {
     const long long i = base + threadIdx.x;
     const int v = i < len ? data[i] : 0;
     int inc = v;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }     // open-coded (no unroll pragma, no width): wave_incl_scan changes k_hm_scan
     if (lane == 63) sh[wv] = inc;
     __syncthreads();
     int woff = 0;
@@ -333,7 +323,7 @@ __global__ __launch_bounds__(HT) void k_hl_points(pcp_hunter_loss_t d, int *__re
     tgt_emb[j * 2 + 0] = ex; tgt_emb[j * 2 + 1] = ey;
     tgt_off[j * 3 + 0] = off[0]; tgt_off[j * 3 + 1] = off[1]; tgt_off[j * 3 + 2] = off[2];
   }
-  const double s = block_sum_d(emb, sh);
+  const double s = block_sum_lane0(emb, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 5, s);
 }
 
@@ -397,11 +387,11 @@ __global__ __launch_bounds__(1024) void k_hard_mining(const float *__restrict__ 
   if (n <= 0) { if (tid == 0) *loss_out = 0.0; return; }
   double c = 0, sp = 0;
   for (int i = tid; i < n; i += 1024) if (pos_mask[i]) { c += 1.0; sp += (double)val[i]; }
-  double t = block_sum_d(c, shd);
+  double t = block_sum_lane0(c, shd);
   if (tid == 0) s_tmp = t;
   __syncthreads();
   const int n_pos = (int)s_tmp;
-  t = block_sum_d(sp, shd);
+  t = block_sum_lane0(sp, shd);
   __syncthreads();
   if (tid == 0) s_tmp = t;
   __syncthreads();
@@ -445,9 +435,9 @@ __global__ __launch_bounds__(1024) void k_hard_mining(const float *__restrict__ 
     const float v = fmaxf(val[i], 0.f);
     if (v > thr) { cgt += 1.0; sgt += (double)v; } else if (v == thr) ceq += 1.0;
   }
-  t = block_sum_d(cgt, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double n_gt = s_tmp; __syncthreads();
-  t = block_sum_d(sgt, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double sum_gt = s_tmp; __syncthreads();
-  t = block_sum_d(ceq, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double n_eq = s_tmp; __syncthreads();
+  t = block_sum_lane0(cgt, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double n_gt = s_tmp; __syncthreads();
+  t = block_sum_lane0(sgt, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double sum_gt = s_tmp; __syncthreads();
+  t = block_sum_lane0(ceq, shd); __syncthreads(); if (tid == 0) s_tmp = t; __syncthreads(); const double n_eq = s_tmp; __syncthreads();
   const double take = (double)k - n_gt;                      // slots left for the tied elements, 1 <= take <= n_eq
   const float w_gt = (float)(scale / k), w_eq = (float)(scale * take / (n_eq * k));
   for (int i = tid; i < n; i += 1024) {
@@ -467,9 +457,9 @@ __global__ __launch_bounds__(HT) void k_ce_counts(const int *__restrict__ labels
     const int y = labels[i];
     c0 += y == 0; c1 += y == 1; c2 += y == 2;
   }
-  double s = block_sum_d(c0, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 12, s);
-  s = block_sum_d(c1, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 13, s);
-  s = block_sum_d(c2, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 14, s);
+  double s = block_sum_lane0(c0, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 12, s);
+  s = block_sum_lane0(c1, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 13, s);
+  s = block_sum_lane0(c2, sh); if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 14, s);
 }
 
 __device__ __forceinline__ void ce_weights(const double *acc, float *w) {
@@ -505,8 +495,8 @@ __global__ __launch_bounds__(HT) void k_ce_forward(const float *__restrict__ hea
     for (int c = 0; c < 3; ++c) err[(long long)c * n + i] = fabsf((y == c ? 1.f : 0.f) - p[c]);
     idx[i] = (int)i;
   }
-  double s = block_sum_d(nll, sh); if (threadIdx.x == 0) atomicAdd(acc + 0, s);
-  s = block_sum_d(ws, sh); if (threadIdx.x == 0) atomicAdd(acc + 1, s);
+  double s = block_sum_lane0(nll, sh); if (threadIdx.x == 0) atomicAdd(acc + 0, s);
+  s = block_sum_lane0(ws, sh); if (threadIdx.x == 0) atomicAdd(acc + 1, s);
 }
 
 // Lovasz gradient of one class by ONE workgroup: cumulative foreground count along the descending-error order, Jaccard differences,
@@ -527,7 +517,7 @@ __global__ __launch_bounds__(1024) void k_lovasz_class(const float *__restrict__
     const long long k = base + threadIdx.x;
     const int fg = (k < n && labels[perm[k]] == cls) ? 1 : 0;
     int inc = fg;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }     // open-coded, as in wg_exclusive_scan
     if (lane == 63) shw[wv] = inc;
     __syncthreads();
     int woff = 0;
@@ -551,7 +541,7 @@ __global__ __launch_bounds__(1024) void k_lovasz_class(const float *__restrict__
     if (threadIdx.x == 1023) running = cum;
     __syncthreads();
   }
-  const double s = block_sum_d(loss, shd);
+  const double s = block_sum_lane0(loss, shd);
   if (threadIdx.x == 0) acc[2 + cls] = s;
 }
 
@@ -664,7 +654,7 @@ __global__ __launch_bounds__(HT) void k_hl_distill(pcp_hunter_loss_t d, double *
     d.dlocal_feat_fg[(long long)j * d.c + ch] = g;
     if (g != 0.f) atomicAdd(dlocals_acc + (long long)l * d.c + ch, -(double)g);
   }
-  const double s = block_sum_d(v, sh);
+  const double s = block_sum_lane0(v, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc + 6, s);
 }
 
@@ -714,7 +704,7 @@ __global__ __launch_bounds__(HT) void k_fuse2_backward(const float *__restrict__
     dcat[pix * ld_dcat + ch] = g * w0;
     dcat[pix * ld_dcat + c + ch] = g * w1;
   }
-  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }     // a pair in one loop: two wave_sum calls change the schedule
   const float dot = w0 * s0 + w1 * s1;
   for (int k = lane; k < ld_dl; k += 64) dlogits[pix * ld_dl + k] = k == 0 ? w0 * (s0 - dot) : (k == 1 ? w1 * (s1 - dot) : 0.f);
 }
@@ -761,7 +751,7 @@ __global__ __launch_bounds__(HT) void k_bilinear_backward(const float *__restric
     }
   }
   if (bev) {
-    for (int o = 32; o > 0; o >>= 1) { gx += __shfl_xor(gx, o); gy += __shfl_xor(gy, o); }
+    for (int o = 32; o > 0; o >>= 1) { gx += __shfl_xor(gx, o); gy += __shfl_xor(gy, o); }   // a pair in one loop, as above
     if (lane == 0) {
       dxyz[i * ld_dxyz + 0] += gx / pix_x;
       dxyz[i * ld_dxyz + 1] += gy / pix_y;
@@ -816,6 +806,7 @@ inline LossWs loss_carve(void *ws, long long n, int n_fg, int n_local, int c) {
   LossWs L;
   size_t off = 0;
   char *base = static_cast<char *>(ws);
+  // not PcpCarver: empty blocks take 16 bytes and every field is a pointer (null for a size query); two more arguments at each of the 21 calls
   auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + (bytes ? bytes : 16), 256); return base ? base + o : (char *)nullptr; };
   const size_t nf = n_fg > 0 ? n_fg : 1, nl = n_local > 0 ? n_local : 1, nn = n > 0 ? n : 1;
   L.acc = (double *)take(sizeof(double) * LACC);

@@ -12,6 +12,7 @@
 // Latency-bound integer/float work (<= 500 boxes, 16 384 cells): one workgroup per frame for the targets, flat streaming
 // kernels for the losses; every reduction is float64 (atomics per block), so the scalar losses are order independent.
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -138,17 +139,6 @@ __device__ __forceinline__ float clamped_sigmoid(float x, int *inside) {
   return fminf(fmaxf(s, 1e-4f), 1.f - 1e-4f);
 }
 
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  double t = 0;
-  if (threadIdx.x == 0) for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) t += sh[w];
-  return t;   // valid on thread 0
-}
-
 __global__ __launch_bounds__(256) void k_focal_reduce(pcp_headloss_t d, const float *__restrict__ head, const float *__restrict__ heat,
                                                      double *acc) {
   __shared__ double sh[4];
@@ -168,11 +158,11 @@ __global__ __launch_bounds__(256) void k_focal_reduce(pcp_headloss_t d, const fl
       neg += (double)(logf(1.f - p) * p * p * (w * w));
     }
   }
-  double s = block_sum(pos, sh);
+  double s = block_sum_lane0(pos, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 0, s);
-  s = block_sum(neg, sh);
+  s = block_sum_lane0(neg, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 1, s);
-  s = block_sum(npos, sh);
+  s = block_sum_lane0(npos, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 2, s);
 }
 
@@ -193,11 +183,11 @@ __global__ __launch_bounds__(256) void k_reg_reduce(pcp_headloss_t d, const floa
       s[j] += (double)fabsf(px[d.reg_ch[j]] - tv);
     }
   }
-  double r = block_sum(num, sh);
+  double r = block_sum_lane0(num, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 3, r);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    r = block_sum(s[j], sh);
+    r = block_sum_lane0(s[j], sh);
     if (threadIdx.x == 0) atomicAdd(acc + 4 + j, r);
   }
 }
@@ -286,8 +276,7 @@ __global__ __launch_bounds__(256) void k_distill(const float *__restrict__ fused
       mf = fmaxf(mf, f[i]);
       me = fmaxf(me, e[i]);
     }
-    for (int o = 32; o > 0; o >>= 1) { mf = fmaxf(mf, __shfl_xor(mf, o)); me = fmaxf(me, __shfl_xor(me, o)); }
-    float sf = 0.f, se = 0.f;
+    for (int o = 32; o > 0; o >>= 1) { mf = fmaxf(mf, __shfl_xor(mf, o)); me = fmaxf(me, __shfl_xor(me, o)); }    float sf = 0.f, se = 0.f;
 #pragma unroll
     for (int i = 0; i < DIST_MAXV; ++i) {
       f[i] = expf(f[i] - mf);
@@ -295,7 +284,7 @@ __global__ __launch_bounds__(256) void k_distill(const float *__restrict__ fused
       sf += f[i];
       se += e[i];
     }
-    for (int o = 32; o > 0; o >>= 1) { sf += __shfl_xor(sf, o); se += __shfl_xor(se, o); }
+    for (int o = 32; o > 0; o >>= 1) { sf += __shfl_xor(sf, o); se += __shfl_xor(se, o); }     // a pair in one loop: two wave_sum calls change the schedule
     float dot = 0.f;
     float gs[DIST_MAXV];
 #pragma unroll
@@ -308,7 +297,7 @@ __global__ __launch_bounds__(256) void k_distill(const float *__restrict__ fused
       gs[i] = ad < 1.f ? diff : (diff > 0.f ? 1.f : -1.f);
       dot += ch < c ? gs[i] * f[i] : 0.f;
     }
-    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);     // open-coded: the wave_ops.h call changes this kernel's schedule
     if (dfused) {
       const float k = weight * grad_scale * (float)inv_n;
 #pragma unroll
@@ -322,7 +311,7 @@ __global__ __launch_bounds__(256) void k_distill(const float *__restrict__ fused
       }
     }
   }
-  const double s = block_sum(loss, sh);
+  const double s = block_sum_lane0(loss, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 12, s);
 }
 
@@ -348,10 +337,8 @@ __global__ __launch_bounds__(256) void k_masked_sl1(const float *__restrict__ fu
       n2 = fmaf(t, t, n2);
       l += a < 1.0f ? 0.5f * d * d : a - 0.5f;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      n2 += __shfl_xor(n2, o);
-      l += __shfl_xor(l, o);
-    }
+    n2 = wave_sum(n2);
+    l = wave_sum(l);
     if (sqrtf(n2) > thresh) {
       sum += (double)l;
       cnt += 1.0;
@@ -368,7 +355,7 @@ __global__ __launch_bounds__(256) void k_masked_sl1(const float *__restrict__ fu
 __global__ void k_masked_sl1_finalize(const double *__restrict__ acc, int nb, float *__restrict__ loss) {
   double s = 0.0, n = 0.0;
   for (int i = threadIdx.x; i < nb; i += 64) { s += acc[2 * i]; n += acc[2 * i + 1]; }
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {                                     // a pair in one loop, as in k_distill
     s += __shfl_xor(s, o);
     n += __shfl_xor(n, o);
   }
@@ -561,11 +548,11 @@ __global__ __launch_bounds__(256) void k_lossx_reduce(LossExtParams p, double *_
         neg += (double)(logf(1.f - q) * q * q * (wt * wt));
       }
     }
-    double s = block_sum(pos, sh);
+    double s = block_sum_lane0(pos, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 0] = s;
-    s = block_sum(neg, sh);
+    s = block_sum_lane0(neg, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 1] = s;
-    s = block_sum(npos, sh);
+    s = block_sum_lane0(npos, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 2] = s;
     return;
   }
@@ -584,11 +571,11 @@ __global__ __launch_bounds__(256) void k_lossx_reduce(LossExtParams p, double *_
     for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j)
       if (j < hd.n_codes) s[j] += (double)fabsf(px[hd.reg_ch[j]] - tv[j]);
   }
-  double r = block_sum(num, sh);
+  double r = block_sum_lane0(num, sh);
   if (threadIdx.x == 0) wr[0] = r;
 #pragma unroll
   for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) {
-    r = block_sum(s[j], sh);
+    r = block_sum_lane0(s[j], sh);
     if (threadIdx.x == 0) wr[1 + j] = r;
   }
 }

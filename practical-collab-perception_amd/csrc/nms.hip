@@ -185,14 +185,13 @@ struct NmsLayout {
 };
 inline NmsLayout nms_layout(int n_max, int batch) {
   NmsLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
+  PcpCarver ws;
   int cb = (n_max + 63) / 64;
-  L.order = take((size_t)batch * n_max * 4);
-  L.sorted_boxes = take((size_t)batch * n_max * 8 * 4);
-  L.mask = take((size_t)batch * n_max * cb * 8);
-  L.n_eff = take((size_t)batch * 4 + 64);
-  L.total = off;
+  L.order = ws.take((size_t)batch * n_max * 4);
+  L.sorted_boxes = ws.take((size_t)batch * n_max * 8 * 4);
+  L.mask = ws.take((size_t)batch * n_max * cb * 8);
+  L.n_eff = ws.take((size_t)batch * 4 + 64);
+  L.total = ws.total();
   return L;
 }
 

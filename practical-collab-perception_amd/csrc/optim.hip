@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void k_sqnorm(const float *__restrict__ x, lon
     s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = x[n4 * 4 + threadIdx.x]; s += (double)v * v; }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);     // open-coded: the wave_ops.h call changes this kernel's schedule
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);

@@ -15,6 +15,14 @@
 
 static inline size_t pcp_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Workspace carving: take(bytes) gives the offset of the next field and moves on to the next 256-byte boundary; total() is the size so far.
+struct PcpCarver {
+  size_t off = 0;
+  explicit PcpCarver(size_t start = 0) : off(start) {}
+  size_t take(size_t bytes) { const size_t o = off; off = pcp_align_up(off + bytes, 256); return o; }
+  size_t total() const { return off; }
+};
+
 // abi.hip: the override of option `option` (PCP_OPT_*, include/pcp_hip.h) or `builtin` while none is set; the CU count of the current device
 __attribute__((visibility("hidden"))) long long pcp_option(int option, long long builtin);
 __attribute__((visibility("hidden"))) int pcp_current_device_cus();
@@ -74,21 +82,20 @@ constexpr int PCP_LONG_PILLAR = 16;
 
 static inline VoxLayout pcp_vox_layout(int64_t cells, int64_t n) {
   VoxLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
-  L.cell_count = take((size_t)cells * 4);
-  L.cell_rank = take((size_t)cells * 4);
-  L.cell_rs = take((size_t)cells * 8);
-  L.point_cell = take((size_t)n * 4);
-  L.point_rank = take((size_t)n * 4);
-  L.bucket_order = take((size_t)n * 4);
-  L.pillar_cell = take((size_t)n * 4);
-  L.pillar_start = take((size_t)(n + 1) * 4);
+  PcpCarver ws;
+  L.cell_count = ws.take((size_t)cells * 4);
+  L.cell_rank = ws.take((size_t)cells * 4);
+  L.cell_rs = ws.take((size_t)cells * 8);
+  L.point_cell = ws.take((size_t)n * 4);
+  L.point_rank = ws.take((size_t)n * 4);
+  L.bucket_order = ws.take((size_t)n * 4);
+  L.pillar_cell = ws.take((size_t)n * 4);
+  L.pillar_start = ws.take((size_t)(n + 1) * 4);
   int64_t nblk = (cells + 1023) / 1024 + (n + 1023) / 1024 + 2;
-  L.block_sums = take((size_t)(3 * nblk + 8) * 4);
-  L.counters = take(64);
-  L.long_list = take((size_t)(n / PCP_LONG_PILLAR + 2) * 4);
-  L.total = off;
+  L.block_sums = ws.take((size_t)(3 * nblk + 8) * 4);
+  L.counters = ws.take(64);
+  L.long_list = ws.take((size_t)(n / PCP_LONG_PILLAR + 2) * 4);
+  L.total = ws.total();
   return L;
 }
 
@@ -114,11 +121,10 @@ struct RowsLayout {
 static inline RowsLayout pcp_rows_layout(int64_t cells, int64_t n, int num_raw) {
   RowsLayout R;
   R.v = pcp_vox_layout(cells, n);
-  size_t off = R.v.total;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
-  R.srows = take((size_t)n * pcp_rows_stride(num_raw) * 4);
-  R.tile_desc = take((size_t)(n / PCP_PFN_TILE + 2) * 8);
-  R.crowd_list = take((size_t)(n / PCP_PFN_CROWD_MIN + 2) * 16);
-  R.total = off;
+  PcpCarver ws(R.v.total);
+  R.srows = ws.take((size_t)n * pcp_rows_stride(num_raw) * 4);
+  R.tile_desc = ws.take((size_t)(n / PCP_PFN_TILE + 2) * 8);
+  R.crowd_list = ws.take((size_t)(n / PCP_PFN_CROWD_MIN + 2) * 16);
+  R.total = ws.total();
   return R;
 }

@@ -23,6 +23,7 @@
 // L2 and skips, wave-uniformly, every offset none of its 16 rows has.  Waves share nothing, so there is no LDS stage and no barrier; a row's
 // bits depend on its own neighbour list only.  No scatter, no float atomics.
 #include "pcp_common.h"
+#include "wave_ops.h"
 #include "vox_cells_z.h"
 
 namespace {
@@ -46,13 +47,12 @@ struct MvLayout {
 inline MvLayout mv_layout(int64_t cells, int64_t n) {
   MvLayout L;
   L.v = pcp_vox_layout(cells, n);
-  size_t off = L.v.total;
-  auto take = [&](size_t bytes) { size_t o = off; off = pcp_align_up(off + bytes, 256); return o; };
-  L.point_cz = take((size_t)n * 4);
-  L.tile_sums = take((size_t)((n + MV_TILE - 1) / MV_TILE + 1) * 4);
-  L.vox_start = take((size_t)(n + 1) * 4);
-  L.dense_coords = take((size_t)n * 16);
-  L.total = off;
+  PcpCarver ws(L.v.total);
+  L.point_cz = ws.take((size_t)n * 4);
+  L.tile_sums = ws.take((size_t)((n + MV_TILE - 1) / MV_TILE + 1) * 4);
+  L.vox_start = ws.take((size_t)(n + 1) * 4);
+  L.dense_coords = ws.take((size_t)n * 16);
+  L.total = ws.total();
   return L;
 }
 
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_mv_flags(const int *__restrict__
 #pragma unroll
   for (int i = 0; i < MV_ITEMS; i++) total += mv_opens(base + i, kept, order, point_cell, point_cz) ? 1 : 0;
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
   if (lane == 0) wave_tot[wave] = total;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -159,8 +159,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_mv_number(pcp_grid_t g, const in
   const int kept = counters_ws[1];
   int pre = 0;
   for (int i = threadIdx.x; i < tile; i += MV_THREADS) pre += tile_sums[i];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) pre += __shfl_xor(pre, d, 64);
+  pre = wave_sum(pre);
   if (lane == 0) red[wave] = pre;
   const long long base = (long long)tile * MV_TILE + (long long)threadIdx.x * MV_ITEMS;
   bool open[MV_ITEMS];
@@ -171,12 +170,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_mv_number(pcp_grid_t g, const in
     excl[i] = local;
     local += open[i] ? 1 : 0;
   }
-  int incl = local;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
+  const int incl = wave_incl_scan(local, lane);
   if (lane == 63) lds_wave[wave] = incl;
   __syncthreads();
   int before = incl - local;
@@ -320,18 +314,21 @@ inline long long sp_words(const SpShape &s) { return ((long long)s.B * s.D * s.H
 inline size_t sp_table_bytes(const SpShape &s) {
   const long long nw = sp_words(s);
   const long long nt = (nw + MV_TILE - 1) / MV_TILE;
-  return pcp_align_up((size_t)nw * 8, 256) + pcp_align_up((size_t)(nw + 1) * 4, 256) + pcp_align_up((size_t)(nt + 1) * 4, 256);
+  PcpCarver ws;                                                     // the fields of sp_table below
+  ws.take((size_t)nw * 8);
+  ws.take((size_t)(nw + 1) * 4);
+  ws.take((size_t)(nt + 1) * 4);
+  return ws.total();
 }
 inline SpTable sp_table(void *mem, const SpShape &s) {
   SpTable t;
   t.words = sp_words(s);
   t.n_tiles = (int)((t.words + MV_TILE - 1) / MV_TILE);
   char *p = (char *)mem;
-  t.bits = (u64 *)p;
-  p += pcp_align_up((size_t)t.words * 8, 256);
-  t.prefix = (int *)p;
-  p += pcp_align_up((size_t)(t.words + 1) * 4, 256);
-  t.tile_sums = (int *)p;
+  PcpCarver ws;
+  t.bits = (u64 *)(p + ws.take((size_t)t.words * 8));
+  t.prefix = (int *)(p + ws.take((size_t)(t.words + 1) * 4));
+  t.tile_sums = (int *)(p + ws.take((size_t)(t.n_tiles + 1) * 4));
   return t;
 }
 
@@ -396,7 +393,7 @@ __global__ __launch_bounds__(256) void k_sp_mark_strided(const int *__restrict__
 __device__ __forceinline__ int sp_block_sum(int v, int *lds4) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);     // open-coded: the wave_ops.h call changes k_sp_tile_sums' schedule
   __syncthreads();
   if (lane == 0) lds4[wave] = v;
   __syncthreads();
@@ -427,7 +424,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_sp_scan_tiles(int *__restrict__ 
     int incl = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
+      const int up = __shfl_up(incl, d, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
       if (lane >= d) incl += up;
     }
     if (lane == 63) lds_wave[wave] = incl;
@@ -461,12 +458,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_sp_prefix(const u64 *__restrict_
     excl[i] = local;
     if (base + i < words) local += __popcll(bits[base + i]);
   }
-  int incl = local;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
+  const int incl = wave_incl_scan(local, lane);
   if (lane == 63) lds_wave[wave] = incl;
   __syncthreads();
   int before = tile_sums[blockIdx.x] + incl - local;

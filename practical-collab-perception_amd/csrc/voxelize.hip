@@ -10,6 +10,7 @@
 // 4 dense int32 tables of B*nx*ny (1 MiB each at 512x512), and O(n) int32 side arrays.
 #include <stdlib.h>
 #include "pcp_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -41,12 +42,7 @@ __device__ __forceinline__ void block_scan_excl(T (&v)[SCAN_ITEMS], T *lds_wave 
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; i++) local += v[i];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T incl = local;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    T up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
+  const T incl = wave_incl_scan(local, lane);
   if (lane == 63) lds_wave[wave] = incl;
   __syncthreads();
   T wave_base = 0, tot = 0;
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_cell_tile_sums(const int *__re
     ones += (SEG && cnt[i] == 1) ? 1u : 0u;
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
+  for (int d = 32; d >= 1; d >>= 1) {                                    // a pair in one loop: two wave_sum calls change the schedule
     s += __shfl_xor(s, d, 64);
     ones += __shfl_xor(ones, d, 64);
   }
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_cell_finish(const int *__restr
     if (SEG) pre1 += tile_singles[i];
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
+  for (int d = 32; d >= 1; d >>= 1) {                                    // a pair in one loop, as above
     pre += __shfl_xor(pre, d, 64);
     if (SEG) pre1 += __shfl_xor(pre1, d, 64);
   }
@@ -189,7 +185,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_cell_finish(const int *__restr
   u64 incl = local;
   unsigned incl1 = local1;
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
+  for (int d = 1; d < 64; d <<= 1) {                                     // a pair in one loop: two wave_incl_scan calls change the schedule
     const u64 up = __shfl_up(incl, d, 64);
     const unsigned up1 = SEG ? __shfl_up(incl1, d, 64) : 0u;
     if (lane >= d) {
@@ -465,7 +461,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_point_cells(const float *__res
       if (hslot[i] >= 0) point_rank[base + i * SCAN_THREADS + threadIdx.x] = h_cnt[hslot[i]] + hloc[i];
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) valid += __shfl_xor(valid, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) valid += __shfl_xor(valid, d, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
   if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = valid;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -712,7 +708,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_stc_scatter(const float *__res
 #pragma unroll
     for (int k = 0; k < STC_MAX_SLOTS; k++) {
 #pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
+      for (int d = 32; d >= 1; d >>= 1) {                                // a pair in one loop, as in k_cell_tile_sums
         tot[k] += __shfl_xor(tot[k], d, 64);
         bef[k] += __shfl_xor(bef[k], d, 64);
       }

@@ -418,6 +418,25 @@ def test_train_conv_table_is_the_recorded_one():
                                         'mp_conv3x3', 'mp_pointwise', 'pack_conv3x3_group', 'mp_pack_conv3x3_group', 'dilate2x'}
 
 
+def test_workspace_sizes_are_the_recorded_ones():
+    """tests/golden/workspace_bytes.json was recorded by tests/golden/make_workspace_bytes.py with the library of the commit before
+    PcpCarver (csrc/pcp_common.h) replaced the written-out carving lambdas (the file names it).  The same recorder on the built library
+    must give the same value for every size query and argument set: the order and sizes of all workspace fields are unchanged."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('make_workspace_bytes', os.path.join(GOLDEN, 'make_workspace_bytes.py'))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(rec.TABLE) as f:
+        want = json.load(f)['table']
+    got = rec.record()
+    assert sorted(got) == sorted(want) and len(want) == 8
+    for name in sorted(want):
+        assert len(want[name]) >= 36, name
+        assert got[name] == want[name], (name, [(w, g) for w, g in zip(want[name], got[name]) if w != g][:3])
+        assert any(row[-1] > 256 for row in want[name]), name          # a table of refusals (0) or minimal sizes would pin nothing
+
+
 def test_auto_resume_validates_a_checkpoint_before_anything_is_loaded(tmp_path):
     """tools/train.py: the newest checkpoint that is readable AND holds every model tensor at its shape is chosen; a torn file and a
     checkpoint of another architecture are skipped without touching the model (ADVICE r2 / VERDICT r3 item 9)."""
