@@ -629,6 +629,36 @@ int pcp_object_augment_drop_boxes(const float *gt_boxes, int32_t batch, int32_t 
                                   int32_t n_sweeps, int32_t tf_rows, const float *extent, const float *intensity, int32_t direction,
                                   float *frame_thr, float *gt_out, float *tf_out, int32_t *n_boxes_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training half of the sparse 3D convolution (csrc/spconv3d_train.hip; the forward and its tables: include/pcp_hip.h).  fp32, no float
+ * atomics: every call repeats bit for bit.
+ *
+ * Data gradient: pcp_spconv3d itself.  Submanifold layer: dx = pcp_spconv3d(dy, nbr, W') with the forward's own table (it is symmetric
+ * under mirroring the offset: nbr[k][j] == i exactly when nbr[26 - k][i] == j) and W'[k] = W[26 - k]^T packed [K][Cin][Cout].  Strided
+ * layer: dx = pcp_spconv3d(dy, inv, W'), W'[k] = W[k]^T, with the inverse table below.  No bias, residual or ReLU.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* inv (num_offsets, n_in) int32: inv[k][i] = j where nbr[k][j] == i, else -1.  nbr (num_offsets, n_out).  A fill and one launch; each
+ * (k, i) has at most one j, so the stores do not race.  Entries of nbr outside [0, n_in) are passed over. */
+int pcp_spconv_invert_nbr(const int32_t *nbr, int32_t num_offsets, int64_t n_out, int64_t n_in, int32_t *inv, void *stream);
+
+/* dw (cout, num_offsets, cin) -- the parameter's (Cout, kz, ky, kx, Cin) -- (+)= sum over rows j with nbr[k][j] in [0, n_in) of
+ * dy[j][co] * x[nbr[k][j]][ci].  x (n_in, ld_in) with cin columns, dy (n_out, cout) contiguous and 16-byte aligned; the channel pairs
+ * and the alignment rules of x are pcp_spconv3d's forward ones (PCP_ERR_UNSUPPORTED for another pair).  Two launches: workgroups over
+ * (offset, row chunk) write partial blocks to the workspace, a second kernel adds the partials of an offset in ascending chunk order.
+ * chunk_rows: rows per chunk, a multiple of 16; 0 = the library's rule (at most 32 chunks, none shorter than 1024 rows), which bounds
+ * the workspace by 27 x 32 x cout x cin_pad floats.  The workspace size depends on chunk_rows: ask with the same value.
+ * n_out == 0 or n_in == 0: dw is zero-filled (left alone when accumulating), no kernel runs. */
+size_t pcp_spconv3d_wgrad_workspace_bytes(int64_t n_out, int32_t num_offsets, int32_t cin, int32_t cout, int32_t chunk_rows);
+int pcp_spconv3d_wgrad(const float *x, int64_t n_in, int32_t cin, int32_t ld_in, const float *dy, const int32_t *nbr, int32_t num_offsets,
+                       int64_t n_out, int32_t cout, int32_t chunk_rows, void *workspace, size_t workspace_bytes, float *dw, int32_t accumulate,
+                       void *stream);
+
+/* gradient of pcp_spconv_dense: dfeat[r][c] = dcanvas[(b, y, x)][c * d + z] for row r at coords[r] = [b, z, y, x] (int32, 16-byte
+ * aligned); dcanvas (batch, h, w, channels * d) NHWC.  Every element of dfeat (n, channels) is written (zero for a row outside the grid). */
+int pcp_spconv_dense_backward(const float *dcanvas, const int32_t *coords, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h,
+                              int32_t w, float *dfeat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -736,8 +736,9 @@ extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, in
                             void *stream_) {
   if (n_in < 0 || n_out < 0 || n_in >= (1LL << 31) || n_out >= (1LL << 31) || num_offsets < 1 || num_offsets > 27 || ld_in < cin) return PCP_ERR_ARG;
   const int cin_pad = cin <= 16 ? 16 : cin;
-  const bool pair_ok = cin >= 3 && ((cin_pad == 16 && (cout == 16 || cout == 32)) || (cin_pad == 32 && (cout == 32 || cout == 64)) ||
-                                    (cin_pad == 64 && (cout == 64 || cout == 128)) || (cin_pad == 128 && cout == 128));
+  // (32 -> 16), (64 -> 32), (128 -> 64): the data gradients of the strided layers (csrc/spconv3d_train.hip)
+  const bool pair_ok = cin >= 3 && ((cin_pad == 16 && (cout == 16 || cout == 32)) || (cin_pad == 32 && (cout == 16 || cout == 32 || cout == 64)) ||
+                                    (cin_pad == 64 && (cout == 32 || cout == 64 || cout == 128)) || (cin_pad == 128 && (cout == 64 || cout == 128)));
   if (!pair_ok) return PCP_ERR_UNSUPPORTED;
   if (n_out == 0) return PCP_OK;
   if (!nbr || !w_packed || !bias || !out || (n_in > 0 && !features)) return PCP_ERR_ARG;
@@ -751,10 +752,13 @@ extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, in
                      (long long)n_out, w_packed, bias, residual, (int)relu, out)
   if (cin_pad == 16 && cout == 16) { if (vec) PCP_SPCONV(1, 1, true); else PCP_SPCONV(1, 1, false); }
   else if (cin_pad == 16 && cout == 32) { if (vec) PCP_SPCONV(1, 2, true); else PCP_SPCONV(1, 2, false); }
+  else if (cin_pad == 32 && cout == 16) PCP_SPCONV(2, 1, true);
   else if (cin_pad == 32 && cout == 32) PCP_SPCONV(2, 2, true);
   else if (cin_pad == 32 && cout == 64) PCP_SPCONV(2, 4, true);
+  else if (cin_pad == 64 && cout == 32) PCP_SPCONV(4, 2, true);
   else if (cin_pad == 64 && cout == 64) PCP_SPCONV(4, 4, true);
   else if (cin_pad == 64 && cout == 128) PCP_SPCONV(4, 8, true);
+  else if (cin_pad == 128 && cout == 64) PCP_SPCONV(8, 4, true);
   else PCP_SPCONV(8, 8, true);
 #undef PCP_SPCONV
   PCP_CHECK_LAUNCH();

@@ -1,5 +1,6 @@
 """VoxelResBackBone8x on gfx950 (pcdet/models/backbones_3d/spconv_backbone.py of the reference): four stages of residual submanifold blocks,
-three stride-2 sparse convs between them and the (3, 1, 1) conv that halves z at the end, all on pcp_spconv3d.  Inference only.  Module nesting
+three stride-2 sparse convs between them and the (3, 1, 1) conv that halves z at the end, all on pcp_spconv3d.  Inference only unless the
+model config sets MODEL.BACKBONE_3D.HIP_TRAIN (then train() is allowed and a training forward runs second_train_path.VoxelBackboneTrain).  Module nesting
 and state_dict keys are the reference's (conv_input.0.weight, conv1.0.conv1.weight / .bias, conv1.0.bn1.*, conv2.0.0.weight, ...,
 conv_out.0.weight), so a published SECOND checkpoint loads by name.
 
@@ -14,6 +15,7 @@ import torch.nn as nn
 from pcp_amd import spconv
 
 from ...utils.spconv_utils import replace_feature  # noqa: F401  (re-exported as in the reference)
+from ..packed import train_tape
 
 INFERENCE_ONLY = 'inference only'
 
@@ -94,15 +96,32 @@ class VoxelResBackBone8x(nn.Module):
             norm_fn(128), nn.ReLU())
         self.num_point_features = 128
         self.backbone_channels = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': 128}
+        self.hip_train = bool(self.model_cfg.get('HIP_TRAIN', False))         # opt-in: the HIP training path (second_train_path.py)
+        self._pcp_train = None
 
     def train(self, mode=True):
-        if mode:
+        if mode and not self.hip_train:
             raise NotImplementedError(INFERENCE_ONLY)
         return super().train(mode)
 
+    def _forward_train(self, batch_dict):
+        from ..second_train_path import VoxelBackboneTrain
+        if self._pcp_train is None:
+            self._pcp_train = VoxelBackboneTrain(self)
+        out, scales = self._pcp_train.forward(batch_dict['voxel_features'], batch_dict['voxel_coords'], batch_dict['batch_size'],
+                                              trusted=batch_dict.get('_pcp_voxels_trusted', False))
+        batch_dict.update({
+            'encoded_spconv_tensor': out, 'encoded_spconv_tensor_stride': 8,
+            'multi_scale_3d_features': dict(zip(('x_conv1', 'x_conv2', 'x_conv3', 'x_conv4'), scales)),
+            'multi_scale_3d_strides': {'x_conv1': 1, 'x_conv2': 2, 'x_conv3': 4, 'x_conv4': 8}})
+        train_tape(batch_dict).append(('backbone_3d', self._pcp_train.backward))
+        return batch_dict
+
     def forward(self, batch_dict):
         if self.training:
-            raise NotImplementedError(INFERENCE_ONLY)
+            if not self.hip_train:
+                raise NotImplementedError(INFERENCE_ONLY)
+            return self._forward_train(batch_dict)
         feats, coords = batch_dict['voxel_features'], batch_dict['voxel_coords']
         if not feats.is_cuda:
             raise RuntimeError('VoxelResBackBone8x needs CUDA/ROCm tensors; there is no CPU fallback')

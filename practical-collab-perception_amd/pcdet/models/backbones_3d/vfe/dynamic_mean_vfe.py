@@ -1,9 +1,12 @@
 """DynMeanVFE on gfx950 (pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py of the reference): the mean of every point column per voxel of the 3D
-grid, voxels in ascending merged id (what torch.unique returns), on pcp_mean_vfe -- no sort, no float atomics.  Inference only; no parameters."""
+grid, voxels in ascending merged id (what torch.unique returns), on pcp_mean_vfe -- no sort, no float atomics.  No parameters.  Inference only
+unless the model config sets MODEL.VFE.HIP_TRAIN: then train() is allowed, the forward is the same and its backward closure returns None (the
+points carry no gradient)."""
 import torch
 
 from pcp_amd import ops
 
+from ...packed import train_tape
 from .vfe_template import VFETemplate
 
 
@@ -19,12 +22,13 @@ class DynamicMeanVFE(VFETemplate):
         self.voxel_size = [float(v) for v in voxel_size]
         self.point_cloud_range = [float(v) for v in point_cloud_range]
         self._workspace = None
+        self.hip_train = bool(self.model_cfg.get('HIP_TRAIN', False))
 
     def get_output_feature_dim(self):
         return self.num_raw_point_features
 
     def train(self, mode=True):
-        if mode:
+        if mode and not self.hip_train:
             raise NotImplementedError('inference only')
         return super().train(mode)
 
@@ -33,7 +37,7 @@ class DynamicMeanVFE(VFETemplate):
 
     @torch.no_grad()
     def forward(self, batch_dict, **kwargs):
-        if self.training:
+        if self.training and not self.hip_train:
             raise NotImplementedError('inference only')
         points = batch_dict['points']
         if not points.is_cuda:
@@ -49,4 +53,6 @@ class DynamicMeanVFE(VFETemplate):
         batch_dict['voxel_features'] = feats
         batch_dict['voxel_coords'] = coords
         batch_dict['_pcp_voxels_trusted'] = True          # distinct sites inside the grid: the backbone need not read a count back to check
+        if self.training:
+            train_tape(batch_dict).append(('vfe', lambda g: None))
         return batch_dict

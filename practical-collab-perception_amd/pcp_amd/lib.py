@@ -435,6 +435,12 @@ SYMBOLS.update({
     'pcp_spconv3d': (c_i32, [vp, c_i64, c_i32, c_i32, vp, c_i32, c_i64, vp, vp, vp, c_i32, c_i32, vp, vp]),
     'pcp_spconv_dense': (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_sz, vp, vp, vp]),
 })
+SYMBOLS.update({
+    'pcp_spconv_invert_nbr': (c_i32, [vp, c_i32, c_i64, c_i64, vp, vp]),
+    'pcp_spconv3d_wgrad_workspace_bytes': (c_sz, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    'pcp_spconv3d_wgrad': (c_i32, [vp, c_i64, c_i32, c_i32, vp, vp, c_i32, c_i64, c_i32, c_i32, vp, c_sz, vp, c_i32, vp]),
+    'pcp_spconv_dense_backward': (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp]),
+})
 
 # PCP_OPT_* of include/pcp_hip.h.  The C library never reads the environment; the PCP_* variables of earlier rounds are mapped onto the option
 # table ONCE, here, when the library is loaded (set_option() changes an option later, e.g. from a test)

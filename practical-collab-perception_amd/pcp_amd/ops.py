@@ -1211,7 +1211,8 @@ def pillar_vfe(voxels, voxel_num_points, voxel_coords, voxel_size, offset, w, b,
 # the SECOND family: per-voxel mean, sparse 3D convolution index tables, the convolution, dense() (csrc/spconv3d.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 MEAN_VFE_MAX_NZ, MEAN_VFE_MAX_BATCH, MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, MEAN_VFE_COUNTERS = 64, 64, 3, 16, 4
-SPCONV_CHANNEL_PAIRS = ((16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128))       # (cin padded to 16, cout)
+# (cin padded to 16, cout); (32, 16), (64, 32), (128, 64) are the data gradients of the strided layers (train_ops.spconv3d_wgrad takes the others)
+SPCONV_CHANNEL_PAIRS = ((16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64), (64, 128), (128, 64), (128, 128))
 
 
 def mean_vfe(points, grid, num_features, *, nz, workspace=None):
@@ -1341,6 +1342,16 @@ def spconv_pack_weight(weight, cin_pad=None):
     w = weight.detach().float().reshape(cout, -1, cin).permute(1, 0, 2)
     if cin_pad != cin:
         w = torch.nn.functional.pad(w, (0, cin_pad - cin))
+    return w.contiguous()
+
+
+def spconv_pack_weight_dgrad(weight, mirror):
+    """(Cout, kz, ky, kx, Cin) -> [K][Cin][Cout]: the weights of the data gradient dx = spconv3d(dy, table, .).  mirror (a submanifold layer,
+    whose own table serves): W'[k] = W[K - 1 - k]^T; a strided layer (the inverse table, train_ops.spconv_invert_nbr): W'[k] = W[k]^T."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
+    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 2, 0)
+    if mirror:
+        w = w.flip(0)
     return w.contiguous()
 
 

@@ -959,3 +959,61 @@ def add_relu_backward(dout, out, c, dz=None, dz2=None, dout_ch_off=0, out_ch_off
                                             _chan_ptr(dz2, dz2_ch_off) if dz2 is not None else ctypes.c_void_p(0),
                                             dz2.shape[-1] if dz2 is not None else 0, rows, int(c), _stream()), 'pcp_add_relu_backward')
     return dz
+
+
+# ---- sparse 3D convolution, training half (csrc/spconv3d_train.hip): fp32 only ---------------------------------------------------------
+
+SPCONV_WGRAD_PAIRS = ((16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128))       # (cin padded to 16, cout): the forward layers
+
+
+def spconv_invert_nbr(nbr, n_in):
+    """inv (K, n_in) int32 of a strided layer's table nbr (K, n_out): inv[k][i] = j where nbr[k][j] == i, else -1"""
+    _need_cuda(nbr)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not nbr.is_contiguous():
+        raise _lib.PcpError('pcp_spconv_invert_nbr reads a contiguous int32 (K, N_out) table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
+    K, n_out = int(nbr.shape[0]), int(nbr.shape[1])
+    inv = torch.empty((K, int(n_in)), dtype=torch.int32, device=nbr.device)
+    check(_lib.load().pcp_spconv_invert_nbr(_p(nbr), K, n_out, int(n_in), _p(inv), _stream()), 'pcp_spconv_invert_nbr')
+    return inv
+
+
+def spconv3d_wgrad(x, dy, nbr, dw, accumulate=False, chunk_rows=0, workspace=None):
+    """dw (Cout, kz, ky, kx, Cin) (+)= sum_j dy[j] (x) x[nbr[k][j]] per offset k (include/pcp_hip_train.h: pcp_spconv3d_wgrad).  x (N_in, Cin),
+    dy (N_out, Cout), nbr (K, N_out) int32.  chunk_rows 0: the library's rule.  workspace: a uint8 tensor to use instead of the shared scratch."""
+    _need_cuda(x, dy, nbr, dw)
+    _need_f32('pcp_spconv3d_wgrad', x, dy, dw)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not nbr.is_contiguous():
+        raise _lib.PcpError('pcp_spconv3d_wgrad reads a contiguous int32 (K, N_out) table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
+    assert x.dim() == 2 and x.stride(1) == 1 and dy.dim() == 2 and dy.is_contiguous() and dw.is_contiguous()
+    n_in, cin = int(x.shape[0]), int(x.shape[1])
+    ld_in = int(x.stride(0)) if n_in > 1 else cin
+    K, n_out = int(nbr.shape[0]), int(nbr.shape[1])
+    cout = int(dy.shape[1])
+    if cin < 3 or (16 if cin <= 16 else cin, cout) not in SPCONV_WGRAD_PAIRS:
+        raise NotImplementedError('pcp_spconv3d_wgrad: the channel pair (Cin, Cout) = (%d, %d) has no kernel; supported: Cin 3..16 -> 16, and %s'
+                                  % (cin, cout, ', '.join('%d -> %d' % p for p in SPCONV_WGRAD_PAIRS)))
+    assert int(dy.shape[0]) == n_out and dw.numel() == cout * K * cin and int(dw.shape[0]) == cout and int(dw.shape[-1]) == cin, \
+        (tuple(dy.shape), tuple(dw.shape), K)
+    L = _lib.load()
+    need = L.pcp_spconv3d_wgrad_workspace_bytes(n_out, K, cin, cout, int(chunk_rows))
+    if need == 0:
+        raise _lib.PcpError('pcp_spconv3d_wgrad: chunk_rows %d is not a multiple of 16' % chunk_rows)
+    ws = workspace if workspace is not None else _WG_WS.get(need, x.device)
+    check(L.pcp_spconv3d_wgrad(_p(x), n_in, cin, ld_in, _p(dy), _p(nbr), K, n_out, cout, int(chunk_rows), _p(ws), ws.numel(), _p(dw),
+                               1 if accumulate else 0, _stream()), 'pcp_spconv3d_wgrad')
+    return dw
+
+
+def spconv_dense_backward(dcanvas, coords, shape4, channels):
+    """gradient of ops.spconv_dense: dfeat (N, channels) gathered from the NHWC canvas gradient (B, H, W, channels * D) at coords (N, 4) int32
+    [b, z, y, x]; every element written"""
+    _need_cuda(dcanvas, coords)
+    _need_f32('pcp_spconv_dense_backward', dcanvas)
+    B, D, H, W = (int(v) for v in shape4)
+    assert coords.dtype == torch.int32 and coords.is_contiguous() and coords.dim() == 2 and coords.shape[1] == 4
+    assert dcanvas.is_contiguous() and tuple(dcanvas.shape) == (B, H, W, channels * D), (tuple(dcanvas.shape), shape4, channels)
+    n = int(coords.shape[0])
+    dfeat = torch.empty((n, channels), dtype=torch.float32, device=dcanvas.device)
+    check(_lib.load().pcp_spconv_dense_backward(_p(dcanvas), _p(coords), n, int(channels), B, D, H, W, _p(dfeat), _stream()),
+          'pcp_spconv_dense_backward')
+    return dfeat

@@ -3,6 +3,11 @@ VoxelResBackBone8x, with their row counts, then the whole v2x_second_ego model. 
 minimum of 30.
 
     python tools/bench_spconv.py [--out ../../profiles/spconv_bench.txt]
+    python tools/bench_spconv.py --train [--out ../../profiles/spconv_train_bench.txt]
+
+--train: one training iteration of the sparse 3D stage (VoxelBackboneTrain + HeightCompression, forward and backward behind a seeded canvas
+gradient) on the B = 1 uniform cloud: every conv forward, BatchNorm, weight-gradient and data-gradient call in order, the sums per kind and
+the whole iteration (3 warm-up iterations, mean and minimum of 10).
 
 Clouds: the synthetic ego cloud (13 point features, +-52 m), 6 agents x 60 000 rows per frame, B = 1 and 4, uniform and ring.  Grid: the
 YAML's 1024 x 1024 x 40 voxels of (0.1, 0.1, 0.2) m.
@@ -19,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, '..'))
 
 from pcp_amd import ops, synth  # noqa: E402
+from pcp_amd import train_ops as tops  # noqa: E402
 
 WARMUP, RUNS = 5, 30
 TIMED = ('mean_vfe', 'spconv_table', 'spconv_build_subm', 'spconv_build_strided', 'spconv3d', 'spconv_dense')
@@ -84,10 +90,106 @@ def make_cloud(batch, dist):
     return torch.from_numpy(synth.collate(frames)).cuda()
 
 
+TRAIN_WARMUP, TRAIN_RUNS = 3, 10
+TRAIN_TIMED = ((ops, 'spconv3d', 'conv'), (tops, 'spconv3d_wgrad', 'wgrad'), (tops, 'bn_train_stats', 'bn'), (tops, 'scale_shift_act', 'bn'),
+               (tops, 'bn_act_backward', 'bn'), (tops, 'colsum', 'bias'), (tops, 'spconv_invert_nbr', 'tables'), (tops, 'add_relu', 'residual'),
+               (tops, 'add_relu_backward', 'residual'), (tops, 'accumulate', 'residual'), (ops, 'spconv_build_subm', 'tables'),
+               (ops, 'spconv_build_strided', 'tables'), (ops, 'spconv_table', 'tables'), (ops, 'spconv_dense', 'dense'),
+               (tops, 'spconv_dense_backward', 'dense'))
+
+
+class TrainRecorder:
+    """as Recorder, over the entry points one training iteration of the sparse stage goes through; `phase` tells a conv forward from a data
+    gradient (both are ops.spconv3d)"""
+
+    def __init__(self):
+        self.calls, self.orig, self.phase = [], [], 'forward'
+
+    def __enter__(self):
+        for mod, name, kind in TRAIN_TIMED:
+            self.orig.append((mod, name, getattr(mod, name)))
+            setattr(mod, name, self.wrap(name, kind, getattr(mod, name)))
+        return self
+
+    def __exit__(self, *exc):
+        for mod, name, fn in self.orig:
+            setattr(mod, name, fn)
+
+    def wrap(self, name, kind, fn):
+        def timed(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            kd, label = kind, name
+            if name == 'spconv3d':
+                kd = 'conv forward' if self.phase == 'forward' else 'dgrad'
+                label = '%-12s %3d -> %3d K=%2d rows %8d -> %8d' % (kd, a[0].shape[1], a[2].shape[1], a[1].shape[0], a[0].shape[0], a[1].shape[1])
+            elif name == 'spconv3d_wgrad':
+                label = '%-12s %3d -> %3d K=%2d rows %8d -> %8d' % ('wgrad', a[0].shape[1], a[1].shape[1], a[2].shape[0], a[0].shape[0], a[1].shape[0])
+            elif name in ('bn_train_stats', 'scale_shift_act', 'bn_act_backward', 'colsum'):
+                label = '%-16s %3d channels, rows %8d' % (name, a[2] if name == 'bn_act_backward' else a[1], a[0].shape[0])
+            self.calls.append((kd, label, e0, e1))
+            return out
+        return timed
+
+
+def train_main(args):
+    from pcdet.models.second_train_path import VoxelBackboneTrain
+    from pcp_amd.train_layers import Act
+    model = build_model()
+    model.backbone_3d.hip_train = True                    # the switch of MODEL.BACKBONE_3D.HIP_TRAIN, set on the built module
+    path = VoxelBackboneTrain(model.backbone_3d)
+    pts = make_cloud(1, 'uniform')
+    with torch.no_grad():
+        bd = model.vfe({'points': pts, 'batch_size': 1})
+    feats, coords = bd['voxel_features'], bd['voxel_coords']
+    dcanvas = None
+    per_call, wall = None, []
+    with torch.no_grad(), TrainRecorder() as rec:
+        for it in range(TRAIN_WARMUP + TRAIN_RUNS):
+            rec.calls, rec.phase = [], 'forward'
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out, _ = path.forward(feats, coords, 1, trusted=True)
+            canvas = out.dense_nhwc()
+            if dcanvas is None:
+                dcanvas = torch.from_numpy(synth.uniform(7, 1, canvas.numel(), -1.0, 1.0).reshape(tuple(canvas.shape))).cuda()
+            rec.phase = 'backward'
+            g = tops.spconv_dense_backward(dcanvas, out.indices, (1,) + tuple(out.spatial_shape), int(out.features.shape[1]))
+            path.backward(g)
+            torch.cuda.synchronize()
+            if it >= TRAIN_WARMUP:
+                wall.append((time.perf_counter() - t0) * 1e3)
+                ms = [(kd, label, e0.elapsed_time(e1)) for kd, label, e0, e1 in rec.calls]
+                per_call = per_call or [(kd, label, []) for kd, label, _ in ms]
+                for (_, _, acc), (_, _, v) in zip(per_call, ms):
+                    acc.append(v)
+    lines = ['one training iteration of the sparse 3D stage of v2x_second_ego (VoxelBackboneTrain + HeightCompression, fp32), milliseconds:',
+             'mean (min) of %d after %d warm-up iterations, measured on one run; uniform cloud, B = 1, %d rows, %d voxels'
+             % (TRAIN_RUNS, TRAIN_WARMUP, pts.shape[0], feats.shape[0]), '']
+    sums = {}
+    for kd, label, acc in per_call:
+        lines.append('  %-64s %8.3f (%7.3f)' % (label, float(np.mean(acc)), float(np.min(acc))))
+        sums[kd] = sums.get(kd, 0.0) + float(np.mean(acc))
+    lines.append('')
+    for kd in ('conv forward', 'bn', 'wgrad', 'dgrad', 'bias', 'residual', 'tables', 'dense'):
+        lines.append('  sum %-60s %8.3f' % (kd, sums.get(kd, 0.0)))
+    lines.append('  whole iteration of the stage (wall clock, host reads included)    %8.3f (%7.3f)' % (float(np.mean(wall)), float(np.min(wall))))
+    text = '\n'.join(lines) + '\n'
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--train', action='store_true', help='time one training iteration of the sparse 3D stage instead of the forward')
     args = ap.parse_args()
+    if args.train:
+        return train_main(args)
     model = build_model()
     front = [model.vfe, model.backbone_3d, model.map_to_bev_module]
     lines = ['v2x_second_ego on the device, milliseconds: mean (min) of %d after %d warm-up forwards; 6 agents x 60 000 rows per frame' % (RUNS, WARMUP)]

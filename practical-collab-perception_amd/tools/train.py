@@ -69,6 +69,9 @@ def parse_config():
         cfg.DATA_CONFIG.SYNTHETIC.GT_DROP_UNSTOCKED_GROUPS = False
     if 'GT_BOXES' not in cfg.DATA_CONFIG.SYNTHETIC:
         cfg.DATA_CONFIG.SYNTHETIC.GT_BOXES = 40                # boxes of a synthetic training frame (pcdet/datasets)
+    for section in ('VFE', 'BACKBONE_3D'):                     # HIP_TRAIN: the opt-in training path of the SECOND family (second_train_path.py)
+        if cfg.MODEL.get(section, None) is not None and 'HIP_TRAIN' not in cfg.MODEL[section]:
+            cfg.MODEL[section].HIP_TRAIN = False
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
     return args, cfg
