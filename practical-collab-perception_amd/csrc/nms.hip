@@ -25,7 +25,9 @@ constexpr int SORT_CAP = 4096;
 constexpr int SORT_THREADS = 1024;
 
 __device__ __forceinline__ u64 score_key(float s, int idx) {
-  // total order on floats (negative scores allowed), descending sort => larger key first; ties: lower index first
+  // total order on floats (negative scores allowed), descending sort => larger key first; ties: lower index first.
+  // -0.0f keys as +0.0f: the reference sorts with a float comparison, under which the two zeros tie and keep index order
+  if (s == 0.f) s = 0.f;
   unsigned u = __float_as_uint(s);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((u64)u << 32) | (u64)(0xffffffffu - (unsigned)idx);
