@@ -8,6 +8,10 @@ import torch
 
 from . import lib as _lib
 from .lib import Conv3x3, Decode, DecodeHead, DetHead, DetHeadExt, Grid, Pointwise, check
+# limits and flag values of include/pcp_hip.h that this module's checks and callers name
+from .lib import (HARD_VOXEL_COUNTERS, HARD_VOXEL_MAX_BATCH, HARD_VOXEL_MAX_FEATURES, HARD_VOXEL_MAX_T, HARD_VOXEL_MIN_FEATURES,
+                  MEAN_VFE_COUNTERS, MEAN_VFE_MAX_BATCH, MEAN_VFE_MAX_FEATURES, MEAN_VFE_MAX_NZ, MEAN_VFE_MIN_FEATURES, PFN_ABSOLUTE_XYZ,
+                  PFN_WITH_DISTANCE, PILLAR_VFE_MAX_OUT, ROWS_BUCKET_ORDER, ROWS_CELLS_READY)
 
 
 _RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
@@ -146,9 +150,6 @@ def pfn_scatter(points, vox, num_raw, w0, b0, w1, b1, canvas=None, pillar_featur
                             _p(w1), _p(b1), _p(pillar_features), _p(canvas), _stream()), 'pcp_pfn_scatter')
 
 
-ROWS_CELLS_READY, ROWS_BUCKET_ORDER = 1, 2
-
-
 def rows_workspace(grid, n, num_raw, device, workspace=None):
     """a pcp_pillarise_rows workspace large enough for (grid, n rows, num_raw); `workspace` is returned unchanged when it already is"""
     need = _lib.load().pcp_pillarise_rows_workspace_bytes(ctypes.byref(grid), n, num_raw)
@@ -255,7 +256,7 @@ def pfn_features(points, vox, num_raw, use_absolute_xyz=True, with_distance=Fals
     rows = max(vox.n, 1)
     fbuf = torch.empty((rows, fw), dtype=torch.float32, device=points.device)
     slot_pillar = torch.empty((rows,), dtype=torch.int32, device=points.device)
-    flags = (1 if use_absolute_xyz else 0) | (2 if with_distance else 0)
+    flags = (PFN_ABSOLUTE_XYZ if use_absolute_xyz else 0) | (PFN_WITH_DISTANCE if with_distance else 0)
     check(L.pcp_pfn_features(_p(points), vox.n, vox.row_stride, num_raw, flags, ctypes.byref(vox.grid), _p(vox.workspace), fw, _p(fbuf),
                              _p(slot_pillar), _stream()), 'pcp_pfn_features')
     return fbuf, slot_pillar, f
@@ -1109,11 +1110,6 @@ def topk_boxes(keys, labels, boxes, k):
 # hard voxelisation + one-layer PillarVFE: the classic PointPillar front end (csrc/hard_voxel.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 
-HARD_VOXEL_MAX_T, HARD_VOXEL_MIN_FEATURES, HARD_VOXEL_MAX_FEATURES, HARD_VOXEL_MAX_BATCH = 128, 3, 16, 64
-HARD_VOXEL_COUNTERS = 132
-PILLAR_VFE_MAX_OUT = 128
-PFN_ABSOLUTE_XYZ, PFN_WITH_DISTANCE = 1, 2
-
 
 class HardVoxelResult:
     """voxels (M, T, C) float32, voxel_coords (M, 4) int32 [b, z, y, x], voxel_num_points (M,) int32 on the device; voxels_per_frame: a
@@ -1210,7 +1206,6 @@ def pillar_vfe(voxels, voxel_num_points, voxel_coords, voxel_size, offset, w, b,
 # ---------------------------------------------------------------------------------------------------------------------
 # the SECOND family: per-voxel mean, sparse 3D convolution index tables, the convolution, dense() (csrc/spconv3d.hip)
 # ---------------------------------------------------------------------------------------------------------------------
-MEAN_VFE_MAX_NZ, MEAN_VFE_MAX_BATCH, MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, MEAN_VFE_COUNTERS = 64, 64, 3, 16, 4
 # (cin padded to 16, cout); (32, 16), (64, 32), (128, 64) are the data gradients of the strided layers (train_ops.spconv3d_wgrad takes the others)
 SPCONV_CHANNEL_PAIRS = ((16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64), (64, 128), (128, 64), (128, 128))
 

@@ -603,7 +603,7 @@ def masked_smooth_l1_rows(fused, teacher, c, thresh=1e-3):
 # PFN (train mode)
 # ---------------------------------------------------------------------------------------------------------------------
 
-PFN_TRAIN_MIN_RAW, PFN_TRAIN_MAX_RAW = 3, 26        # PCP_PFN_TRAIN_MIN_RAW / _MAX_RAW of include/pcp_hip_train.h
+PFN_TRAIN_MIN_RAW, PFN_TRAIN_MAX_RAW = _lib.PFN_TRAIN_MIN_RAW, _lib.PFN_TRAIN_MAX_RAW        # include/pcp_hip_train.h; the VFE module's refusal names them
 
 
 def pfn_train_features(points, vox, num_raw, fbuf, slot_pillar):
