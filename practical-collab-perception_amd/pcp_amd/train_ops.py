@@ -491,8 +491,9 @@ _LOSS_EXT_WS = {}
 
 def centerhead_loss_ext(desc, heads, with_grad=True, grad_scale=1.0):
     """pcp_centerhead_loss_ext: all heads in four launches.  desc: lib.HeadLossExt.  heads: list of dict(head (B,H,W,ld) raw maps, heat, tb,
-    inds, mask, ch_hm, num_class, reg_ch (channels in HEAD_ORDER concatenation order)).  A target_boxes width other than len(reg_ch) is a
-    ValueError (column j pairs with code j).  Returns (losses (H, 4) [hm, loc, hm + loc, num_pos], total (1,), [dhead per head] | None)."""
+    inds, mask, ch_hm, num_class, reg_ch (channels in HEAD_ORDER concatenation order) and, optionally, dhead: the (B,H,W,ld_d) buffer the
+    gradient goes to, of another pixel stride than head if need be).  A target_boxes width other than len(reg_ch) is a ValueError (column j
+    pairs with code j).  Returns (losses (H, 4) [hm, loc, hm + loc, num_pos], total (1,), [dhead per head] | None)."""
     assert 0 < len(heads) <= _lib.DET_MAX_HEADS, 'pcp_centerhead_loss_ext takes 1 .. %d heads' % _lib.DET_MAX_HEADS
     for i, h in enumerate(heads):
         n = len(h['reg_ch'])
@@ -510,11 +511,16 @@ def centerhead_loss_ext(desc, heads, with_grad=True, grad_scale=1.0):
         _need_cuda(buf, h['heat'], h['tb'], h['inds'], h['mask'])
         assert buf.dtype == torch.float32 and buf.is_contiguous() and tuple(buf.shape[:3]) == (desc.batch, desc.h, desc.w)
         assert h['tb'].is_contiguous() and h['heat'].is_contiguous() and h['inds'].dtype == torch.int32 and h['mask'].dtype == torch.int32
-        dh = torch.empty_like(buf) if with_grad else None
+        dh = h.get('dhead') if with_grad else None
+        if with_grad and dh is None:
+            dh = torch.empty_like(buf)
+        if dh is not None:
+            _need_cuda(dh)
+            assert dh.dtype == torch.float32 and dh.is_contiguous() and tuple(dh.shape[:3]) == tuple(buf.shape[:3])
         dheads.append(dh)
         arr[i].head, arr[i].dhead, arr[i].heatmap, arr[i].target_boxes = _p(buf).value, _p(dh).value, _p(h['heat']).value, _p(h['tb']).value
         arr[i].inds, arr[i].mask = _p(h['inds']).value, _p(h['mask']).value
-        arr[i].ld = arr[i].ld_d = buf.shape[3]
+        arr[i].ld, arr[i].ld_d = buf.shape[3], (dh if dh is not None else buf).shape[3]
         arr[i].ch_hm, arr[i].num_class = int(h['ch_hm']), int(h['num_class'])
         arr[i].n_codes = arr[i].tb_width = len(h['reg_ch'])
         for j, ch in enumerate(h['reg_ch']):
