@@ -421,8 +421,8 @@ int pcp_bev_sample_bilinear(const float *bev, int32_t batch, int32_t h, int32_t 
                             float pix_y, const uint8_t *row_mask, float *out, int32_t ld_out, void *stream);
 /* Fused HunterJr point head (hunter_jr.py:78-101 on top of the sampling above): pf = bilinear(bev, points) (n, ld_pf) is
  * written once; h = relu(pf W1^T + b1); f = relu(h W2^T + b2) + pf; head = f Wh^T + bh (n, n_out) = [cls(3) | flow(3) | embed(2)].
- * Weights are BN-folded row-major float32: w1 (hidden, c), w2 (c, hidden), wh (n_out, c).  This build: c = 384, hidden = 32,
- * n_out = 8 (PCP_ERR_UNSUPPORTED otherwise; the unfused ops remain available). */
+ * Weights are BN-folded row-major float32: w1 (hidden, c), w2 (c, hidden), wh (n_out, c).  This build: c = 256 or 384, hidden = 32
+ * or 64, n_out = 8 (PCP_ERR_UNSUPPORTED otherwise; the unfused ops remain available). */
 int pcp_hunter_point_head(const float *bev, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t ld_bev,
                           const float *points, int64_t n, int32_t row_stride, float min_x, float min_y, float pix_x,
                           float pix_y, const float *w1, const float *b1, const float *w2, const float *b2, const float *wh,

@@ -1,10 +1,14 @@
 // a14 -- HunterJr point head, fused: bilinear sampling of the BEV map at every point -> feature MLP (C -> H -> C, Linear+BN+ReLU
 // twice) + residual -> the three point heads (C -> 3 | 3 | 2) in ONE kernel.  The hidden width H is a template parameter: 32
-// (POINT_HEAD_HIDDEN_CHANNELS of the V2X-Sim configs) or 64 (the nuScenes corrector).
+// (POINT_HEAD_HIDDEN_CHANNELS of the V2X-Sim configs) or 64 (the nuScenes corrector, v2x_second_rsu).  The channel count C is the second
+// template parameter: 384 (the PointPillar trunks) or 256 (BaseBEVBackbone [128 + 128] of the SECOND trunk); everything else is refused.
 //
 // LDS and occupancy (compiler resource remarks, gfx950; the CU has 160 KB):
-//   H = 32   73 224 bytes / workgroup, 96 VGPRs, 2 waves / SIMD   -> 2 workgroups per CU, as __launch_bounds__(256, 2) asks
-//   H = 64   77 320 bytes / workgroup, 106 VGPRs, 2 waves / SIMD  -> 2 workgroups per CU (154 640 bytes of the 160 KB)
+//   C = 384, H = 32   73 224 bytes / workgroup, 96 VGPRs, 2 waves / SIMD   -> 2 workgroups per CU, as __launch_bounds__(256, 2) asks
+//   C = 384, H = 64   77 320 bytes / workgroup, 106 VGPRs, 2 waves / SIMD  -> 2 workgroups per CU (154 640 bytes of the 160 KB)
+//   C = 256, H = 32   56 840 bytes / workgroup, 89 VGPRs, 2 waves / SIMD   -> 2 workgroups per CU (a third would need <= 54 613 bytes)
+//   C = 256, H = 64   60 936 bytes / workgroup, 89 VGPRs, 2 waves / SIMD   -> 2 workgroups per CU
+// The 384 rows and their instruction streams are those of the kernel before C became a parameter (profiles/pointhead_256.txt).
 // H = 64 grows only H1s (32 x 68 floats): `red` keeps its 32-column size, phase 2 reduces the four waves' partials in two
 // 32-column halves through it (two more barriers per tile).  A 64-column `red` would take 92 KB and one workgroup per CU.
 //
@@ -24,9 +28,8 @@
 namespace {
 
 constexpr int PH_BM = 32;           // points per workgroup
-constexpr int PH_C = 384;           // BEV channels (num_bev_features of the five configs)
-constexpr int PH_LDF = PH_C + 4;    // padded row: a ds_read_b128 group's 16 lanes hit distinct slots
-// the hidden width (POINT_HEAD_HIDDEN_CHANNELS: [32] or [64]) is k_point_head's template parameter PH_H; the H1 row is padded like F's
+// the hidden width (POINT_HEAD_HIDDEN_CHANNELS: [32] or [64]) and the BEV channel count (num_bev_features: 384 behind the PointPillar
+// trunks, 256 behind BaseBEVBackbone [128 + 128] of the SECOND trunk) are k_point_head's template parameters PH_H and PH_C
 constexpr int PH_NOUT = 8;
 
 struct PointHeadParams {
@@ -58,10 +61,15 @@ __device__ __forceinline__ long long xcd_remap_ph(long long bid, long long nwg) 
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
-template <int PH_H>
+template <int PH_H, int PH_C>
 __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   static_assert(PH_H == 32 || PH_H == 64, "hidden width: one or two 32-column MFMA tiles");
-  constexpr int PH_LDH = PH_H + 4;
+  static_assert(PH_C == 256 || PH_C == 384, "channels: four waves x whole 32-column tiles, K quarters of whole groups of 8");
+  constexpr int PH_LDF = PH_C + 4;           // padded row: a ds_read_b128 group's 16 lanes hit distinct slots
+  constexpr int PH_LDH = PH_H + 4;           // the H1 row is padded like F's
+  constexpr int PH_KQ = PH_C / 4;            // a wave's K quarter in phases 2 and 4: 96 channels (64 at C = 256)
+  constexpr int PH_KG = PH_KQ / 8;           // ... in groups of 8: 12 (8)
+  constexpr int PH_CT = PH_C / 32 / 4;       // 32-channel column tiles per wave in phase 3: 3 (2)
   constexpr int PH_NT = PH_H / 32;           // 32-column tiles of the hidden layer
   __shared__ __attribute__((aligned(16))) float Fs[PH_BM * PH_LDF];
   __shared__ __attribute__((aligned(16))) float H1s[PH_BM * PH_LDH];
@@ -114,12 +122,12 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
     c_ok[tid] = ok;
   }
   __syncthreads();
-  // ---- phase 1b: gather + blend, 32 points x 96 float4 --------------------------------------------------------------------
+  // ---- phase 1b: gather + blend, 32 points x C / 4 float4 ----------------------------------------------------------------
   {
 #pragma clang fp contract(off)
-    // 12 (point, float4) items per thread; the 16 corner loads of four items are issued before any is consumed (the kernel was
+    // 12 (8 at C = 256) (point, float4) items per thread; the 16 corner loads of four items are issued before any is consumed (the kernel was
     // latency bound with 4 loads in flight per thread: 3.2 TB/s of L2-resident gathers)
-    constexpr int ITEMS = PH_BM * (PH_C / 4) / 256;      // 12
+    constexpr int ITEMS = PH_BM * (PH_C / 4) / 256;      // 12 (8)
     static_assert(ITEMS % 4 == 0, "unroll group");
     for (int it = 0; it < ITEMS; it += 4) {
       f32x4 Ia[4], Ib[4], Ic[4], Id[4];
@@ -154,17 +162,17 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   }
   __syncthreads();
 
-  // ---- phase 2: H1 partial over this wave's K quarter (96 channels = 12 groups of 8) -----------------------------------------
+  // ---- phase 2: H1 partial over this wave's K quarter (C / 4 channels in groups of 8) -------------------------------------------
   {
     f32x16 acc[PH_NT];
 #pragma unroll
     for (int t = 0; t < PH_NT; t++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-    const float *asrc = Fs + r * PH_LDF + wave * 96 + 4 * h;
-    const float *bsrc = p.w1 + r * PH_C + wave * 96 + 4 * h;          // B[k][n = 32 t + r] = W1[32 t + r][k]
+    const float *asrc = Fs + r * PH_LDF + wave * PH_KQ + 4 * h;
+    const float *bsrc = p.w1 + r * PH_C + wave * PH_KQ + 4 * h;          // B[k][n = 32 t + r] = W1[32 t + r][k]
 #pragma unroll 4
-    for (int g = 0; g < 12; g++) {
+    for (int g = 0; g < PH_KG; g++) {
       f32x4 a = *reinterpret_cast<const f32x4 *>(asrc + g * 8);
 #pragma unroll
       for (int t = 0; t < PH_NT; t++) {
@@ -191,14 +199,14 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
   }
   __syncthreads();
 
-  // ---- phase 3: final = relu(H1 W2^T + b2) + F, three 32-channel column tiles per wave, in place -----------------------------
+  // ---- phase 3: final = relu(H1 W2^T + b2) + F, C / 128 32-channel column tiles per wave, in place -------------------------
   {
     f32x4 a[PH_H / 8];
 #pragma unroll
     for (int g = 0; g < PH_H / 8; g++) a[g] = *reinterpret_cast<const f32x4 *>(H1s + r * PH_LDH + g * 8 + 4 * h);
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const int ct = wave * 3 + j;
+    for (int j = 0; j < PH_CT; j++) {
+      const int ct = wave * PH_CT + j;
       const float *bsrc = p.w2 + (ct * 32 + r) * PH_H + 4 * h;         // B[k][n] = W2[n][k]
       f32x16 acc;
 #pragma unroll
@@ -230,11 +238,11 @@ __global__ __launch_bounds__(256, 2) void k_point_head(PointHeadParams p) {
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; e++) acc[e] = 0.f;
-    const float *asrc = Fs + r * PH_LDF + wave * 96 + 4 * h;
-    const float *bsrc = p.wh + (r < PH_NOUT ? r : 0) * PH_C + wave * 96 + 4 * h;      // B[k][n = r] = Wh[r][k]
+    const float *asrc = Fs + r * PH_LDF + wave * PH_KQ + 4 * h;
+    const float *bsrc = p.wh + (r < PH_NOUT ? r : 0) * PH_C + wave * PH_KQ + 4 * h;      // B[k][n = r] = Wh[r][k]
     const float bmask = r < PH_NOUT ? 1.f : 0.f;
 #pragma unroll 4
-    for (int g = 0; g < 12; g++) {
+    for (int g = 0; g < PH_KG; g++) {
       f32x4 a = *reinterpret_cast<const f32x4 *>(asrc + g * 8);
       f32x4 bq = *reinterpret_cast<const f32x4 *>(bsrc + g * 8);
       acc = mfma32(a.x, bq.x * bmask, acc);
@@ -328,7 +336,7 @@ static int point_head_launch(const float *bev, int32_t batch, int32_t h, int32_t
                              float *head, const int32_t *order, const int32_t *order_count, float *points_mut, float flow_thresh,
                              unsigned char *dyn_mask, void *stream_) {
   if (!bev || !w1 || !b1 || !w2 || !b2 || !wh || !bh || !pf || !head || n < 0 || batch <= 0 || h <= 0 || w <= 0) return PCP_ERR_ARG;
-  if (c != PH_C || (hidden != 32 && hidden != 64) || n_out != PH_NOUT) return PCP_ERR_UNSUPPORTED;
+  if ((c != 256 && c != 384) || (hidden != 32 && hidden != 64) || n_out != PH_NOUT) return PCP_ERR_UNSUPPORTED;
   if ((ld_bev & 3) || (ld_pf & 3) || row_stride < 3 || (((uintptr_t)bev) & 15) || (((uintptr_t)pf) & 15)) return PCP_ERR_ARG;
   if (n == 0) return PCP_OK;
   if (!points) return PCP_ERR_ARG;
@@ -341,10 +349,15 @@ static int point_head_launch(const float *bev, int32_t batch, int32_t h, int32_t
   p.order = order; p.order_count = order_count;
   p.points_mut = points_mut; p.flow_thresh = flow_thresh; p.dyn_mask = dyn_mask;
   long long blocks = (n + PH_BM - 1) / PH_BM;
-  if (hidden == 32)
-    hipLaunchKernelGGL(k_point_head<32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p);
-  else
-    hipLaunchKernelGGL(k_point_head<64>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p);
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (c == 384) {
+    if (hidden == 32) hipLaunchKernelGGL((k_point_head<32, 384>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_point_head<64, 384>), grid, block, 0, stream, p);
+  } else {
+    if (hidden == 32) hipLaunchKernelGGL((k_point_head<32, 256>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_point_head<64, 256>), grid, block, 0, stream, p);
+  }
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }

@@ -7,7 +7,8 @@ Forward: conv_input (MFMA 3x3, written into the first half of a 768-channel NHWC
 point MLP (two fused Linear+BN+ReLU launches, residual add fused into the second) -> the three point heads as ONE
 384->8 linear -> dynamic-foreground test + in-place xyz correction (reference quirk Q8: batch_dict['points'] is mutated) ->
 re-sample only the corrected rows -> deterministic scatter-mean into the second half of the 768 buffer -> weightor convs
-(768->768, 768->2) -> 2-way softmax blend.  No concat copy, no torch.unique, no host sync.
+(768->768, 768->2) -> 2-way softmax blend.  No concat copy, no torch.unique, no host sync.  The widths above are those behind the
+PointPillar trunks (C = 384); behind the SECOND trunk (v2x_second_car / _rsu) C = 256 and the buffer is 512 wide -- same launches.
 """
 from functools import partial
 
@@ -19,6 +20,9 @@ from pcp_amd import lib, ops, pack
 
 from ..convnet import PackedConv, pack_conv_module
 from ..packed import PackedModule, require_eval_hip, train_tape
+
+
+FUSED_CHANNELS = (256, 384)        # num_bev_features the fused point-head kernel is built for (csrc/pointhead.hip)
 
 
 def conv_bn_relu(in_channels, out_channels, kernel_size=3, stride=1, padding=0, norm_layer=nn.BatchNorm2d):
@@ -107,8 +111,9 @@ class HunterJr(PackedModule):
         heads_b = torch.cat([ph.seg[0].bias, ph.reg_flow3d[0].bias, ph.instance_embedding[0].bias], 0).detach().float()
         heads = PackedConv('plain', heads_w.shape[1], heads_w.shape[0], False, pack.pack_plain(heads_w, heads_b))
         fused = None
-        if len(lf) == 6 and heads_w.shape == (8, 384) and tuple(lf[0].weight.shape) in ((32, 384), (64, 384)):
-            # plain row-major folded weights for the fused point-head kernel (hidden width 32 or 64)
+        C = int(heads_w.shape[1])
+        if len(lf) == 6 and C in FUSED_CHANNELS and heads_w.shape[0] == 8 and tuple(lf[0].weight.shape) in ((32, C), (64, C)):
+            # plain row-major folded weights for the fused point-head kernel (hidden width 32 or 64, 256 or 384 channels)
             f1 = pack.fold_bn(lf[0].weight.detach().float(), lf[1].weight.detach(), lf[1].bias.detach(), lf[1].running_mean,
                               lf[1].running_var, lf[1].eps)
             f2 = pack.fold_bn(lf[3].weight.detach().float(), lf[4].weight.detach(), lf[4].bias.detach(), lf[4].running_mean,
@@ -148,9 +153,10 @@ class HunterJr(PackedModule):
         pk['conv_input'].run(x, out=cat, out_ch_off=0)
         min_xy = self.point_cloud_range[:2]
         pix = [np.float32(self.voxel_size[0]) * self.bev_image_stride, np.float32(self.voxel_size[1]) * self.bev_image_stride]
-        if pk['fused'] is not None and C == 384 and self.fused_point_head:
-            # visit the points in the pillariser's bucket order (spatially sorted): the 4 x 384-float gathers of neighbouring
-            # points then hit L2; results are written at the original rows, so the output does not change
+        if pk['fused'] is not None and C in FUSED_CHANNELS and self.fused_point_head:
+            # visit the points in the pillariser's bucket order (spatially sorted): the 4 x C-float gathers of neighbouring
+            # points then hit L2; results are written at the original rows, so the output does not change.  Behind DynMeanVFE
+            # (the SECOND trunk, C = 256) there is no stash and the rows are visited in index order
             stash = batch_dict.get('_pcp_vfe', None)
             order = None
             if self.sorted_gather and stash is not None and stash['vox'].n == points.shape[0] and getattr(stash['vox'], 'has_bucket_order', True):

@@ -1,10 +1,11 @@
-"""Micro-benchmark of the fused HunterJr point head: python tools/bench_pointhead.py [--hidden 32|64] [--cloud car|nusc]
-[--points N per frame] [--frames B] [--stage]
+"""Micro-benchmark of the fused HunterJr point head: python tools/bench_pointhead.py [--hidden 32|64] [--channels 256|384]
+[--cloud car|nusc] [--points N per frame] [--frames B] [--stage]
 
 Without options: the fused kernel alone at hidden 32 on 4 x 60 000 'car' points, in index order and in the pillariser's bucket order.
 --stage times the whole point-head stage of HunterJr.forward (sampling through the re-sampling of the corrected rows, the points moved in
 place) three ways: fused in index order, fused in bucket order, and the five-launch chain (sample, two pointwise, heads, flow, re-sample).
-Every timed call gets its own copy of the cloud (the stage moves points), made outside the timed region."""
+Every timed call gets its own copy of the cloud (the stage moves points), made outside the timed region.  --channels 256 is the width of
+the SECOND trunk (v2x_second_car / _rsu); the map stays 128 x 128, read through the first half of a 2C-wide buffer as HunterJr does."""
 import argparse
 import os
 import sys
@@ -35,13 +36,14 @@ def timed(fn, clouds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--hidden', type=int, default=32, choices=[32, 64])
+    ap.add_argument('--channels', type=int, default=384, choices=[256, 384])
     ap.add_argument('--cloud', default='car', choices=['car', 'nusc'])
     ap.add_argument('--points', type=int, default=60000, help='points per frame')
     ap.add_argument('--frames', type=int, default=4)
     ap.add_argument('--stage', action='store_true', help='time the whole stage (flow correction and re-sampling included), fused and unfused')
     args = ap.parse_args()
     dev = 'cuda:0'
-    B, H, W, C, hid = args.frames, 128, 128, 384, args.hidden
+    B, H, W, C, hid = args.frames, 128, 128, args.channels, args.hidden
     cat = torch.randn((B, H, W, 2 * C), device=dev)
     if args.cloud == 'nusc':
         frames = [synth.nusc_cloud(f, args.points, with_map=True, dist='ring') for f in range(B)]
@@ -76,7 +78,7 @@ def main():
     clouds = lambda: [pts.clone() for _ in range(3 + REPS)]
     n = pts.shape[0]
     dyn = chain(pts.clone())
-    tag = 'hidden %d, %s cloud, N = %d (%d x %d), %.1f %% of the rows corrected' % (hid, args.cloud, n, B, args.points,
+    tag = '%shidden %d, %s cloud, N = %d (%d x %d), %.1f %% of the rows corrected' % ('' if C == 384 else 'C = %d, ' % C, hid, args.cloud, n, B, args.points,
                                                                                     100.0 * float(dyn.float().mean()))
     print('point-head stage, ' + tag)
     rows = [('fused, index order', lambda p: ops.hunter_point_head(cat, p, min_xy, pix, *w, channels=C, flow_thresh=0.3)),
