@@ -41,28 +41,81 @@ __device__ float gaussian_radius_f32(float height, float width, float min_overla
 
 struct BoxT { int valid, x, y, r, cls; };
 
-__global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const float *__restrict__ gt, int m, float *__restrict__ heat,
-                                                        float *__restrict__ tbox, int *__restrict__ inds, int *__restrict__ mask) {
+// One head as targets_frame sees it.  pcp_centerhead_targets leaves the optional parts absent; everything the two entry points do
+// differently on purpose is a field here.
+struct TgtHead {
+  int bw, tw;                        // row width of gt_boxes (class in the last column; 10: vx, vy before it) and of target_boxes
+  int num_class;                     // channels of the heat map
+  float *heat, *tbox;                // the four outputs, all frames
+  int *inds, *mask;
+  const int *class_to_local;         // the head's class table; nullptr: the head owns classes 1 .. num_class
+  const pcp_target_head_t *iou;      // raw head maps and channels the IoU column decodes; nullptr: no IoU column
+  bool zero_heat;                    // the block zeroes its heat-map slab, so the assignment is one launch; false: the host zeroed it
+  bool guard_boxes;                  // also test i < TGT_MAX_BOXES around boxes[].  Both entry points refuse max_boxes > TGT_MAX_BOXES on
+                                     // the host, so either form is safe; the flag only keeps each kernel's code as it was
+};
+
+// head-local class of a row, 1-based (0: not this head's), from its class column
+__device__ __forceinline__ int local_class(const TgtHead &f, float c) {
+  if (!f.class_to_local) return (c >= 1.f && c <= (float)f.num_class) ? (int)c : 0;
+  const int gc = (c >= 1.f && c < (float)PCP_TGT_MAX_CLASSES) ? (int)c : 0;
+  return f.class_to_local[gc];
+}
+
+// box_utils.py:6-25 as it stands: the (3, 4) sign table is reshaped with .view(4, 3), NOT transposed, so the four "corners" are
+// (+,+), (-,-), (+,-), (+,+) -- three distinct points.  The rectangle is the axis-aligned hull of those, rotated (common_utils.py:39-61:
+// x' = x cos - y sin, y' = x sin + y cos) and shifted to the centre.
+__device__ void aa_rect(float x, float y, float dx, float dy, float angle, float *r) {
+  const float c = cosf(angle), s = sinf(angle);
+  const float hx = 0.5f * dx, hy = 0.5f * dy;
+  const float sx[4] = {1.f, -1.f, 1.f, 1.f}, sy[4] = {1.f, -1.f, -1.f, 1.f};
+  float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float lx = hx * sx[i], ly = hy * sy[i];
+    const float wx = lx * c + ly * (-s) + x;
+    const float wy = lx * s + ly * c + y;
+    x0 = fminf(x0, wx); x1 = fmaxf(x1, wx);
+    y0 = fminf(y0, wy); y1 = fmaxf(y1, wy);
+  }
+  r[0] = x0; r[1] = y0; r[2] = x1; r[3] = y1;
+}
+
+// box_utils.py:39-67
+__device__ float aa_iou(const float *a, const float *b) {
+  const float ix1 = fminf(a[2], b[2]), iy1 = fminf(a[3], b[3]);
+  const float ix0 = fmaxf(a[0], b[0]), iy0 = fmaxf(a[1], b[1]);
+  const float inter = fmaxf(ix1 - ix0, 0.f) * fmaxf(iy1 - iy0, 0.f);
+  const float a1 = fmaxf(a[2] - a[0], 0.f) * fmaxf(a[3] - a[1], 0.f);
+  const float a2 = fmaxf(b[2] - b[0], 0.f) * fmaxf(b[3] - b[1], 0.f);
+  const float uni = a1 + a2 - inter;
+  return uni > 0.f ? inter / uni : 0.f;
+}
+
+// CenterHead target assignment (center_head.py:166-268): frame b of one head per workgroup of TGT_THREADS, gt_boxes (batch, m, bw).
+// pcp_centerhead_targets (a15) and pcp_centerhead_targets_ext (a15x: several heads, velocity codes, the IoU column) both run this body.
+__device__ __forceinline__ void targets_frame(const pcp_target_t &d, const TgtHead &f, const float *gt, int m, int b) {
   __shared__ BoxT boxes[TGT_MAX_BOXES];
   __shared__ int rank_of[TGT_MAX_BOXES];
   __shared__ int wave_tot[TGT_THREADS / 64];
   __shared__ int base;
-  const int b = blockIdx.x;
   const int tid = threadIdx.x;
-  const float *g = gt + (long long)b * m * 8;
+  const int bw = f.bw, tw = f.tw, ncls = f.num_class;
+  const float *g = gt + (long long)b * m * bw;
+  float *heat = f.heat + (long long)b * d.h * d.w * ncls, *tbox = f.tbox + (long long)b * d.k * tw;
+  int *inds = f.inds + (long long)b * d.k, *mask = f.mask + (long long)b * d.k;
   if (tid == 0) base = 0;
   // zero this frame's sparse outputs
-  for (int i = tid; i < d.k * 8; i += TGT_THREADS) tbox[(long long)b * d.k * 8 + i] = 0.f;
-  for (int i = tid; i < d.k; i += TGT_THREADS) { inds[(long long)b * d.k + i] = 0; mask[(long long)b * d.k + i] = 0; }
+  for (int i = tid; i < d.k * tw; i += TGT_THREADS) tbox[i] = 0.f;
+  for (int i = tid; i < d.k; i += TGT_THREADS) { inds[i] = 0; mask[i] = 0; }
+  if (f.zero_heat)
+    for (int i = tid; i < d.h * d.w * ncls; i += TGT_THREADS) heat[i] = 0.f;
   __syncthreads();
-  // rank of each foreground row among the rows of this head (class filter of center_head.py:192-204 keeps order)
+  // rank of each foreground row among the rows of this head, in row order (class filter of center_head.py:192-210)
   for (int start = 0; start < m; start += TGT_THREADS) {
     const int i = start + tid;
-    int fg = 0;
-    if (i < m) {
-      const float c = g[i * 8 + 7];
-      fg = (c >= 1.f && c <= (float)d.num_class) ? 1 : 0;
-    }
+    const int local = i < m ? local_class(f, g[i * bw + bw - 1]) : 0;
+    const int fg = local > 0 ? 1 : 0;
     const unsigned long long bal = __ballot(fg);
     const int lane = tid & 63, wv = tid >> 6;
     const int before = __popcll(bal & ((1ull << lane) - 1ull));
@@ -70,16 +123,19 @@ __global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const f
     __syncthreads();
     int off = base;
     for (int w = 0; w < wv; ++w) off += wave_tot[w];
-    if (i < m) rank_of[i] = fg ? off + before : -1;
+    if (i < m) {
+      rank_of[i] = fg ? off + before : -1;
+      if (f.class_to_local) boxes[i].cls = local - 1;          // the table lookup is kept for the box loop
+    }
     __syncthreads();
     if (tid == 0) { int t = 0; for (int w = 0; w < TGT_THREADS / 64; ++w) t += wave_tot[w]; base += t; }
     __syncthreads();
   }
   for (int i = tid; i < m; i += TGT_THREADS) {
-    BoxT bx{0, 0, 0, 0, 0};
+    BoxT bx{0, 0, 0, 0, f.class_to_local ? boxes[i].cls : 0};
     const int k = rank_of[i];
     if (k >= 0 && k < d.k) {
-      const float *r = g + i * 8;
+      const float *r = g + i * bw;
       float cx = (r[0] - d.min_x) / d.voxel_x / d.stride;
       float cy = (r[1] - d.min_y) / d.voxel_y / d.stride;
       cx = fminf(fmaxf(cx, 0.f), (float)d.w - 0.5f);
@@ -91,11 +147,13 @@ __global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const f
         float rad = gaussian_radius_f32(dx, dy, d.gaussian_overlap);
         int ri = (rad == rad) ? (int)rad : 0;
         if (ri < d.min_radius) ri = d.min_radius;
-        bx.valid = 1; bx.x = ix; bx.y = iy; bx.r = ri; bx.cls = (int)r[7] - 1;
-        const long long o = ((long long)b * d.k + k);
-        inds[o] = iy * d.w + ix;
-        mask[o] = 1;
-        float *t = tbox + o * 8;
+        bx.valid = 1; bx.x = ix; bx.y = iy; bx.r = ri;
+        // no table: a row that has a slot passed the range test, so its class converts directly.  Open-coded: the trip through LDS,
+        // or a second range test, costs k_targets 1 % of a targets + loss call (profiles/centerhead_train_twins.txt)
+        if (!f.class_to_local) bx.cls = (int)r[bw - 1] - 1;
+        inds[k] = iy * d.w + ix;
+        mask[k] = 1;
+        float *t = tbox + (long long)k * tw;
         t[0] = cx - (float)ix;
         t[1] = cy - (float)iy;
         t[2] = r[2];
@@ -104,14 +162,27 @@ __global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const f
         t[5] = logf(r[5]);
         t[6] = cosf(r[6]);
         t[7] = sinf(r[6]);
+        if (bw == 10) { t[8] = r[7]; t[9] = r[8]; }
+        if (f.iou) {
+          // center_head.py:213-242: the prediction at the ground-truth centre's cell, decoded, against the ground-truth box
+          const pcp_target_head_t &hd = *f.iou;
+          const float *px = hd.head + (((long long)b * d.h + iy) * d.w + ix) * hd.ld;
+          const float pxw = ((float)ix + px[hd.ch_center]) * d.stride * d.voxel_x + d.min_x;
+          const float pyw = ((float)iy + px[hd.ch_center + 1]) * d.stride * d.voxel_y + d.min_y;
+          const float ang = atan2f(px[hd.ch_rot + 1], px[hd.ch_rot]);
+          float ra[4], rb[4];
+          aa_rect(pxw, pyw, expf(px[hd.ch_dim]), expf(px[hd.ch_dim + 1]), ang, ra);
+          aa_rect(r[0], r[1], r[3], r[4], r[6], rb);
+          t[tw - 1] = 2.0f * aa_iou(ra, rb) - 1.f;
+        }
       }
     }
-    if (i < TGT_MAX_BOXES) boxes[i] = bx;
+    if (!f.guard_boxes || i < TGT_MAX_BOXES) boxes[i] = bx;
   }
   __syncthreads();
   // gaussian splat with max blending (order independent); float64 exp then one rounding, like numpy float64 -> .float()
-  int *hm = reinterpret_cast<int *>(heat + (long long)b * d.h * d.w * d.num_class);
-  for (int i = 0; i < m && i < TGT_MAX_BOXES; ++i) {
+  int *hm = reinterpret_cast<int *>(heat);
+  for (int i = 0; i < m && (!f.guard_boxes || i < TGT_MAX_BOXES); ++i) {
     const BoxT bx = boxes[i];
     if (!bx.valid) continue;
     const int r = bx.r;
@@ -124,9 +195,31 @@ __global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const f
     for (int p = tid; p < ww * hh; p += TGT_THREADS) {
       const int py = p / ww - top, px = p % ww - left;
       const float v = (float)exp(-(double)(px * px + py * py) * inv);
-      atomicMax(hm + ((long long)(bx.y + py) * d.w + (bx.x + px)) * d.num_class + bx.cls, __float_as_int(v));
+      atomicMax(hm + ((long long)(bx.y + py) * d.w + (bx.x + px)) * ncls + bx.cls, __float_as_int(v));
     }
   }
+}
+
+// grid = frames.  The one-head form: classes 1 .. num_class, 8-column rows, no IoU column; the host zeroed the heat map before the launch.
+__global__ __launch_bounds__(TGT_THREADS) void k_targets(pcp_target_t d, const float *__restrict__ gt, int m, float *__restrict__ heat,
+                                                        float *__restrict__ tbox, int *__restrict__ inds, int *__restrict__ mask) {
+  const TgtHead f = {8, 8, d.num_class, heat, tbox, inds, mask, nullptr, nullptr, /*zero_heat*/ false, /*guard_boxes*/ true};
+  targets_frame(d, f, gt, m, blockIdx.x);
+}
+
+struct TgtExtParams {
+  pcp_target_t d;
+  pcp_target_head_t heads[PCP_DET_MAX_HEADS];
+  int bw, with_iou, tw;            // row width of gt_boxes, IoU column requested, row width of target_boxes
+};
+
+// grid = heads x frames: block (h * batch + b).  The head's class table, 8- or 10-column rows and the IoU column; the block zeroes its
+// own heat-map slab, so the whole assignment is this one launch.
+__global__ __launch_bounds__(TGT_THREADS) void k_targets_ext(TgtExtParams p, const float *__restrict__ gt, int m) {
+  const pcp_target_head_t &hd = p.heads[blockIdx.x / p.d.batch];
+  const TgtHead f = {p.bw, p.tw, hd.num_class, hd.heatmap, hd.target_boxes, hd.inds, hd.mask, hd.class_to_local,
+                     p.with_iou ? &hd : nullptr, /*zero_heat*/ true, /*guard_boxes*/ false};
+  targets_frame(p.d, f, gt, m, blockIdx.x % p.d.batch);
 }
 
 // ---- losses ---------------------------------------------------------------------------------------------------------------
@@ -139,30 +232,78 @@ __device__ __forceinline__ float clamped_sigmoid(float x, int *inside) {
   return fminf(fmaxf(s, 1e-4f), 1.f - 1e-4f);
 }
 
+// neg_loss_cornernet (loss_utils.py:264-290): a thread's sums, and what one heat-map element adds to them (x the raw logit, gtv the
+// target).  By value: accumulators passed by reference end up in scratch.
+struct FocalSums { double pos, neg, npos; };
+
+__device__ __forceinline__ FocalSums focal_add(FocalSums a, float x, float gtv) {
+  int inside;
+  const float p = clamped_sigmoid(x, &inside);
+  if (gtv == 1.f) {
+    a.pos += (double)(logf(p) * (1.f - p) * (1.f - p));
+    a.npos += 1.0;
+  } else if (gtv < 1.f) {
+    const float w = (1.f - gtv) * (1.f - gtv);
+    a.neg += (double)(logf(1.f - p) * p * p * (w * w));
+  }
+  return a;
+}
+
+// ... and its derivative by the logit, weighted: zero where the sigmoid clamp is active; npos is the head's count of gtv == 1 elements
+__device__ __forceinline__ float focal_grad(float x, float gtv, double npos, float cls_weight, float grad_scale) {
+  const float coef = -cls_weight * grad_scale / (float)(npos == 0.0 ? 1.0 : npos);
+  int inside;
+  const float p = clamped_sigmoid(x, &inside);
+  float dldp = 0.f;
+  if (gtv == 1.f) {
+    if (npos != 0.0) dldp = (1.f - p) * (1.f - p) / p - 2.f * (1.f - p) * logf(p);
+  } else if (gtv < 1.f) {
+    const float w = (1.f - gtv) * (1.f - gtv);
+    dldp = (w * w) * (-(p * p) / (1.f - p) + 2.f * p * logf(1.f - p));
+  }
+  return inside ? coef * dldp * p * (1.f - p) : 0.f;
+}
+
+// the mask sum as the L1 terms divide by it: torch.clamp_min(num, 1.0) of _reg_loss
+__device__ __forceinline__ double clamped_num(double mask_sum) { return mask_sum < 1.0 ? 1.0 : mask_sum; }
+
+// one head's losses from its sums (center_head.py:274-295): out = [hm_loss (weighted), loc_loss (weighted), hm + loc, num_pos]; returns
+// out[2].  sums[j] is the L1 sum of code j; its mean is rounded to float32 before the code weight, as the reference's float32 tensor is.
+__device__ __forceinline__ float head_losses(double pos, double neg, double npos, double mask_sum, const double *sums, int n_codes,
+                                             const float *code_weights, float cls_weight, float loc_weight, float *out) {
+  const double hm = (npos == 0.0 ? -neg : -(pos + neg) / npos) * (double)cls_weight;
+  const double num = clamped_num(mask_sum);
+  double loc = 0;
+  for (int j = 0; j < n_codes; ++j) loc += (double)(float)(sums[j] / num) * (double)code_weights[j];
+  loc *= (double)loc_weight;
+  out[0] = (float)hm;
+  out[1] = (float)loc;
+  out[2] = (float)(hm + loc);
+  out[3] = (float)npos;
+  return (float)(hm + loc);
+}
+
+// the L1 term of one code: its sign (0 where prediction and target are equal: nothing is added), and what one slot adds to dL/d(pred)
+__device__ __forceinline__ float l1_sign(float diff) { return diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f); }
+__device__ __forceinline__ float l1_grad_term(float sg, float loc_weight, float code_weight, float grad_scale, double num) {
+  return sg * loc_weight * code_weight * grad_scale / (float)num;
+}
+
 __global__ __launch_bounds__(256) void k_focal_reduce(pcp_headloss_t d, const float *__restrict__ head, const float *__restrict__ heat,
                                                      double *acc) {
   __shared__ double sh[4];
   const long long total = (long long)d.batch * d.h * d.w * d.num_class;
-  double pos = 0, neg = 0, npos = 0;
+  FocalSums a = {0, 0, 0};
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     const int c = (int)(t % d.num_class);
     const long long pix = t / d.num_class;
-    int inside;
-    const float p = clamped_sigmoid(head[pix * d.ld + d.ch_hm + c], &inside);
-    const float gtv = heat[t];
-    if (gtv == 1.f) {
-      pos += (double)(logf(p) * (1.f - p) * (1.f - p));
-      npos += 1.0;
-    } else if (gtv < 1.f) {
-      const float w = (1.f - gtv) * (1.f - gtv);
-      neg += (double)(logf(1.f - p) * p * p * (w * w));
-    }
+    a = focal_add(a, head[pix * d.ld + d.ch_hm + c], heat[t]);
   }
-  double s = block_sum_lane0(pos, sh);
+  double s = block_sum_lane0(a.pos, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 0, s);
-  s = block_sum_lane0(neg, sh);
+  s = block_sum_lane0(a.neg, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 1, s);
-  s = block_sum_lane0(npos, sh);
+  s = block_sum_lane0(a.npos, sh);
   if (threadIdx.x == 0) atomicAdd(acc + 2, s);
 }
 
@@ -192,19 +333,9 @@ __global__ __launch_bounds__(256) void k_reg_reduce(pcp_headloss_t d, const floa
   }
 }
 
-// losses_out: [0] hm_loss (weighted)  [1] loc_loss (weighted)  [2] hm + loc  [3] num_pos
 __global__ void k_headloss_finalize(pcp_headloss_t d, const double *acc, float *losses_out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const double npos = acc[2];
-  const double hm = (npos == 0.0 ? -acc[1] : -(acc[0] + acc[1]) / npos) * (double)d.cls_weight;
-  const double num = acc[3] < 1.0 ? 1.0 : acc[3];
-  double loc = 0;
-  for (int j = 0; j < 8; ++j) loc += (double)(float)(acc[4 + j] / num) * (double)d.code_weights[j];
-  loc *= (double)d.loc_weight;
-  losses_out[0] = (float)hm;
-  losses_out[1] = (float)loc;
-  losses_out[2] = (float)(hm + loc);
-  losses_out[3] = (float)npos;
+  head_losses(acc[0], acc[1], acc[2], acc[3], acc + 4, 8, d.code_weights, d.cls_weight, d.loc_weight, losses_out);
 }
 
 // dense part of dL/d(head): heat-map channels get the focal gradient, every other channel of the ld_d-wide row is zeroed
@@ -217,21 +348,7 @@ __global__ __launch_bounds__(256) void k_focal_grad(pcp_headloss_t d, const floa
   const long long pix = t / d.ld_d;
   float gval = 0.f;
   const int c = ch - d.ch_hm;
-  if (c >= 0 && c < d.num_class) {
-    const double npos = acc[2];
-    const float coef = -d.cls_weight * grad_scale / (float)(npos == 0.0 ? 1.0 : npos);
-    int inside;
-    const float p = clamped_sigmoid(head[pix * d.ld + ch], &inside);
-    const float gtv = heat[pix * d.num_class + c];
-    float dldp = 0.f;
-    if (gtv == 1.f) {
-      if (npos != 0.0) dldp = (1.f - p) * (1.f - p) / p - 2.f * (1.f - p) * logf(p);
-    } else if (gtv < 1.f) {
-      const float w = (1.f - gtv) * (1.f - gtv);
-      dldp = (w * w) * (-(p * p) / (1.f - p) + 2.f * p * logf(1.f - p));
-    }
-    gval = inside ? coef * dldp * p * (1.f - p) : 0.f;
-  }
+  if (c >= 0 && c < d.num_class) gval = focal_grad(head[pix * d.ld + ch], heat[pix * d.num_class + c], acc[2], d.cls_weight, grad_scale);
   dhead[t] = gval;
 }
 
@@ -240,16 +357,15 @@ __global__ __launch_bounds__(256) void k_reg_grad(pcp_headloss_t d, const float 
                                                  float grad_scale, float *__restrict__ dhead) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= d.batch * d.k || !mask[t]) return;
-  const double num = acc[3] < 1.0 ? 1.0 : acc[3];
+  const double num = clamped_num(acc[3]);
   const int b = t / d.k;
   const long long pix = (long long)b * d.h * d.w + inds[t];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float tv = tbox[(long long)t * 8 + j];
     if (tv != tv) continue;
-    const float diff = head[pix * d.ld + d.reg_ch[j]] - tv;
-    const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-    if (sg != 0.f) atomicAdd(dhead + pix * d.ld_d + d.reg_ch[j], sg * d.loc_weight * d.code_weights[j] * grad_scale / (float)num);
+    const float sg = l1_sign(head[pix * d.ld + d.reg_ch[j]] - tv);
+    if (sg != 0.f) atomicAdd(dhead + pix * d.ld_d + d.reg_ch[j], l1_grad_term(sg, d.loc_weight, d.code_weights[j], grad_scale, num));
   }
 }
 
@@ -363,156 +479,11 @@ __global__ void k_masked_sl1_finalize(const double *__restrict__ acc, int nb, fl
 }
 }  // namespace
 
-// ---- a15x: several heads, velocity codes, the IoU branch (center_head.py:168-300 for the nuScenes head) ------------------------
+// ---- a15x: the losses of several heads, with velocity and IoU codes (center_head.py:270-300 for the nuScenes head) ---------------
+// Per element and per head these are the a15 functions above (focal_add, focal_grad, head_losses, l1_grad_term); the kernels differ
+// on purpose: block partials added in a fixed order and ordered stores where a15 has float64 / float atomics, and no NaN-target mask.
 namespace {
 
-struct TgtExtParams {
-  pcp_target_t d;
-  pcp_target_head_t heads[PCP_DET_MAX_HEADS];
-  int bw, with_iou, tw;            // row width of gt_boxes, IoU column requested, row width of target_boxes
-};
-
-// box_utils.py:6-25 as it stands: the (3, 4) sign table is reshaped with .view(4, 3), NOT transposed, so the four "corners" are
-// (+,+), (-,-), (+,-), (+,+) -- three distinct points.  The rectangle is the axis-aligned hull of those, rotated (common_utils.py:39-61:
-// x' = x cos - y sin, y' = x sin + y cos) and shifted to the centre.
-__device__ void aa_rect(float x, float y, float dx, float dy, float angle, float *r) {
-  const float c = cosf(angle), s = sinf(angle);
-  const float hx = 0.5f * dx, hy = 0.5f * dy;
-  const float sx[4] = {1.f, -1.f, 1.f, 1.f}, sy[4] = {1.f, -1.f, -1.f, 1.f};
-  float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lx = hx * sx[i], ly = hy * sy[i];
-    const float wx = lx * c + ly * (-s) + x;
-    const float wy = lx * s + ly * c + y;
-    x0 = fminf(x0, wx); x1 = fmaxf(x1, wx);
-    y0 = fminf(y0, wy); y1 = fmaxf(y1, wy);
-  }
-  r[0] = x0; r[1] = y0; r[2] = x1; r[3] = y1;
-}
-
-// box_utils.py:39-67
-__device__ float aa_iou(const float *a, const float *b) {
-  const float ix1 = fminf(a[2], b[2]), iy1 = fminf(a[3], b[3]);
-  const float ix0 = fmaxf(a[0], b[0]), iy0 = fmaxf(a[1], b[1]);
-  const float inter = fmaxf(ix1 - ix0, 0.f) * fmaxf(iy1 - iy0, 0.f);
-  const float a1 = fmaxf(a[2] - a[0], 0.f) * fmaxf(a[3] - a[1], 0.f);
-  const float a2 = fmaxf(b[2] - b[0], 0.f) * fmaxf(b[3] - b[1], 0.f);
-  const float uni = a1 + a2 - inter;
-  return uni > 0.f ? inter / uni : 0.f;
-}
-
-// grid = heads x frames: block (h * batch + b).  k_targets with a per-head class table, 8- or 10-column rows and the IoU column; the
-// block also zeroes its own heat-map slab, so the whole assignment is this one launch.
-__global__ __launch_bounds__(TGT_THREADS) void k_targets_ext(TgtExtParams p, const float *__restrict__ gt, int m) {
-  __shared__ BoxT boxes[TGT_MAX_BOXES];
-  __shared__ int rank_of[TGT_MAX_BOXES];
-  __shared__ int wave_tot[TGT_THREADS / 64];
-  __shared__ int base;
-  const pcp_target_t &d = p.d;
-  const int hi = blockIdx.x / d.batch, b = blockIdx.x % d.batch;
-  const pcp_target_head_t &hd = p.heads[hi];
-  const int tid = threadIdx.x;
-  const int bw = p.bw, tw = p.tw, ncls = hd.num_class;
-  const float *g = gt + (long long)b * m * bw;
-  float *tbox = hd.target_boxes + (long long)b * d.k * tw;
-  int *inds = hd.inds + (long long)b * d.k, *mask = hd.mask + (long long)b * d.k;
-  float *heat = hd.heatmap + (long long)b * d.h * d.w * ncls;
-  if (tid == 0) base = 0;
-  for (int i = tid; i < d.k * tw; i += TGT_THREADS) tbox[i] = 0.f;
-  for (int i = tid; i < d.k; i += TGT_THREADS) { inds[i] = 0; mask[i] = 0; }
-  for (int i = tid; i < d.h * d.w * ncls; i += TGT_THREADS) heat[i] = 0.f;
-  __syncthreads();
-  // head-local class of each row (0: not this head's), rank among this head's rows in row order (center_head.py:200-210)
-  for (int start = 0; start < m; start += TGT_THREADS) {
-    const int i = start + tid;
-    int local = 0;
-    if (i < m) {
-      const float c = g[i * bw + bw - 1];
-      const int gc = (c >= 1.f && c < (float)PCP_TGT_MAX_CLASSES) ? (int)c : 0;
-      local = hd.class_to_local[gc];
-    }
-    const int fg = local > 0 ? 1 : 0;
-    const unsigned long long bal = __ballot(fg);
-    const int lane = tid & 63, wv = tid >> 6;
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wv] = __popcll(bal);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wv; ++w) off += wave_tot[w];
-    if (i < m) {
-      rank_of[i] = fg ? off + before : -1;
-      boxes[i].cls = local - 1;
-    }
-    __syncthreads();
-    if (tid == 0) { int t = 0; for (int w = 0; w < TGT_THREADS / 64; ++w) t += wave_tot[w]; base += t; }
-    __syncthreads();
-  }
-  for (int i = tid; i < m; i += TGT_THREADS) {
-    BoxT bx{0, 0, 0, 0, boxes[i].cls};
-    const int k = rank_of[i];
-    if (k >= 0 && k < d.k) {
-      const float *r = g + i * bw;
-      float cx = (r[0] - d.min_x) / d.voxel_x / d.stride;
-      float cy = (r[1] - d.min_y) / d.voxel_y / d.stride;
-      cx = fminf(fmaxf(cx, 0.f), (float)d.w - 0.5f);
-      cy = fminf(fmaxf(cy, 0.f), (float)d.h - 0.5f);
-      const int ix = (int)cx, iy = (int)cy;
-      const float dx = r[3] / d.voxel_x / d.stride;
-      const float dy = r[4] / d.voxel_y / d.stride;
-      if (dx > 0.f && dy > 0.f) {
-        float rad = gaussian_radius_f32(dx, dy, d.gaussian_overlap);
-        int ri = (rad == rad) ? (int)rad : 0;
-        if (ri < d.min_radius) ri = d.min_radius;
-        bx.valid = 1; bx.x = ix; bx.y = iy; bx.r = ri;
-        inds[k] = iy * d.w + ix;
-        mask[k] = 1;
-        float *t = tbox + (long long)k * tw;
-        t[0] = cx - (float)ix;
-        t[1] = cy - (float)iy;
-        t[2] = r[2];
-        t[3] = logf(r[3]);
-        t[4] = logf(r[4]);
-        t[5] = logf(r[5]);
-        t[6] = cosf(r[6]);
-        t[7] = sinf(r[6]);
-        if (bw == 10) { t[8] = r[7]; t[9] = r[8]; }
-        if (p.with_iou) {
-          // center_head.py:213-242: the prediction at the ground-truth centre's cell, decoded, against the ground-truth box
-          const float *px = hd.head + (((long long)b * d.h + iy) * d.w + ix) * hd.ld;
-          const float pxw = ((float)ix + px[hd.ch_center]) * d.stride * d.voxel_x + d.min_x;
-          const float pyw = ((float)iy + px[hd.ch_center + 1]) * d.stride * d.voxel_y + d.min_y;
-          const float ang = atan2f(px[hd.ch_rot + 1], px[hd.ch_rot]);
-          float ra[4], rb[4];
-          aa_rect(pxw, pyw, expf(px[hd.ch_dim]), expf(px[hd.ch_dim + 1]), ang, ra);
-          aa_rect(r[0], r[1], r[3], r[4], r[6], rb);
-          t[tw - 1] = 2.0f * aa_iou(ra, rb) - 1.f;
-        }
-      }
-    }
-    boxes[i] = bx;
-  }
-  __syncthreads();
-  int *hm = reinterpret_cast<int *>(heat);
-  for (int i = 0; i < m; ++i) {
-    const BoxT bx = boxes[i];
-    if (!bx.valid) continue;
-    const int r = bx.r;
-    const int left = min(bx.x, r), right = min(d.w - bx.x, r + 1);
-    const int top = min(bx.y, r), bottom = min(d.h - bx.y, r + 1);
-    const int ww = left + right, hh = top + bottom;
-    if (ww <= 0 || hh <= 0) continue;
-    const double sigma = (double)(2 * r + 1) / 6.0;
-    const double inv = 1.0 / (2.0 * sigma * sigma);
-    for (int q = tid; q < ww * hh; q += TGT_THREADS) {
-      const int py = q / ww - top, px = q % ww - left;
-      const float v = (float)exp(-(double)(px * px + py * py) * inv);
-      atomicMax(hm + ((long long)(bx.y + py) * d.w + (bx.x + px)) * ncls + bx.cls, __float_as_int(v));
-    }
-  }
-}
-
-// ---- losses of all heads ---------------------------------------------------------------------------------------------------------
 // workspace (double) per head: [LX_BLOCKS][3] focal partials (pos, neg, num_pos) | [1 + 16] mask sum and per-code L1 sums | [2] num_pos, num
 constexpr int LX_BLOCKS = 64;
 constexpr int LX_PER_HEAD = LX_BLOCKS * 3 + 1 + PCP_HEADLOSS_MAX_CODES + 2;
@@ -533,26 +504,17 @@ __global__ __launch_bounds__(256) void k_lossx_reduce(LossExtParams p, double *_
   double *w = ws + (long long)blockIdx.y * LX_PER_HEAD;
   if (blockIdx.x < LX_BLOCKS) {
     const long long total = (long long)d.batch * d.h * d.w * hd.num_class;
-    double pos = 0, neg = 0, npos = 0;
+    FocalSums a = {0, 0, 0};
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)LX_BLOCKS * blockDim.x) {
       const int c = (int)(t % hd.num_class);
       const long long pix = t / hd.num_class;
-      int inside;
-      const float q = clamped_sigmoid(hd.head[pix * hd.ld + hd.ch_hm + c], &inside);
-      const float gtv = hd.heatmap[t];
-      if (gtv == 1.f) {
-        pos += (double)(logf(q) * (1.f - q) * (1.f - q));
-        npos += 1.0;
-      } else if (gtv < 1.f) {
-        const float wt = (1.f - gtv) * (1.f - gtv);
-        neg += (double)(logf(1.f - q) * q * q * (wt * wt));
-      }
+      a = focal_add(a, hd.head[pix * hd.ld + hd.ch_hm + c], hd.heatmap[t]);
     }
-    double s = block_sum_lane0(pos, sh);
+    double s = block_sum_lane0(a.pos, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 0] = s;
-    s = block_sum_lane0(neg, sh);
+    s = block_sum_lane0(a.neg, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 1] = s;
-    s = block_sum_lane0(npos, sh);
+    s = block_sum_lane0(a.npos, sh);
     if (threadIdx.x == 0) w[blockIdx.x * 3 + 2] = s;
     return;
   }
@@ -590,18 +552,10 @@ __global__ void k_lossx_finalize(LossExtParams p, double *__restrict__ ws, float
     double pos = 0, neg = 0, npos = 0;
     for (int i = 0; i < LX_BLOCKS; ++i) { pos += w[i * 3]; neg += w[i * 3 + 1]; npos += w[i * 3 + 2]; }
     const double *wr = w + LX_BLOCKS * 3;
-    const double hm = (npos == 0.0 ? -neg : -(pos + neg) / npos) * (double)d.cls_weight;
-    const double num = wr[0] < 1.0 ? 1.0 : wr[0];
-    double loc = 0;
-    for (int j = 0; j < p.heads[h].n_codes; ++j) loc += (double)(float)(wr[1 + j] / num) * (double)d.code_weights[j];
-    loc *= (double)d.loc_weight;
-    losses[h * 4 + 0] = (float)hm;
-    losses[h * 4 + 1] = (float)loc;
-    losses[h * 4 + 2] = (float)(hm + loc);
-    losses[h * 4 + 3] = (float)npos;
+    sums[h] = (double)head_losses(pos, neg, npos, wr[0], wr + 1, p.heads[h].n_codes, d.code_weights, d.cls_weight, d.loc_weight,
+                                  losses + h * 4);
     w[LX_PER_HEAD - 2] = npos;
     w[LX_PER_HEAD - 1] = wr[0];
-    sums[h] = (double)(float)(hm + loc);
   }
   __syncthreads();
   if (h == 0) {
@@ -622,21 +576,9 @@ __global__ __launch_bounds__(256) void k_lossx_focal_grad(LossExtParams p, const
   const long long pix = t / hd.ld_d;
   float gval = 0.f;
   const int c = ch - hd.ch_hm;
-  if (c >= 0 && c < hd.num_class) {
-    const double npos = ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 2];
-    const float coef = -d.cls_weight * p.grad_scale / (float)(npos == 0.0 ? 1.0 : npos);
-    int inside;
-    const float q = clamped_sigmoid(hd.head[pix * hd.ld + ch], &inside);
-    const float gtv = hd.heatmap[pix * hd.num_class + c];
-    float dldp = 0.f;
-    if (gtv == 1.f) {
-      if (npos != 0.0) dldp = (1.f - q) * (1.f - q) / q - 2.f * (1.f - q) * logf(q);
-    } else if (gtv < 1.f) {
-      const float wt = (1.f - gtv) * (1.f - gtv);
-      dldp = (wt * wt) * (-(q * q) / (1.f - q) + 2.f * q * logf(1.f - q));
-    }
-    gval = inside ? coef * dldp * q * (1.f - q) : 0.f;
-  }
+  if (c >= 0 && c < hd.num_class)
+    gval = focal_grad(hd.head[pix * hd.ld + ch], hd.heatmap[pix * hd.num_class + c], ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 2],
+                      d.cls_weight, p.grad_scale);
   hd.dhead[t] = gval;
 }
 
@@ -652,8 +594,7 @@ __global__ __launch_bounds__(256) void k_lossx_reg_grad(LossExtParams p, const d
   const int cell = inds[k0];
   for (int k = 0; k < k0; ++k)
     if (mask[k] && inds[k] == cell) return;
-  const double numd = ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 1];
-  const double num = numd < 1.0 ? 1.0 : numd;
+  const double num = clamped_num(ws[(long long)blockIdx.y * LX_PER_HEAD + LX_PER_HEAD - 1]);
   const long long pix = (long long)b * d.h * d.w + cell;
   float acc[PCP_HEADLOSS_MAX_CODES];
 #pragma unroll
@@ -664,9 +605,8 @@ __global__ __launch_bounds__(256) void k_lossx_reg_grad(LossExtParams p, const d
 #pragma unroll
     for (int j = 0; j < PCP_HEADLOSS_MAX_CODES; ++j) {
       if (j >= hd.n_codes) continue;
-      const float diff = hd.head[pix * hd.ld + hd.reg_ch[j]] - tv[j];
-      const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-      if (sg != 0.f) acc[j] += sg * d.loc_weight * d.code_weights[j] * p.grad_scale / (float)num;
+      const float sg = l1_sign(hd.head[pix * hd.ld + hd.reg_ch[j]] - tv[j]);
+      if (sg != 0.f) acc[j] += l1_grad_term(sg, d.loc_weight, d.code_weights[j], p.grad_scale, num);
     }
   }
   // two codes never share a channel (checked on the host), so these are plain stores

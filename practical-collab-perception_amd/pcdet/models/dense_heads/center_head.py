@@ -242,19 +242,20 @@ class CenterHead(PackedModule):
     def generate_predicted_boxes(self, batch_size, head_bufs, pk):
         return self.finalize(self.device_postprocess(head_bufs, pk), batch_size)
 
+    @staticmethod
+    def _pred_dict(buf, names, starts, outs):
+        """the reference's pred_dict of one head: NCHW views of its branches' channels [start, start + out) inside the head buffer"""
+        view = ops.nchw_view(buf)
+        return {n: view[:, int(s):int(s) + int(o)] for n, s, o in zip(names, starts, outs)}
+
     def forward(self, data_dict):
         if self.training:
             return self._forward_train(data_dict)
         pk = self.packed()
         x = ops.as_nhwc(data_dict['spatial_features_2d'])
         x = pk['shared'].run(x)
-        head_bufs, pred_dicts = [], []
-        for entry in pk['heads']:
-            buf = self._run_head_convs(x, entry)
-            head_bufs.append(buf)
-            view = ops.nchw_view(buf)
-            pred_dicts.append({n: view[:, int(entry['offs'][i]):int(entry['offs'][i + 1])] for i, n in enumerate(entry['names'])})
-        self.forward_ret_dict['pred_dicts'] = pred_dicts
+        head_bufs = [self._run_head_convs(x, entry) for entry in pk['heads']]
+        self.forward_ret_dict['pred_dicts'] = [self._pred_dict(buf, e['names'], e['offs'], e['outs']) for buf, e in zip(head_bufs, pk['heads'])]
         if getattr(self, 'defer_finalize', False):                   # graph capture: keep the host sync outside
             data_dict['_pcp_pending_head'] = self.device_postprocess(head_bufs, pk)
             return data_dict
@@ -311,8 +312,15 @@ class CenterHead(PackedModule):
             if n_codes > lib.HEADLOSS_MAX_CODES:
                 raise ValueError('%d regression codes, the loss kernel takes at most %d' % (n_codes, lib.HEADLOSS_MAX_CODES))
 
-    def _forward_train(self, data_dict):
+    def _target_desc(self, B, H, W, num_class):
+        """lib.Target of the TARGET_ASSIGNER_CONFIG; num_class 0 for the _ext entry point (each head brings its own)"""
         from pcp_amd import lib
+        ta = self.model_cfg.TARGET_ASSIGNER_CONFIG
+        return lib.Target(B, H, W, num_class, int(ta.NUM_MAX_OBJS), float(ta.FEATURE_MAP_STRIDE), float(np.float32(self.voxel_size[0])),
+                          float(np.float32(self.voxel_size[1])), float(self.point_cloud_range[0]), float(self.point_cloud_range[1]),
+                          float(ta.GAUSSIAN_OVERLAP), int(ta.MIN_RADIUS))
+
+    def _forward_train(self, data_dict):
         from pcp_amd import train_ops as tops
         from pcp_amd.train_layers import Act
         from ..train_path import HeadTrain
@@ -331,29 +339,22 @@ class CenterHead(PackedModule):
         x = ops.as_nhwc(data_dict['spatial_features_2d'])
         if gt.dtype != torch.float32 or not gt.is_contiguous():
             gt = gt.float().contiguous()
-        ta = self.model_cfg.TARGET_ASSIGNER_CONFIG
         if ext:
-            return self._forward_train_ext(data_dict, x, gt, ta)
+            return self._forward_train_ext(data_dict, x, gt)
         buf = self._pcp_train.forward(Act(x))
         B, H, W, ld = buf.shape
         off, outs, reg, names = self._head_channels()
-        view = ops.nchw_view(buf)
-        offs = np.concatenate([[0], np.cumsum(outs)]).astype(int)
-        self.forward_ret_dict['pred_dicts'] = [{n: view[:, int(offs[i]):int(offs[i + 1])] for i, n in enumerate(names)}]
+        self.forward_ret_dict['pred_dicts'] = [self._pred_dict(buf, names, [off[n] for n in names], outs)]
         ncls = outs[names.index('hm')]
-        tdesc = lib.Target(B, H, W, ncls, int(ta.NUM_MAX_OBJS), float(ta.FEATURE_MAP_STRIDE), float(np.float32(self.voxel_size[0])),
-                           float(np.float32(self.voxel_size[1])), float(self.point_cloud_range[0]), float(self.point_cloud_range[1]),
-                           float(ta.GAUSSIAN_OVERLAP), int(ta.MIN_RADIUS))
-        heat, tb, inds, mask = tops.centerhead_targets(gt, tdesc)
+        heat, tb, inds, mask = tops.centerhead_targets(gt, self._target_desc(B, H, W, ncls))
         self.forward_ret_dict['target_dicts'] = {'heatmaps': [ops.nchw_view(heat)], 'target_boxes': [tb], 'inds': [inds.long()],
                                                  'masks': [mask.long()]}
         self._train_state = dict(buf=buf, heat=heat, tb=tb, inds=inds, mask=mask, off=off, reg=reg, ncls=ncls)
         train_tape(data_dict).append(('dense_head', self._backward_from_loss))
         return data_dict
 
-    def _forward_train_ext(self, data_dict, x, gt, ta):
+    def _forward_train_ext(self, data_dict, x, gt):
         """several heads / vel / iou (reference :168-268): head convs first (the IoU target reads them), then ONE targets launch"""
-        from pcp_amd import lib
         from pcp_amd import train_ops as tops
         from pcp_amd.train_layers import Act
         bufs = self._pcp_train.forward_heads(Act(x))
@@ -363,9 +364,7 @@ class CenterHead(PackedModule):
         heads, pred_dicts = [], []
         for idx, buf in enumerate(bufs):
             off, outs, reg, names = self._head_channels(idx)
-            offs = np.concatenate([[0], np.cumsum(outs)]).astype(int)
-            view = ops.nchw_view(buf)
-            pred_dicts.append({n: view[:, int(offs[i]):int(offs[i + 1])] for i, n in enumerate(names)})
+            pred_dicts.append(self._pred_dict(buf, names, [off[n] for n in names], outs))
             table = [0] * n_global
             for local, name in enumerate(self.class_names_each_head[idx]):
                 table[self.class_names.index(name) + 1] = local + 1
@@ -376,10 +375,7 @@ class CenterHead(PackedModule):
                 h.update(head=buf, ch_center=off['center'], ch_z=off.get('center_z', 0), ch_dim=off['dim'], ch_rot=off['rot'])
             heads.append(h)
         self.forward_ret_dict['pred_dicts'] = pred_dicts
-        tdesc = lib.Target(B, H, W, 0, int(ta.NUM_MAX_OBJS), float(ta.FEATURE_MAP_STRIDE), float(np.float32(self.voxel_size[0])),
-                           float(np.float32(self.voxel_size[1])), float(self.point_cloud_range[0]), float(self.point_cloud_range[1]),
-                           float(ta.GAUSSIAN_OVERLAP), int(ta.MIN_RADIUS))
-        targets = tops.centerhead_targets_ext(gt, tdesc, heads, with_iou=with_iou)
+        targets = tops.centerhead_targets_ext(gt, self._target_desc(B, H, W, 0), heads, with_iou=with_iou)
         self.forward_ret_dict['target_dicts'] = {'heatmaps': [ops.nchw_view(t[0]) for t in targets], 'target_boxes': [t[1] for t in targets],
                                                  'inds': [t[2].long() for t in targets], 'masks': [t[3].long() for t in targets]}
         self._train_state = dict(ext=True, bufs=bufs, heads=heads, targets=targets)
