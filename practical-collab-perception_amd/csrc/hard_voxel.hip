@@ -7,24 +7,19 @@
 //     a cell not seen before becomes voxel nvox++ unless nvox == max_voxels (then the point is skipped, later points go on)
 //     the point takes the next slot of its voxel unless the voxel already holds T points
 // so voxels are numbered by FIRST APPEARANCE and slots by input order.  No step here depends on the arrival order of an atomic:
-//   k_cells_z      (csrc/vox_cells_z.h, shared with the mean VFE) cell id per row (z range too), integer histogram, frame column validated        (the only atomics: integer adds)
-//   pcp_voxelize_cells_ready + pcp_voxelize_sort_pillar_rows (csrc/voxelize.hip, called, not changed): rows grouped by cell, every cell's
-//                  rows in ascending row index -- the first entry of a run is the cell's first point, entry j its slot-j point; a cell
-//                  of thousands of rows is ranked by a whole workgroup there
+//   k_cells_z      (csrc/vox_front.h, shared with the mean VFE) cell id per row (z range too), integer histogram, frame column validated        (the only atomics: integer adds)
+//   pcp_voxelize_cells_ready + pcp_voxelize_sort_pillar_rows (csrc/voxelize.hip, called, not changed; the sort itself is csrc/vox_front.h's):
+//                  rows grouped by cell, every cell's rows in ascending row index -- the first entry of a run is the cell's first point,
+//                  entry j its slot-j point; a cell of thousands of rows is ranked by a whole workgroup there
 //   k_hv_flags     flag "first point of its cell" per row; flags per 1024-row tile and per frame
 //   k_hv_number    exclusive prefix of the flags in row order = first-appearance rank; minus the frame's start = rank inside the frame;
 //                  kept if < max_voxels; voxel number = kept voxels of the frames in front + rank.  Writes coords, num_points, counters
+//                  (both on csrc/vox_front.h's tile-sum and tile-prefix helpers and its 1024-row tile)
 //   k_hv_gather    (after the host read M) one thread per (voxel, slot): the row of slot j < min(count, T), zeros behind
-#include "pcp_common.h"
-#include "wave_ops.h"
-#include "vox_cells_z.h"
+#include "vox_front.h"
 
 namespace {
 
-constexpr int HV_THREADS = 256;
-constexpr int HV_ITEMS = 4;
-constexpr int HV_TILE = HV_THREADS * HV_ITEMS;       // 1024 rows per workgroup
-static_assert(HV_TILE == CZ_TILE, "k_cells_z and the tile passes below walk the same 1024-row tiles");
 constexpr int HV_MAX_B = PCP_HARD_VOXEL_MAX_BATCH;   // 64: one wave scans the per-frame counts
 
 // counters (int32, PCP_HARD_VOXEL_COUNTERS of them): [0] M, [1] error word, [4 .. 4 + 64) voxels kept per frame, [68 .. 68 + 64) cells hit per frame
@@ -39,9 +34,8 @@ struct HvLayout {
 };
 inline HvLayout hv_layout(int64_t cells, int64_t n) {
   HvLayout L;
-  L.v = pcp_vox_layout(cells, n);
-  PcpCarver ws(L.v.total);
-  L.tile_sums = ws.take((size_t)((n + HV_TILE - 1) / HV_TILE + 1) * 4);
+  PcpCarver ws = pcp_behind_vox_layout(cells, n, &L.v);
+  L.tile_sums = ws.take((size_t)((n + SCAN_TILE - 1) / SCAN_TILE + 1) * 4);
   L.vox_pillar = ws.take((size_t)n * 4);
   L.dense_coords = ws.take((size_t)n * 16);
   L.total = ws.total();
@@ -59,20 +53,20 @@ __device__ __forceinline__ bool hv_is_first(long long r, long long n, const int 
   return bucket_order[cell_rs[c].y] == (int)r;
 }
 
-__global__ __launch_bounds__(HV_THREADS) void k_hv_flags(long long n, int plane, const int *__restrict__ point_cell,
+__global__ __launch_bounds__(SCAN_THREADS) void k_hv_flags(long long n, int plane, const int *__restrict__ point_cell,
                                                          const int2 *__restrict__ cell_rs, const int *__restrict__ bucket_order,
                                                          int *__restrict__ tile_sums, int *__restrict__ counters) {
   __shared__ int s_frame[HV_MAX_B];
-  __shared__ int wave_tot[HV_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int wave_tot[SCAN_THREADS / 64];
+  const int lane = threadIdx.x & 63;
   if (threadIdx.x < HV_MAX_B) s_frame[threadIdx.x] = 0;
   __syncthreads();
-  const long long base = (long long)blockIdx.x * HV_TILE;
+  const long long base = (long long)blockIdx.x * SCAN_TILE;
   int total = 0;
 #pragma unroll
-  for (int i = 0; i < HV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     int c;
-    const bool first = hv_is_first(base + i * HV_THREADS + threadIdx.x, n, point_cell, cell_rs, bucket_order, &c);
+    const bool first = hv_is_first(base + i * SCAN_THREADS + threadIdx.x, n, point_cell, cell_rs, bucket_order, &c);
     const int b = first ? c / plane : -1;
     // frames are grouped, so a wave's flagged rows share one or two frames: one LDS add per (wave, frame)
     unsigned long long todo = __ballot(first);
@@ -85,24 +79,18 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_flags(long long n, int plane,
       todo &= ~same;
     }
   }
-  if (lane == 0) wave_tot[wave] = total;         // `total` is already the wave's count (ballots)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < HV_THREADS / 64; w++) s += wave_tot[w];
-    tile_sums[blockIdx.x] = s;
-  }
+  tile_sum_store(total, wave_tot, tile_sums);         // `total` is already the wave's count (ballots)
   if (threadIdx.x < HV_MAX_B && s_frame[threadIdx.x]) atomicAdd(&counters[HV_CNT_FIRST + threadIdx.x], s_frame[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(HV_THREADS) void k_hv_number(long long n, pcp_grid_t g, int T, int max_voxels, int n_tiles,
+__global__ __launch_bounds__(SCAN_THREADS) void k_hv_number(long long n, pcp_grid_t g, int T, int max_voxels, int n_tiles,
                                                           const int *__restrict__ point_cell, const int2 *__restrict__ cell_rs,
                                                           const int *__restrict__ bucket_order, const int *__restrict__ cell_count,
                                                           const int *__restrict__ tile_sums, int *__restrict__ counters,
                                                           int *__restrict__ vox_pillar, int *__restrict__ voxel_coords,
                                                           int *__restrict__ voxel_num_points) {
   __shared__ int s_first0[HV_MAX_B], s_vox0[HV_MAX_B];      // per frame: first-appearance rank of its first cell, number of its first voxel
-  __shared__ int red[HV_THREADS / 64], lds_wave[HV_THREADS / 64];
+  __shared__ int red[SCAN_THREADS / 64], lds_wave[SCAN_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tile = blockIdx.x;
   if (wave == 0) {
@@ -124,53 +112,39 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_number(long long n, pcp_grid_
       if (lane == 63) counters[HV_CNT_M] = ik;
     }
   }
-  // flags of the tiles in front of this one
-  int pre = 0;
-  for (int i = threadIdx.x; i < tile && i < n_tiles; i += HV_THREADS) pre += tile_sums[i];
-  pre = wave_sum(pre);
-  if (lane == 0) red[wave] = pre;
+  tiles_in_front(tile_sums, min(tile, n_tiles), red);
   // exclusive scan of this tile's flags; a thread's items are CONSECUTIVE rows
-  const long long base = (long long)tile * HV_TILE + (long long)threadIdx.x * HV_ITEMS;
-  int cell[HV_ITEMS], excl[HV_ITEMS], local = 0;
+  const long long base = (long long)tile * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
+  int cell[SCAN_ITEMS], excl[SCAN_ITEMS], local = 0;
 #pragma unroll
-  for (int i = 0; i < HV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     const bool first = hv_is_first(base + i, n, point_cell, cell_rs, bucket_order, &cell[i]);
     if (!first) cell[i] = -1;
     excl[i] = local;
     local += first ? 1 : 0;
   }
-  const int incl = wave_incl_scan(local, lane);
-  if (lane == 63) lds_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - local;
+  const int before = tile_prefix_before<true>(local, red, lds_wave);
 #pragma unroll
-  for (int w = 0; w < HV_THREADS / 64; w++) {
-    before += red[w];
-    if (w < wave) before += lds_wave[w];
-  }
-  const int plane = g.nx * g.ny;
-#pragma unroll
-  for (int i = 0; i < HV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     const int c = cell[i];
     if (c < 0) continue;
-    const int b = c / plane, rem = c - b * plane;
-    const int in_frame = before + excl[i] - s_first0[b];
+    const CellCoords at = cell_coords(c, g);
+    const int in_frame = before + excl[i] - s_first0[at.b];
     if (in_frame >= max_voxels) continue;                        // the frame is full: this cell never becomes a voxel
-    const int v = s_vox0[b] + in_frame;
-    const int cx = rem / g.ny, cy = rem - cx * g.ny;
+    const int v = s_vox0[at.b] + in_frame;
     vox_pillar[v] = cell_rs[c].x;
-    *reinterpret_cast<int4 *>(voxel_coords + 4LL * v) = make_int4(b, 0, cy, cx);       // [b, z, y, x]
+    *reinterpret_cast<int4 *>(voxel_coords + 4LL * v) = make_int4(at.b, 0, at.cy, at.cx);       // [b, z, y, x]
     voxel_num_points[v] = min(cell_count[c], T);
   }
 }
 
 // one thread per (voxel, slot): C floats
 template <bool VEC4>
-__global__ __launch_bounds__(HV_THREADS) void k_hv_gather(const float *__restrict__ points, int stride, int C, int T, long long slots,
+__global__ __launch_bounds__(SCAN_THREADS) void k_hv_gather(const float *__restrict__ points, int stride, int C, int T, long long slots,
                                                           const int *__restrict__ vox_pillar, const int *__restrict__ pillar_start,
                                                           const int *__restrict__ bucket_order, const int *__restrict__ voxel_num_points,
                                                           float *__restrict__ voxels) {
-  const long long s = (long long)blockIdx.x * HV_THREADS + threadIdx.x;
+  const long long s = (long long)blockIdx.x * SCAN_THREADS + threadIdx.x;
   if (s >= slots) return;
   const long long v = s / T;
   const int j = (int)(s - v * T);
@@ -185,8 +159,9 @@ __global__ __launch_bounds__(HV_THREADS) void k_hv_gather(const float *__restric
   }
 }
 
+// the checks behind pcp_front_args' PCP_ERR_ARG ones
 inline bool hv_args_ok(const pcp_grid_t *grid, int64_t n, int32_t row_stride, int32_t nz, int32_t T, int64_t max_voxels) {
-  if (!grid || n < 0 || row_stride < 4 || grid->nx <= 0 || grid->ny <= 0 || grid->batch_size <= 0) return false;
+  if (row_stride < 4) return false;
   if (nz != 1 || T < 1 || T > PCP_HARD_VOXEL_MAX_T || max_voxels < 1 || grid->batch_size > HV_MAX_B) return false;
   return true;
 }
@@ -201,11 +176,12 @@ extern "C" size_t pcp_hard_voxelize_workspace_bytes(const pcp_grid_t *grid, int6
 extern "C" int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_stride, const pcp_grid_t *grid, int32_t nz, int32_t max_points,
                                  int64_t max_voxels, void *workspace, size_t workspace_bytes, int32_t *voxel_coords,
                                  int32_t *voxel_num_points, int32_t *counters, void *stream_) {
-  if (!hv_args_ok(grid, n, row_stride, nz, max_points, max_voxels)) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !hv_args_ok(grid, n, row_stride, nz, max_points, max_voxels)) return PCP_ERR_ARG;
   if (!workspace || !voxel_coords || !voxel_num_points || !counters || (n > 0 && !points)) return PCP_ERR_ARG;
   if ((((uintptr_t)voxel_coords) & 15) || (((uintptr_t)counters) & 15)) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   const int64_t n_alloc = n > 0 ? n : 1;
   const HvLayout L = hv_layout(cells, n_alloc);
   if (workspace_bytes < L.total) return PCP_ERR_WORKSPACE;
@@ -217,13 +193,13 @@ extern "C" int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_str
   const int *bucket_order = (const int *)(ws + L.v.bucket_order);
   const int2 *cell_rs = (const int2 *)(ws + L.v.cell_rs);
   int *tile_sums = (int *)(ws + L.tile_sums);
-  const int n_tiles = (int)((n + HV_TILE - 1) / HV_TILE);
+  const int n_tiles = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
   const int mv = (int)(max_voxels > 0x7fffffffLL ? 0x7fffffffLL : max_voxels);
 
   if (pcp_zero_async(cell_count, (size_t)cells * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (pcp_zero_async(counters, (size_t)PCP_HARD_VOXEL_COUNTERS * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(k_cells_z<false>, dim3(n_tiles), dim3(CZ_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
+    hipLaunchKernelGGL(k_cells_z<false>, dim3(n_tiles), dim3(SCAN_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
                        point_cell, point_rank, (int *)nullptr, counters + HV_CNT_ERR);
     PCP_CHECK_LAUNCH();
   }
@@ -233,11 +209,11 @@ extern "C" int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_str
   st = pcp_voxelize_sort_pillar_rows(grid, workspace, n, stream_);
   if (st != PCP_OK) return st;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(k_hv_flags, dim3(n_tiles), dim3(HV_THREADS), 0, stream, (long long)n, grid->nx * grid->ny, point_cell, cell_rs, bucket_order,
+    hipLaunchKernelGGL(k_hv_flags, dim3(n_tiles), dim3(SCAN_THREADS), 0, stream, (long long)n, grid->nx * grid->ny, point_cell, cell_rs, bucket_order,
                        tile_sums, counters);
     PCP_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_hv_number, dim3(n_tiles > 0 ? n_tiles : 1), dim3(HV_THREADS), 0, stream, (long long)n, *grid, (int)max_points, mv, n_tiles,
+  hipLaunchKernelGGL(k_hv_number, dim3(n_tiles > 0 ? n_tiles : 1), dim3(SCAN_THREADS), 0, stream, (long long)n, *grid, (int)max_points, mv, n_tiles,
                      point_cell, cell_rs, bucket_order, cell_count, tile_sums, counters, (int *)(ws + L.vox_pillar), voxel_coords,
                      voxel_num_points);
   PCP_CHECK_LAUNCH();
@@ -247,22 +223,23 @@ extern "C" int pcp_hard_voxelize(const float *points, int64_t n, int32_t row_str
 extern "C" int pcp_hard_voxelize_gather(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid,
                                         int32_t max_points, const void *workspace, size_t workspace_bytes, int64_t num_voxels,
                                         const int32_t *voxel_num_points, float *voxels, void *stream_) {
-  if (!hv_args_ok(grid, n, row_stride, 1, max_points, 1)) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !hv_args_ok(grid, n, row_stride, 1, max_points, 1)) return PCP_ERR_ARG;
   if (num_features < PCP_HARD_VOXEL_MIN_FEATURES || num_features > PCP_HARD_VOXEL_MAX_FEATURES || row_stride < 1 + num_features) return PCP_ERR_ARG;
   if (num_voxels < 0 || num_voxels > n) return PCP_ERR_ARG;
   if (num_voxels == 0) return PCP_OK;
   if (!points || !workspace || !voxel_num_points || !voxels) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   const HvLayout L = hv_layout(cells, n);
   if (workspace_bytes < L.total) return PCP_ERR_WORKSPACE;
   const char *ws = (const char *)workspace;
   const long long slots = (long long)num_voxels * max_points;
-  const long long blocks = (slots + HV_THREADS - 1) / HV_THREADS;
+  const long long blocks = (slots + SCAN_THREADS - 1) / SCAN_THREADS;
   if (blocks >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
   const bool vec4 = (num_features % 4 == 0) && ((((uintptr_t)voxels) & 15) == 0);
 #define PCP_HV_GATHER(V_)                                                                                                                     \
-  hipLaunchKernelGGL(k_hv_gather<V_>, dim3((unsigned)blocks), dim3(HV_THREADS), 0, (hipStream_t)stream_, points, (int)row_stride,             \
+  hipLaunchKernelGGL(k_hv_gather<V_>, dim3((unsigned)blocks), dim3(SCAN_THREADS), 0, (hipStream_t)stream_, points, (int)row_stride,             \
                      (int)num_features, (int)max_points, slots, (const int *)(ws + L.vox_pillar), (const int *)(ws + L.v.pillar_start),      \
                      (const int *)(ws + L.v.bucket_order), voxel_num_points, voxels)
   if (vec4) PCP_HV_GATHER(true); else PCP_HV_GATHER(false);

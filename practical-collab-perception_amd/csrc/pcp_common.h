@@ -99,6 +99,22 @@ static inline VoxLayout pcp_vox_layout(int64_t cells, int64_t n) {
   return L;
 }
 
+// The argument front of every entry point that takes (grid, n rows): PCP_ERR_ARG for no grid, a negative row count or an extent that is not
+// positive; PCP_ERR_UNSUPPORTED for 2^31 cells or rows and more (*cells is set by then); else PCP_OK.  A caller returns the first at once and
+// the second only behind its own argument checks, so that a call which fails both kinds of check still reports PCP_ERR_ARG.
+static inline int pcp_front_args(const pcp_grid_t *grid, int64_t n, int64_t *cells) {
+  if (!grid || n < 0 || grid->nx <= 0 || grid->ny <= 0 || grid->batch_size <= 0) return PCP_ERR_ARG;
+  *cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
+  return (*cells >= (1LL << 31) || n >= (1LL << 31)) ? PCP_ERR_UNSUPPORTED : PCP_OK;
+}
+
+// A front end's workspace is the pillariser's in front (pcp_voxelize_cells_ready runs on it as it is) and its own fields behind: fills *v
+// and returns the carver that stands behind it.
+static inline PcpCarver pcp_behind_vox_layout(int64_t cells, int64_t n, VoxLayout *v) {
+  *v = pcp_vox_layout(cells, n);
+  return PcpCarver(v->total);
+}
+
 // ---- round 5: rows in pillar order + wave tiles for pcp_pfn_rows (csrc/pfn_rows.hip) ---------------------------------------------------
 // The first VoxLayout fields keep their offsets, so a rows workspace is also a pcp_voxelize workspace (cell -> rank table for the sparse
 // first layer, bucket order for the training kernels).
@@ -120,8 +136,7 @@ struct RowsLayout {
 };
 static inline RowsLayout pcp_rows_layout(int64_t cells, int64_t n, int num_raw) {
   RowsLayout R;
-  R.v = pcp_vox_layout(cells, n);
-  PcpCarver ws(R.v.total);
+  PcpCarver ws = pcp_behind_vox_layout(cells, n, &R.v);
   R.srows = ws.take((size_t)n * pcp_rows_stride(num_raw) * 4);
   R.tile_desc = ws.take((size_t)(n / PCP_PFN_TILE + 2) * 8);
   R.crowd_list = ws.take((size_t)(n / PCP_PFN_CROWD_MIN + 2) * 16);

@@ -6,10 +6,12 @@
 //
 // Mean VFE.  The merged id b*nx*ny*nz + cx*ny*nz + cy*nz + cz has the pillariser's id b*nx*ny + cx*ny + cy as its prefix, so a voxel list in
 // torch.unique order is every pillar's rows split by cz:
-//   k_cells_z<true>   (csrc/vox_cells_z.h, the hard voxeliser's first pass with cz kept) cell id and cz per row, integer histogram
+//   k_cells_z<true>   (csrc/vox_front.h, the hard voxeliser's first pass with cz kept) cell id and cz per row, integer histogram
 //   pcp_voxelize_cells_ready (csrc/voxelize.hip, called, not changed): rows grouped by pillar in ascending cell id
-//   k_mv_sort_short / k_mv_sort_long   a pillar's rows ranked by (cz, input row); a run of more than PCP_LONG_PILLAR rows by a whole workgroup
-//   k_mv_flags / k_mv_number           a slot opens a voxel when its (cell, cz) differs from the slot in front; prefix = voxel number
+//   k_sort_runs / k_sort_long_runs <CzRowKey>   (csrc/vox_front.h, the pillariser's sort with another key) a pillar's rows ranked by (cz, input
+//                     row); a run of more than PCP_LONG_PILLAR rows by a whole workgroup
+//   k_mv_flags / k_mv_number           a slot opens a voxel when its (cell, cz) differs from the slot in front; prefix = voxel number (on
+//                     csrc/vox_front.h's tile-sum and tile-prefix helpers, as k_sp_prefix below)
 //   k_mv_mean         (after the host read M) a wave per voxel: four lane groups walk rows j = g, g + 4, ... in slot order, (g0 + g1) + (g2 + g3),
 //                     IEEE divide by the count.  No float atomics: the sum is a function of the voxel's rows in input order alone.
 //
@@ -22,17 +24,10 @@
 // present neighbour rows straight into v_mfma_f32_16x16x4_f32 A fragments (absent rows are zero), takes the offset's weight fragments from
 // L2 and skips, wave-uniformly, every offset none of its 16 rows has.  Waves share nothing, so there is no LDS stage and no barrier; a row's
 // bits depend on its own neighbour list only.  No scatter, no float atomics.
-#include "pcp_common.h"
-#include "wave_ops.h"
-#include "vox_cells_z.h"
+#include "vox_front.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int MV_THREADS = 256;
-constexpr int MV_ITEMS = 4;
-constexpr int MV_TILE = MV_THREADS * MV_ITEMS;       // 1024 rows / slots / words per workgroup
-static_assert(MV_TILE == CZ_TILE, "k_cells_z and the tile passes below walk the same 1024-row tiles");
 constexpr int MV_MAX_B = PCP_MEAN_VFE_MAX_BATCH;
 constexpr int MV_CNT_M = 0, MV_CNT_ERR = 1, MV_CNT_KEPT = 2;
 
@@ -46,77 +41,13 @@ struct MvLayout {
 };
 inline MvLayout mv_layout(int64_t cells, int64_t n) {
   MvLayout L;
-  L.v = pcp_vox_layout(cells, n);
-  PcpCarver ws(L.v.total);
+  PcpCarver ws = pcp_behind_vox_layout(cells, n, &L.v);
   L.point_cz = ws.take((size_t)n * 4);
-  L.tile_sums = ws.take((size_t)((n + MV_TILE - 1) / MV_TILE + 1) * 4);
+  L.tile_sums = ws.take((size_t)((n + SCAN_TILE - 1) / SCAN_TILE + 1) * 4);
   L.vox_start = ws.take((size_t)(n + 1) * 4);
   L.dense_coords = ws.take((size_t)n * 16);
   L.total = ws.total();
   return L;
-}
-
-__device__ __forceinline__ u64 mv_key(int row, const int *__restrict__ point_cz) { return ((u64)(unsigned)point_cz[row] << 32) | (unsigned)row; }
-
-// short runs: one thread each, insertion sort by (cz, row)
-__global__ __launch_bounds__(256) void k_mv_sort_short(const int *__restrict__ pillar_start, const int *__restrict__ counters,
-                                                       int *__restrict__ bucket_order, const int *__restrict__ point_cz) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= counters[0]) return;
-  const int s0 = pillar_start[p], s1 = pillar_start[p + 1];
-  if (s1 - s0 > PCP_LONG_PILLAR) return;
-  for (int i = s0 + 1; i < s1; ++i) {
-    const int v = bucket_order[i];
-    const u64 kv = mv_key(v, point_cz);
-    int j = i - 1;
-    while (j >= s0 && mv_key(bucket_order[j], point_cz) > kv) {
-      bucket_order[j + 1] = bucket_order[j];
-      --j;
-    }
-    bucket_order[j + 1] = v;
-  }
-}
-
-// long runs (the pillariser lists them): a workgroup per run; an element's place is the number of smaller keys (the keys are distinct),
-// counted against LDS tiles of the run; the sorted run is staged in the idle point_rank array and copied back
-constexpr int MV_SORT_TILE = 2048, MV_SORT_EPT = 4;
-__global__ __launch_bounds__(256) void k_mv_sort_long(const int *__restrict__ pillar_start, int *__restrict__ bucket_order, int *__restrict__ scratch,
-                                                      const int *__restrict__ long_list, const int *__restrict__ counters,
-                                                      const int *__restrict__ point_cz) {
-  __shared__ u64 tile[MV_SORT_TILE];
-  const int tid = threadIdx.x;
-  const int nl = counters[6];
-  for (int li = blockIdx.x; li < nl; li += gridDim.x) {
-    const int q = long_list[li];
-    const int s0 = pillar_start[q], cnt = pillar_start[q + 1] - s0;
-    for (int base = 0; base < cnt; base += 256 * MV_SORT_EPT) {
-      u64 v[MV_SORT_EPT];
-      int rank[MV_SORT_EPT];
-#pragma unroll
-      for (int u = 0; u < MV_SORT_EPT; ++u) {
-        const int e = base + u * 256 + tid;
-        v[u] = e < cnt ? mv_key(bucket_order[s0 + e], point_cz) : ~0ULL;
-        rank[u] = 0;
-      }
-      for (int tb = 0; tb < cnt; tb += MV_SORT_TILE) {
-        const int tn = min(MV_SORT_TILE, cnt - tb);
-        __syncthreads();
-        for (int j = tid; j < tn; j += 256) tile[j] = mv_key(bucket_order[s0 + tb + j], point_cz);
-        __syncthreads();
-        for (int j = 0; j < tn; ++j) {
-          const u64 w = tile[j];                                    // broadcast read
-#pragma unroll
-          for (int u = 0; u < MV_SORT_EPT; ++u) rank[u] += w < v[u] ? 1 : 0;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < MV_SORT_EPT; ++u)
-        if (base + u * 256 + tid < cnt) scratch[s0 + rank[u]] = (int)(unsigned)(v[u] & 0xffffffffULL);
-    }
-    __syncthreads();
-    for (int j = tid; j < cnt; j += 256) bucket_order[s0 + j] = scratch[s0 + j];
-    __syncthreads();
-  }
 }
 
 // does slot s open a voxel?  (cell, cz) differs from the slot in front
@@ -128,69 +59,47 @@ __device__ __forceinline__ bool mv_opens(long long s, int kept, const int *__res
   return point_cell[r] != point_cell[rp] || point_cz[r] != point_cz[rp];
 }
 
-__global__ __launch_bounds__(MV_THREADS) void k_mv_flags(const int *__restrict__ counters_ws, const int *__restrict__ order,
+__global__ __launch_bounds__(SCAN_THREADS) void k_mv_flags(const int *__restrict__ counters_ws, const int *__restrict__ order,
                                                          const int *__restrict__ point_cell, const int *__restrict__ point_cz,
                                                          int *__restrict__ tile_sums) {
-  __shared__ int wave_tot[MV_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int wave_tot[SCAN_THREADS / 64];
   const int kept = counters_ws[1];
-  const long long base = (long long)blockIdx.x * MV_TILE + (long long)threadIdx.x * MV_ITEMS;
+  const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int total = 0;
 #pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++) total += mv_opens(base + i, kept, order, point_cell, point_cz) ? 1 : 0;
+  for (int i = 0; i < SCAN_ITEMS; i++) total += mv_opens(base + i, kept, order, point_cell, point_cz) ? 1 : 0;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
-  if (lane == 0) wave_tot[wave] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < MV_THREADS / 64; w++) s += wave_tot[w];
-    tile_sums[blockIdx.x] = s;
-  }
+  tile_sum_store(total, wave_tot, tile_sums);
 }
 
-__global__ __launch_bounds__(MV_THREADS) void k_mv_number(pcp_grid_t g, const int *__restrict__ counters_ws, const int *__restrict__ order,
+__global__ __launch_bounds__(SCAN_THREADS) void k_mv_number(pcp_grid_t g, const int *__restrict__ counters_ws, const int *__restrict__ order,
                                                           const int *__restrict__ point_cell, const int *__restrict__ point_cz,
                                                           const int *__restrict__ tile_sums, int *__restrict__ vox_start,
                                                           int *__restrict__ voxel_coords, int *__restrict__ counters) {
-  __shared__ int red[MV_THREADS / 64], lds_wave[MV_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int red[SCAN_THREADS / 64], lds_wave[SCAN_THREADS / 64];
   const int tile = blockIdx.x;
   const int kept = counters_ws[1];
-  int pre = 0;
-  for (int i = threadIdx.x; i < tile; i += MV_THREADS) pre += tile_sums[i];
-  pre = wave_sum(pre);
-  if (lane == 0) red[wave] = pre;
-  const long long base = (long long)tile * MV_TILE + (long long)threadIdx.x * MV_ITEMS;
-  bool open[MV_ITEMS];
-  int excl[MV_ITEMS], local = 0;
+  tiles_in_front(tile_sums, tile, red);
+  const long long base = (long long)tile * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
+  bool open[SCAN_ITEMS];
+  int excl[SCAN_ITEMS], local = 0;
 #pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     open[i] = mv_opens(base + i, kept, order, point_cell, point_cz);
     excl[i] = local;
     local += open[i] ? 1 : 0;
   }
-  const int incl = wave_incl_scan(local, lane);
-  if (lane == 63) lds_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - local;
+  const int before = tile_prefix_before<true>(local, red, lds_wave);
 #pragma unroll
-  for (int w = 0; w < MV_THREADS / 64; w++) {
-    before += red[w];
-    if (w < wave) before += lds_wave[w];
-  }
-  const int plane = g.nx * g.ny;
-#pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     const long long s = base + i;
     if (open[i]) {
       const int v = before + excl[i];
       const int r = order[s];
-      const int c = point_cell[r];
-      const int b = c / plane, rem = c - b * plane;
-      const int cx = rem / g.ny, cy = rem - cx * g.ny;
+      const CellCoords at = cell_coords(point_cell[r], g);
       vox_start[v] = (int)s;
-      *reinterpret_cast<int4 *>(voxel_coords + 4LL * v) = make_int4(b, point_cz[r], cy, cx);       // [b, z, y, x]
+      *reinterpret_cast<int4 *>(voxel_coords + 4LL * v) = make_int4(at.b, point_cz[r], at.cy, at.cx);       // [b, z, y, x]
     }
     if (s == (long long)kept - 1) {
       const int M = before + excl[i] + (open[i] ? 1 : 0);
@@ -218,8 +127,9 @@ __global__ __launch_bounds__(256) void k_mv_mean(const float *__restrict__ point
   if (grp == 0 && col < C) voxel_features[v * C + col] = __fdiv_rn(acc, (float)n);
 }
 
+// the checks behind pcp_front_args' PCP_ERR_ARG ones
 inline bool mv_args_ok(const pcp_grid_t *grid, int64_t n, int32_t row_stride, int32_t nz) {
-  if (!grid || n < 0 || row_stride < 4 || grid->nx <= 0 || grid->ny <= 0 || grid->batch_size <= 0) return false;
+  if (row_stride < 4) return false;
   if (nz < 1 || nz > PCP_MEAN_VFE_MAX_NZ || grid->batch_size > MV_MAX_B) return false;
   return true;
 }
@@ -233,11 +143,12 @@ extern "C" size_t pcp_mean_vfe_workspace_bytes(const pcp_grid_t *grid, int64_t m
 
 extern "C" int pcp_mean_vfe(const float *points, int64_t n, int32_t row_stride, const pcp_grid_t *grid, int32_t nz, void *workspace,
                             size_t workspace_bytes, int32_t *voxel_coords, int32_t *counters, void *stream_) {
-  if (!mv_args_ok(grid, n, row_stride, nz)) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !mv_args_ok(grid, n, row_stride, nz)) return PCP_ERR_ARG;
   if (!workspace || !voxel_coords || !counters || (n > 0 && !points)) return PCP_ERR_ARG;
   if ((((uintptr_t)voxel_coords) & 15) || (((uintptr_t)counters) & 15)) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   const int64_t n_alloc = n > 0 ? n : 1;
   const MvLayout L = mv_layout(cells, n_alloc);
   if (workspace_bytes < L.total) return PCP_ERR_WORKSPACE;
@@ -248,32 +159,26 @@ extern "C" int pcp_mean_vfe(const float *points, int64_t n, int32_t row_stride, 
   int *point_rank = (int *)(ws + L.v.point_rank);
   int *point_cz = (int *)(ws + L.point_cz);
   int *bucket_order = (int *)(ws + L.v.bucket_order);
-  const int *pillar_start = (const int *)(ws + L.v.pillar_start);
   const int *counters_ws = (const int *)(ws + L.v.counters);
   int *tile_sums = (int *)(ws + L.tile_sums);
-  const int n_tiles = (int)((n + MV_TILE - 1) / MV_TILE);
+  const int n_tiles = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
 
   if (pcp_zero_async(cell_count, (size_t)cells * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (pcp_zero_async(counters, (size_t)PCP_MEAN_VFE_COUNTERS * 4, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(k_cells_z<true>, dim3(n_tiles), dim3(CZ_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
+    hipLaunchKernelGGL(k_cells_z<true>, dim3(n_tiles), dim3(SCAN_THREADS), 0, stream, points, (long long)n, (int)row_stride, *grid, (int)nz, cell_count,
                        point_cell, point_rank, point_cz, counters + MV_CNT_ERR);
     PCP_CHECK_LAUNCH();
   }
   int st = pcp_voxelize_cells_ready(points, n, row_stride, grid, workspace, L.v.total, (int32_t *)(ws + L.dense_coords), nullptr, nullptr, stream_);
   if (st != PCP_OK) return st;
   if (n > 0) {
-    const int64_t max_pillars = n < cells ? n : cells;
-    hipLaunchKernelGGL(k_mv_sort_short, dim3((unsigned)((max_pillars + 255) / 256)), dim3(256), 0, stream, pillar_start, counters_ws, bucket_order,
-                       point_cz);
-    PCP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mv_sort_long, dim3(1024), dim3(256), 0, stream, pillar_start, bucket_order, point_rank, (const int *)(ws + L.v.long_list),
-                       counters_ws, point_cz);
-    PCP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mv_flags, dim3(n_tiles), dim3(MV_THREADS), 0, stream, counters_ws, bucket_order, point_cell, point_cz, tile_sums);
+    st = sort_pillar_runs<CzRowKey>(ws, L.v, cells, n, stream, (const int *)point_cz);
+    if (st != PCP_OK) return st;
+    hipLaunchKernelGGL(k_mv_flags, dim3(n_tiles), dim3(SCAN_THREADS), 0, stream, counters_ws, bucket_order, point_cell, point_cz, tile_sums);
     PCP_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_mv_number, dim3(n_tiles > 0 ? n_tiles : 1), dim3(MV_THREADS), 0, stream, *grid, counters_ws, bucket_order, point_cell, point_cz,
+  hipLaunchKernelGGL(k_mv_number, dim3(n_tiles > 0 ? n_tiles : 1), dim3(SCAN_THREADS), 0, stream, *grid, counters_ws, bucket_order, point_cell, point_cz,
                      tile_sums, (int *)(ws + L.vox_start), voxel_coords, counters);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
@@ -281,13 +186,14 @@ extern "C" int pcp_mean_vfe(const float *points, int64_t n, int32_t row_stride, 
 
 extern "C" int pcp_mean_vfe_features(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
                                      const void *workspace, size_t workspace_bytes, int64_t num_voxels, float *voxel_features, void *stream_) {
-  if (!mv_args_ok(grid, n, row_stride, nz)) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !mv_args_ok(grid, n, row_stride, nz)) return PCP_ERR_ARG;
   if (num_features < PCP_MEAN_VFE_MIN_FEATURES || num_features > PCP_MEAN_VFE_MAX_FEATURES || row_stride < 1 + num_features) return PCP_ERR_ARG;
   if (num_voxels < 0 || num_voxels > n) return PCP_ERR_ARG;
   if (num_voxels == 0) return PCP_OK;
   if (!points || !workspace || !voxel_features) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   const MvLayout L = mv_layout(cells, n);
   if (workspace_bytes < L.total) return PCP_ERR_WORKSPACE;
   const char *ws = (const char *)workspace;
@@ -313,7 +219,7 @@ inline bool sp_shape_ok(const SpShape &s) {
 inline long long sp_words(const SpShape &s) { return ((long long)s.B * s.D * s.H * s.W + 63) / 64; }
 inline size_t sp_table_bytes(const SpShape &s) {
   const long long nw = sp_words(s);
-  const long long nt = (nw + MV_TILE - 1) / MV_TILE;
+  const long long nt = (nw + SCAN_TILE - 1) / SCAN_TILE;
   PcpCarver ws;                                                     // the fields of sp_table below
   ws.take((size_t)nw * 8);
   ws.take((size_t)(nw + 1) * 4);
@@ -323,7 +229,7 @@ inline size_t sp_table_bytes(const SpShape &s) {
 inline SpTable sp_table(void *mem, const SpShape &s) {
   SpTable t;
   t.words = sp_words(s);
-  t.n_tiles = (int)((t.words + MV_TILE - 1) / MV_TILE);
+  t.n_tiles = (int)((t.words + SCAN_TILE - 1) / SCAN_TILE);
   char *p = (char *)mem;
   PcpCarver ws;
   t.bits = (u64 *)(p + ws.take((size_t)t.words * 8));
@@ -390,6 +296,7 @@ __global__ __launch_bounds__(256) void k_sp_mark_strided(const int *__restrict__
   }
 }
 
+// kept beside vox_front.h's tile_sum_store: that one has a barrier fewer, which changes k_sp_tile_sums' code
 __device__ __forceinline__ int sp_block_sum(int v, int *lds4) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -400,25 +307,25 @@ __device__ __forceinline__ int sp_block_sum(int v, int *lds4) {
   return lds4[0] + lds4[1] + lds4[2] + lds4[3];
 }
 
-__global__ __launch_bounds__(MV_THREADS) void k_sp_tile_sums(const u64 *__restrict__ bits, long long words, int *__restrict__ tile_sums) {
+__global__ __launch_bounds__(SCAN_THREADS) void k_sp_tile_sums(const u64 *__restrict__ bits, long long words, int *__restrict__ tile_sums) {
   __shared__ int lds4[4];
-  const long long base = (long long)blockIdx.x * MV_TILE + (long long)threadIdx.x * MV_ITEMS;
+  const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
   int t = 0;
 #pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++)
+  for (int i = 0; i < SCAN_ITEMS; i++)
     if (base + i < words) t += __popcll(bits[base + i]);
   const int s = sp_block_sum(t, lds4);
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = s;
 }
 
 // one workgroup: tile_sums becomes its exclusive prefix, the total goes to tile_sums[n_tiles] and counters[0]
-__global__ __launch_bounds__(MV_THREADS) void k_sp_scan_tiles(int *__restrict__ tile_sums, int n_tiles, int *__restrict__ counters) {
-  __shared__ int lds_wave[MV_THREADS / 64];
+__global__ __launch_bounds__(SCAN_THREADS) void k_sp_scan_tiles(int *__restrict__ tile_sums, int n_tiles, int *__restrict__ counters) {
+  __shared__ int lds_wave[SCAN_THREADS / 64];
   __shared__ int carry_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) carry_s = 0;
   __syncthreads();
-  for (int base = 0; base < n_tiles; base += MV_THREADS) {
+  for (int base = 0; base < n_tiles; base += SCAN_THREADS) {
     const int i = base + threadIdx.x;
     const int v = i < n_tiles ? tile_sums[i] : 0;
     int incl = v;
@@ -432,7 +339,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_sp_scan_tiles(int *__restrict__ 
     int before = carry_s + incl - v;
     int total = 0;
 #pragma unroll
-    for (int w = 0; w < MV_THREADS / 64; w++) {
+    for (int w = 0; w < SCAN_THREADS / 64; w++) {
       if (w < wave) before += lds_wave[w];
       total += lds_wave[w];
     }
@@ -447,26 +354,19 @@ __global__ __launch_bounds__(MV_THREADS) void k_sp_scan_tiles(int *__restrict__ 
   }
 }
 
-__global__ __launch_bounds__(MV_THREADS) void k_sp_prefix(const u64 *__restrict__ bits, long long words, const int *__restrict__ tile_sums,
+__global__ __launch_bounds__(SCAN_THREADS) void k_sp_prefix(const u64 *__restrict__ bits, long long words, const int *__restrict__ tile_sums,
                                                           int *__restrict__ prefix) {
-  __shared__ int lds_wave[MV_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long base = (long long)blockIdx.x * MV_TILE + (long long)threadIdx.x * MV_ITEMS;
-  int excl[MV_ITEMS], local = 0;
+  __shared__ int lds_wave[SCAN_THREADS / 64];
+  const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
+  int excl[SCAN_ITEMS], local = 0;
 #pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++) {
+  for (int i = 0; i < SCAN_ITEMS; i++) {
     excl[i] = local;
     if (base + i < words) local += __popcll(bits[base + i]);
   }
-  const int incl = wave_incl_scan(local, lane);
-  if (lane == 63) lds_wave[wave] = incl;
-  __syncthreads();
-  int before = tile_sums[blockIdx.x] + incl - local;
+  const int before = tile_sums[blockIdx.x] + tile_prefix_before<false>(local, nullptr, lds_wave);     // tile_sums: k_sp_scan_tiles' prefix already
 #pragma unroll
-  for (int w = 0; w < MV_THREADS / 64; w++)
-    if (w < wave) before += lds_wave[w];
-#pragma unroll
-  for (int i = 0; i < MV_ITEMS; i++)
+  for (int i = 0; i < SCAN_ITEMS; i++)
     if (base + i < words) prefix[base + i] = before + excl[i];
 }
 
@@ -532,11 +432,11 @@ __global__ __launch_bounds__(256) void k_sp_strided_nbr(const int *__restrict__ 
 
 // bits are set; tile sums, their scan (total -> counters[0]) and the per-word prefix
 int sp_finish_table(const SpTable &t, int *counters, hipStream_t stream) {
-  hipLaunchKernelGGL(k_sp_tile_sums, dim3(t.n_tiles), dim3(MV_THREADS), 0, stream, (const u64 *)t.bits, t.words, t.tile_sums);
+  hipLaunchKernelGGL(k_sp_tile_sums, dim3(t.n_tiles), dim3(SCAN_THREADS), 0, stream, (const u64 *)t.bits, t.words, t.tile_sums);
   PCP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_sp_scan_tiles, dim3(1), dim3(MV_THREADS), 0, stream, t.tile_sums, t.n_tiles, counters);
+  hipLaunchKernelGGL(k_sp_scan_tiles, dim3(1), dim3(SCAN_THREADS), 0, stream, t.tile_sums, t.n_tiles, counters);
   PCP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_sp_prefix, dim3(t.n_tiles), dim3(MV_THREADS), 0, stream, (const u64 *)t.bits, t.words, (const int *)t.tile_sums, t.prefix);
+  hipLaunchKernelGGL(k_sp_prefix, dim3(t.n_tiles), dim3(SCAN_THREADS), 0, stream, (const u64 *)t.bits, t.words, (const int *)t.tile_sums, t.prefix);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }

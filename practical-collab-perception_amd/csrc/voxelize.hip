@@ -9,31 +9,9 @@
 // HBM traffic per call: points read twice (n * row_stride * 4 B, second pass only column 0..2 -> same lines),
 // 4 dense int32 tables of B*nx*ny (1 MiB each at 512x512), and O(n) int32 side arrays.
 #include <stdlib.h>
-#include "pcp_common.h"
-#include "wave_ops.h"
+#include "vox_front.h"
 
 namespace {
-
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;   // 1024 elements per block
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int point_to_cell(const float *row, const pcp_grid_t g) {
-  // column 0 = batch index, 1 = x, 2 = y
-  float fb = row[0];
-  float x = row[1], y = row[2];
-  float cx = floorf(__fdiv_rn(__fsub_rn(x, g.min_x), g.voxel_x));
-  float cy = floorf(__fdiv_rn(__fsub_rn(y, g.min_y), g.voxel_y));
-  // float comparisons: NaN / inf / out-of-range all fail (torch's (coords >= 0) & (coords < grid) on the int32 cast
-  // gives the same verdict for every finite in-int-range value)
-  bool ok = (cx >= 0.0f) && (cx < (float)g.nx) && (cy >= 0.0f) && (cy < (float)g.ny) && (fb >= 0.0f) &&
-            (fb < (float)g.batch_size);
-  if (!ok) return -1;
-  int b = (int)fb;
-  return b * (g.nx * g.ny) + (int)cx * g.ny + (int)cy;
-}
 
 // exclusive block scan of one value per (thread, item); returns block total through *total (all threads)
 template <typename T>
@@ -243,7 +221,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_cell_finish(const int *__restr
       const bool crowded = o.crowd_list && o.crowd > 0 && cnt[i] >= o.crowd;
       o.cell_rs[c] = make_int2(rank, crowded ? (start | CROWD_TAG) : start);
       if (cnt[i] > PCP_LONG_PILLAR) o.long_list[atomicAdd(&o.counters_ws[6], 1)] = rank;
-      if (crowded) {
+      if (crowded) {                                                       // open-coded: cell_coords' 32-bit multiply-subtract changes this kernel's code
         const int b = (int)(c / plane), rem = (int)(c % plane);
         const int cx = rem / g.ny, cy = rem % g.ny;
         const int at = atomicAdd(&o.counters_ws[4], 1);
@@ -251,7 +229,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_cell_finish(const int *__restr
       }
       o.pillar_cell[rank] = (int)c;
       o.pillar_start[rank] = start;
-      if (o.voxel_coords) {
+      if (o.voxel_coords) {                                                // open-coded, as above
         const int b = (int)(c / plane), rem = (int)(c % plane);
         const int cx = rem / g.ny, cy = rem % g.ny;
         *reinterpret_cast<int4 *>(o.voxel_coords + 4LL * rank) = make_int4(b, 0, cy, cx);       // [batch, z, y, x] (dynamic_pillar_vfe.py:138-143)
@@ -305,9 +283,8 @@ __device__ __forceinline__ void emit_point(const float *__restrict__ points, int
   if (bucket_order) bucket_order[slot] = (int)r;
   if (RS > 0) {
     const float *row = points + r * stride;
-    const int plane = g.nx * g.ny;
-    const int b = cell / plane, rem = cell - b * plane;
-    const int cx = rem / g.ny, cy = rem - cx * g.ny;
+    const CellCoords at = cell_coords(cell, g);
+    const int b = at.b, cx = at.cx, cy = at.cy;
     float v[RS > 0 ? RS : 1];
 #pragma unroll
     for (int k = 0; k < RS - 3; k++) v[k] = k < num_raw ? row[1 + k] : 0.f;
@@ -403,19 +380,20 @@ inline ScanScratch scan_scratch(char *ws, const VoxLayout &L, int64_t cells, int
 // fixed-point sums, order-free maxima; the training path sorts the rows of a pillar by row index).  Not applied to the makers' compaction
 // (k_stc_scatter): in the agents' own frames every (agent, frame) has its own hot cell, the contention is a sixth of the merged cloud's, and
 // the table cost that register-heavy kernel 17 us per launch on the uniform cloud for nothing on the ring (measured, reverted).
-constexpr int VOX_HT = 2048;
-
+// k_cells_z (csrc/vox_front.h) is this kernel's AGG form with the z range tested and the frame column validated; this one also counts the kept
+// rows per tile (unq_inv).
 template <bool AGG>
 __global__ __launch_bounds__(SCAN_THREADS) void k_point_cells(const float *__restrict__ points, long long n, int stride,
                                                               pcp_grid_t g, int *__restrict__ cell_count,
                                                               int *__restrict__ point_cell, int *__restrict__ point_rank,
                                                               int *__restrict__ pt_block_sums) {
   __shared__ int wave_tot[SCAN_THREADS / 64];
-  __shared__ int h_key[AGG ? VOX_HT : 1], h_cnt[AGG ? VOX_HT : 1];
+  __shared__ int h_key[AGG ? CELL_HT : 1], h_cnt[AGG ? CELL_HT : 1];
   long long base = (long long)blockIdx.x * SCAN_TILE;
   int valid = 0;
+  // the table steps are written out here, not called from vox_front.h: as calls they change this kernel's code (exec-mask handling of the probe)
   if (AGG) {
-    for (int e = threadIdx.x; e < VOX_HT; e += SCAN_THREADS) {
+    for (int e = threadIdx.x; e < CELL_HT; e += SCAN_THREADS) {
       h_key[e] = -1;
       h_cnt[e] = 0;
     }
@@ -428,15 +406,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_point_cells(const float *__res
     hslot[i] = -1;
     hloc[i] = 0;
     if (r < n) {
-      int c = point_to_cell(points + r * stride, g);
+      int c = point_to_cell<false>(points + r * stride, g);
       point_cell[r] = c;
       if (c >= 0) {
         if (AGG) {
-          unsigned h = ((unsigned)c * 2654435761u) >> 21;                    // 11 bits
+          unsigned h = cell_hash(c);
           while (true) {
             const int prev = atomicCAS(&h_key[h], -1, c);
             if (prev == -1 || prev == c) break;
-            h = (h + 1) & (VOX_HT - 1);
+            h = (h + 1) & (CELL_HT - 1);
           }
           hslot[i] = (int)h;
           hloc[i] = atomicAdd(&h_cnt[h], 1);
@@ -451,7 +429,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_point_cells(const float *__res
   }
   if (AGG) {
     __syncthreads();
-    for (int e = threadIdx.x; e < VOX_HT; e += SCAN_THREADS) {
+    for (int e = threadIdx.x; e < CELL_HT; e += SCAN_THREADS) {
       const int c = h_key[e];
       if (c >= 0) h_cnt[e] = atomicAdd(&cell_count[c], h_cnt[e]);            // the entry now holds the first slot its rows take in the cell
     }
@@ -462,7 +440,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_point_cells(const float *__res
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) valid += __shfl_xor(valid, d, 64);     // open-coded: the wave_ops.h call changes this kernel's schedule
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = valid;
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = valid;         // open-coded: tile_sum_store swaps the operands of the final adds
   __syncthreads();
   if (threadIdx.x == 0) {
     int s = 0;
@@ -485,14 +463,14 @@ inline int crowd_threshold() {
 int vox_passes(const float *points, int64_t n, int32_t row_stride, const pcp_grid_t *grid, void *workspace, size_t workspace_bytes,
                int32_t *voxel_coords, int64_t *unq_inv, int32_t *unq_cnt, int32_t *counters, hipStream_t stream, bool cells_ready,
                int rows_raw, bool want_bucket_order) {
-  if (!grid || !workspace || n < 0 || row_stride < 3) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !workspace || row_stride < 3) return PCP_ERR_ARG;
   if (rows_raw == 0 && !voxel_coords) return PCP_ERR_ARG;
   if (n > 0 && !points) return PCP_ERR_ARG;
-  if (grid->nx <= 0 || grid->ny <= 0 || grid->batch_size <= 0) return PCP_ERR_ARG;
   if (cells_ready && unq_inv) return PCP_ERR_ARG;
   if (rows_raw && (rows_raw < 3 || rows_raw > 13 || row_stride < 1 + rows_raw || grid->nx > 65535 || grid->ny > 65535)) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   if (rows_raw && n >= (1LL << 30)) return PCP_ERR_UNSUPPORTED;                   // bit 30 of a first slot tags the crowded pillars
   const int64_t n_alloc = n > 0 ? n : 1;
   VoxLayout L = pcp_vox_layout(cells, n_alloc);
@@ -782,7 +760,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_stc_scatter(const float *__res
         for (int c = 4; c < stride; c++) o[c] = row[c];
         if (emit_cells) {
           const float cell_row[3] = {fb, tx, ty};
-          const int c = point_to_cell(cell_row, g);
+          const int c = point_to_cell<false>(cell_row, g);
           point_cell[pos] = c;
           if (c >= 0) point_rank[pos] = atomicAdd(&cell_count[c], 1);
         }
@@ -1033,94 +1011,13 @@ __global__ __launch_bounds__(256) void k_row_order(const int *__restrict__ point
 }  // namespace
 
 // ---- reproducible bucket order (training) ---------------------------------------------------------------------------------------------------
-// A point's slot inside its pillar comes from the histogram atomic of pass 1, so the ORDER of a pillar's points in the bucket order changes
-// from run to run.  Inference does not see it (per-pillar max / fixed-point mean are order independent); the training path's per-point
-// GEMMs sum over the rows in bucket order, so their last bits would.  One thread per pillar sorts its run by point index (runs are a few
-// points long; insertion sort): the bucket order becomes a function of the input alone.  Runs of more than PCP_LONG_PILLAR points (a LiDAR-like
-// cloud has cells with hundreds to thousands: one thread's insertion sort of 5 000 points in global memory took a SECOND) are ranked by the
-// whole workgroup instead: an element's place is the number of smaller ones (the keys are distinct), counted against LDS tiles of the run,
-// four elements per thread and pass; the sorted run is staged in the (by then idle) point_rank array and copied back.
-namespace {
-constexpr int SORT_TILE = 2048, SORT_EPT = 4;
-
-// the workgroup ranks one long run (see above)
-__device__ __forceinline__ void sort_long_run(int s0, int cnt, int *__restrict__ bucket_order, int *__restrict__ scratch, int *tile) {
-  const int tid = threadIdx.x;
-  for (int base = 0; base < cnt; base += 256 * SORT_EPT) {
-    int v[SORT_EPT], rank[SORT_EPT];
-#pragma unroll
-    for (int u = 0; u < SORT_EPT; ++u) {
-      const int e = base + u * 256 + tid;
-      v[u] = e < cnt ? bucket_order[s0 + e] : 0x7fffffff;
-      rank[u] = 0;
-    }
-    for (int tb = 0; tb < cnt; tb += SORT_TILE) {
-      const int tn = min(SORT_TILE, cnt - tb);
-      __syncthreads();
-      for (int j = tid; j < tn; j += 256) tile[j] = bucket_order[s0 + tb + j];
-      __syncthreads();
-      for (int j = 0; j < tn; ++j) {
-        const int w = tile[j];                                    // broadcast read
-#pragma unroll
-        for (int u = 0; u < SORT_EPT; ++u) rank[u] += w < v[u] ? 1 : 0;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < SORT_EPT; ++u)
-      if (base + u * 256 + tid < cnt) scratch[s0 + rank[u]] = v[u];
-  }
-  __syncthreads();                                                 // the whole sorted run is in scratch; nobody reads the unsorted one any more
-  for (int j = tid; j < cnt; j += 256) bucket_order[s0 + j] = scratch[s0 + j];
-  __syncthreads();
-}
-
-// short runs: one thread each (the long ones are on the pillariser's list: k_sort_long_runs)
-__global__ __launch_bounds__(256) void k_sort_runs(const int *__restrict__ pillar_start, const int *__restrict__ counters,
-                                                  int *__restrict__ bucket_order) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= counters[0]) return;
-  const int s0 = pillar_start[p], s1 = pillar_start[p + 1];
-  if (s1 - s0 > PCP_LONG_PILLAR) return;
-  for (int i = s0 + 1; i < s1; ++i) {
-    const int v = bucket_order[i];
-    int j = i - 1;
-    while (j >= s0 && bucket_order[j] > v) {
-      bucket_order[j + 1] = bucket_order[j];
-      --j;
-    }
-    bucket_order[j + 1] = v;
-  }
-}
-
-// one workgroup per listed run, grid-stride: the long runs of a LiDAR-like cloud sit next to each other in pillar order -- left to the
-// workgroup that found them, a few workgroups sorted hundreds of runs each (4.9 ms), spread over the chip they take tens of microseconds
-__global__ __launch_bounds__(256) void k_sort_long_runs(const int *__restrict__ pillar_start, int *__restrict__ bucket_order,
-                                                       int *__restrict__ scratch, const int *__restrict__ long_list,
-                                                       const int *__restrict__ counters) {
-  __shared__ int tile[SORT_TILE];
-  const int nl = counters[6];
-  for (int li = blockIdx.x; li < nl; li += gridDim.x) {
-    const int q = long_list[li];
-    sort_long_run(pillar_start[q], pillar_start[q + 1] - pillar_start[q], bucket_order, scratch, tile);
-  }
-}
-}  // namespace
-
+// Inference does not see the order of a pillar's points (per-pillar max / fixed-point mean are order independent); the training path's
+// per-point GEMMs sum over the rows in bucket order, so their last bits would.  Every pillar's run sorted by point index (csrc/vox_front.h).
 extern "C" int pcp_voxelize_sort_pillar_rows(const pcp_grid_t *grid, void *workspace, int64_t n, void *stream_) {
   if (!grid || !workspace || n < 0) return PCP_ERR_ARG;
   if (n == 0) return PCP_OK;
   const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  const VoxLayout L = pcp_vox_layout(cells, n);
-  char *ws = (char *)workspace;
-  const int64_t max_pillars = n < cells ? n : cells;
-  hipStream_t st = (hipStream_t)stream_;
-  hipLaunchKernelGGL(k_sort_runs, dim3((unsigned)((max_pillars + 255) / 256)), dim3(256), 0, st, (const int *)(ws + L.pillar_start),
-                     (const int *)(ws + L.counters), (int *)(ws + L.bucket_order));
-  PCP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_sort_long_runs, dim3(1024), dim3(256), 0, st, (const int *)(ws + L.pillar_start), (int *)(ws + L.bucket_order),
-                     (int *)(ws + L.point_rank), (const int *)(ws + L.long_list), (const int *)(ws + L.counters));
-  PCP_CHECK_LAUNCH();
-  return PCP_OK;
+  return sort_pillar_runs<RowKey>((char *)workspace, pcp_vox_layout(cells, n), cells, n, (hipStream_t)stream_);
 }
 
 extern "C" int pcp_voxelize_row_order(const pcp_grid_t *grid, const void *workspace, int64_t n, int32_t *order, int32_t *cursor_scratch,
@@ -1161,11 +1058,8 @@ __global__ __launch_bounds__(256) void k_index_export(long long n, pcp_grid_t g,
     row_rank[r] = c >= 0 ? cell_rank[c] : -1;
   }
   if (voxel_coords && r < counters_ws[0]) {
-    const int c = pillar_cell[r];
-    const int plane = g.nx * g.ny;
-    const int b = c / plane, rem = c - b * plane;
-    const int cx = rem / g.ny, cy = rem - cx * g.ny;
-    *reinterpret_cast<int4 *>(voxel_coords + 4 * r) = make_int4(b, 0, cy, cx);
+    const CellCoords at = cell_coords(pillar_cell[r], g);
+    *reinterpret_cast<int4 *>(voxel_coords + 4 * r) = make_int4(at.b, 0, at.cy, at.cx);
   }
   if (srows && r < counters_ws[1]) {
     if (slot_rank) slot_rank[r] = __float_as_int(srows[r * rs + rs - 3]) & 0x7fffffff;        // the sign bit tags the records of crowded pillars
@@ -1177,12 +1071,13 @@ __global__ __launch_bounds__(256) void k_index_export(long long n, pcp_grid_t g,
 
 extern "C" int pcp_pillar_index_export(const pcp_grid_t *grid, const void *workspace, int64_t n, int32_t num_raw, int32_t *voxel_coords,
                                        int32_t *row_rank, int32_t *slot_rank, int32_t *slot_canvas_row, int32_t *counters, void *stream_) {
-  if (!grid || !workspace || n < 0 || grid->nx <= 0 || grid->ny <= 0 || grid->batch_size <= 0) return PCP_ERR_ARG;
+  int64_t cells;
+  const int front = pcp_front_args(grid, n, &cells);
+  if (front == PCP_ERR_ARG || !workspace) return PCP_ERR_ARG;
   if (num_raw != 0 && (num_raw < 3 || num_raw > 13)) return PCP_ERR_ARG;
   if ((slot_rank || slot_canvas_row) && num_raw == 0) return PCP_ERR_ARG;                        // a pcp_voxelize workspace holds no records
   if (((uintptr_t)voxel_coords) & 15) return PCP_ERR_ARG;
-  const int64_t cells = (int64_t)grid->batch_size * grid->nx * grid->ny;
-  if (cells >= (1LL << 31) || n >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
+  if (front != PCP_OK) return front;
   const int64_t n_alloc = n > 0 ? n : 1;
   const VoxLayout L = pcp_vox_layout(cells, n_alloc);
   const char *ws = (const char *)workspace;
