@@ -732,6 +732,21 @@ int pcp_pillar_vfe(const float *voxels, const int32_t *voxel_num_points, const i
  *
  * Dense: out (batch, h, w, channels * d) float32, EVERY element written: channel c * d_extent + z of pixel (b, y, x) is feature c of site
  * (b, z, y, x) or 0.  d <= 64.
+ *
+ * Device-count forms (`_dev`): the same kernel bodies with every row count read from device memory, for a forward without a host read
+ * in its middle.  Each takes `n_dev`, one int32 an earlier kernel of the same stream wrote (counters[0] of pcp_mean_vfe, of the table
+ * build or of the strided sites), and a host `capacity` that sizes the launch and every buffer; the count used is min(*n_dev, capacity).
+ *   - rows at or past the count are neither read (inputs) nor written (features, coords, nbr, perm); a wave tile or workgroup wholly at or
+ *     past it returns after reading the count alone
+ *   - nbr[k][row] sits at k * capacity + row (pcp_spconv3d_dev takes the stride as ld_nbr >= capacity)
+ *   - rows below the count have the bits of the host-count form: a row's bits depend on its own neighbour list only
+ *   - strided sites: counters[0] = min(rows, out_capacity), counters[2] = rows; rows > out_capacity sets err_bit in *err (err may be NULL) and
+ *     the tail of the ascending linear order is what the build drops.  The exact bound min(in_capacity * prod(ceil(k / s)), output sites)
+ *     never overflows.
+ *   - a lookup that lands on a row at or past the capacity of its set (a dropped tail; a perm entry of a set with duplicated sites, which
+ *     these forms do not detect: the caller guarantees distinct in-range sites) reads as absent; pcp_spconv_dense_below is the dense form
+ *     with that rule (pcp_spconv_dense reads no count and needs no other change)
+ * No float atomics, no scatter; the only atomics remain the bitmap's atomicOr.  The error bit is a plain read-modify-write by one thread.
  * ------------------------------------------------------------------------------------------------------------------ */
 #define PCP_MEAN_VFE_MAX_NZ 64
 #define PCP_MEAN_VFE_MAX_BATCH 64
@@ -758,6 +773,25 @@ int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, int32_t ld_in
                  const float *w_packed, const float *bias, const float *residual, int32_t relu, int32_t cout, float *out, void *stream);
 int pcp_spconv_dense(const float *features, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table,
                      size_t table_bytes, const int32_t *perm, float *out, void *stream);
+int pcp_mean_vfe_features_dev(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
+                              const void *workspace, size_t workspace_bytes, const int32_t *n_dev, int64_t capacity, float *voxel_features,
+                              void *stream);
+int pcp_spconv_table_build_dev(const int32_t *coords, const int32_t *n_dev, int64_t capacity, int32_t batch, int32_t d, int32_t h, int32_t w,
+                               void *table, size_t table_bytes, int32_t *perm, int32_t *counters, void *stream);
+int pcp_spconv_build_subm_dev(const int32_t *coords, const int32_t *n_dev, int64_t capacity, int32_t batch, int32_t d, int32_t h, int32_t w,
+                              const void *table, size_t table_bytes, const int32_t *perm, int32_t *nbr, void *stream);
+int pcp_spconv_strided_sites_dev(const int32_t *in_coords, const int32_t *n_in_dev, int64_t in_capacity, int32_t batch, int32_t d, int32_t h,
+                                 int32_t w, const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, void *out_table,
+                                 size_t out_table_bytes, int64_t out_capacity, int32_t *counters, int32_t *err, int32_t err_bit, void *stream);
+int pcp_spconv_build_strided_dev(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes,
+                                 const int32_t *in_perm, int64_t in_capacity, const int32_t *kernel3, const int32_t *stride3,
+                                 const int32_t *pad3, const void *out_table, size_t out_table_bytes, const int32_t *n_out_dev,
+                                 int64_t out_capacity, int32_t *out_coords, int32_t *nbr, void *stream);
+int pcp_spconv3d_dev(const float *features, int64_t in_capacity, int32_t cin, int32_t ld_in, const int32_t *nbr, int64_t ld_nbr,
+                     int32_t num_offsets, const int32_t *n_dev, int64_t capacity, const float *w_packed, const float *bias,
+                     const float *residual, int32_t relu, int32_t cout, float *out, void *stream);
+int pcp_spconv_dense_below(const float *features, int64_t capacity, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w,
+                           const void *table, size_t table_bytes, const int32_t *perm, float *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -111,11 +111,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_mv_number(pcp_grid_t g, const 
   if (kept == 0 && tile == 0 && threadIdx.x == 0) vox_start[0] = 0;       // counters were zero-filled: M = 0
 }
 
-// a wave per voxel; lane = 16 g + column
+// The device-count forms (DEV): the row count is read from device memory, where an earlier kernel of the stream left it, and clamped to the
+// capacity the host sized the launch and the buffers by.  Rows at or past it are neither read nor written.
+__device__ __forceinline__ long long dev_rows(const int *__restrict__ n_dev, long long capacity) {
+  const long long v = *n_dev;
+  return v < 0 ? 0 : (v < capacity ? v : capacity);
+}
+
+// a wave per voxel; lane = 16 g + column.  DEV: M is the capacity, the count is *n_dev
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_mv_mean(const float *__restrict__ points, int stride, int C, long long M, const int *__restrict__ vox_start,
-                                                 const int *__restrict__ order, float *__restrict__ voxel_features) {
+                                                 const int *__restrict__ order, float *__restrict__ voxel_features, const int *__restrict__ n_dev) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long v = (long long)blockIdx.x * 4 + wave;
+  if (DEV) M = dev_rows(n_dev, M);
   if (v >= M) return;
   const int s0 = vox_start[v], n = vox_start[v + 1] - s0;
   const int col = lane & 15, grp = lane >> 4;
@@ -184,8 +193,10 @@ extern "C" int pcp_mean_vfe(const float *points, int64_t n, int32_t row_stride, 
   return PCP_OK;
 }
 
-extern "C" int pcp_mean_vfe_features(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
-                                     const void *workspace, size_t workspace_bytes, int64_t num_voxels, float *voxel_features, void *stream_) {
+// num_voxels: the count (n_dev NULL) or the capacity the launch is sized by (the count is *n_dev)
+static int mean_vfe_features(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
+                             const void *workspace, size_t workspace_bytes, int64_t num_voxels, const int32_t *n_dev, float *voxel_features,
+                             void *stream_) {
   int64_t cells;
   const int front = pcp_front_args(grid, n, &cells);
   if (front == PCP_ERR_ARG || !mv_args_ok(grid, n, row_stride, nz)) return PCP_ERR_ARG;
@@ -198,10 +209,26 @@ extern "C" int pcp_mean_vfe_features(const float *points, int64_t n, int32_t row
   if (workspace_bytes < L.total) return PCP_ERR_WORKSPACE;
   const char *ws = (const char *)workspace;
   const long long blocks = (num_voxels + 3) / 4;
-  hipLaunchKernelGGL(k_mv_mean, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, points, (int)row_stride, (int)num_features,
-                     (long long)num_voxels, (const int *)(ws + L.vox_start), (const int *)(ws + L.v.bucket_order), voxel_features);
+  if (n_dev)
+    hipLaunchKernelGGL(k_mv_mean<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, points, (int)row_stride, (int)num_features,
+                       (long long)num_voxels, (const int *)(ws + L.vox_start), (const int *)(ws + L.v.bucket_order), voxel_features, (const int *)n_dev);
+  else
+    hipLaunchKernelGGL(k_mv_mean<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, points, (int)row_stride, (int)num_features,
+                       (long long)num_voxels, (const int *)(ws + L.vox_start), (const int *)(ws + L.v.bucket_order), voxel_features, (const int *)nullptr);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
+}
+
+extern "C" int pcp_mean_vfe_features(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid, int32_t nz,
+                                     const void *workspace, size_t workspace_bytes, int64_t num_voxels, float *voxel_features, void *stream_) {
+  return mean_vfe_features(points, n, row_stride, num_features, grid, nz, workspace, workspace_bytes, num_voxels, nullptr, voxel_features, stream_);
+}
+
+extern "C" int pcp_mean_vfe_features_dev(const float *points, int64_t n, int32_t row_stride, int32_t num_features, const pcp_grid_t *grid,
+                                         int32_t nz, const void *workspace, size_t workspace_bytes, const int32_t *n_dev, int64_t capacity,
+                                         float *voxel_features, void *stream_) {
+  if (!n_dev) return PCP_ERR_ARG;
+  return mean_vfe_features(points, n, row_stride, num_features, grid, nz, workspace, workspace_bytes, capacity, n_dev, voxel_features, stream_);
 }
 
 // ---- index tables ------------------------------------------------------------------------------------------------------------------------------
@@ -252,8 +279,18 @@ __device__ __forceinline__ int sp_lookup(const SpShape s, const u64 *__restrict_
   return perm ? perm[rank] : rank;
 }
 
-__global__ __launch_bounds__(256) void k_sp_mark(const int *__restrict__ coords, long long n, SpShape s, u64 *__restrict__ bits, int *__restrict__ counters) {
+// sp_lookup for the device-count forms: a row at or past `limit` (the capacity of the set: a clamped tail, or a perm entry nobody wrote) is absent
+__device__ __forceinline__ int sp_lookup_below(const SpShape s, const u64 *__restrict__ bits, const int *__restrict__ prefix,
+                                               const int *__restrict__ perm, int b, int z, int y, int x, long long limit) {
+  const int r = sp_lookup(s, bits, prefix, perm, b, z, y, x);
+  return (r >= 0 && r < limit) ? r : -1;
+}
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void k_sp_mark(const int *__restrict__ coords, long long n, SpShape s, u64 *__restrict__ bits, int *__restrict__ counters,
+                                                 const int *__restrict__ n_dev) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (DEV) n = dev_rows(n_dev, n);
   if (i >= n) return;
   const int4 c = *reinterpret_cast<const int4 *>(coords + 4 * i);
   if (c.x < 0 || c.x >= s.B || c.y < 0 || c.y >= s.D || c.z < 0 || c.z >= s.H || c.w < 0 || c.w >= s.W) {
@@ -265,9 +302,11 @@ __global__ __launch_bounds__(256) void k_sp_mark(const int *__restrict__ coords,
 }
 
 // every output site some input reaches: o = (i + p - d) / s for the offsets d it divides evenly
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_sp_mark_strided(const int *__restrict__ coords, long long n, SpShape si, SpShape so, SpConvGeom g,
-                                                         u64 *__restrict__ bits, int *__restrict__ counters) {
+                                                         u64 *__restrict__ bits, int *__restrict__ counters, const int *__restrict__ n_dev) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (DEV) n = dev_rows(n_dev, n);
   if (i >= n) return;
   const int4 c = *reinterpret_cast<const int4 *>(coords + 4 * i);
   if (c.x < 0 || c.x >= si.B || c.y < 0 || c.y >= si.D || c.z < 0 || c.z >= si.H || c.w < 0 || c.w >= si.W) {
@@ -318,8 +357,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_sp_tile_sums(const u64 *__rest
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = s;
 }
 
-// one workgroup: tile_sums becomes its exclusive prefix, the total goes to tile_sums[n_tiles] and counters[0]
-__global__ __launch_bounds__(SCAN_THREADS) void k_sp_scan_tiles(int *__restrict__ tile_sums, int n_tiles, int *__restrict__ counters) {
+// one workgroup: tile_sums becomes its exclusive prefix, the total goes to tile_sums[n_tiles] and counters[0].  DEV: counters[0] is the total
+// clamped to `capacity`, counters[2] the total itself, and a total above the capacity sets `err_bit` in *err (one thread of one workgroup, and
+// the kernels of a stream run in order: a plain read-modify-write)
+template <bool DEV>
+__global__ __launch_bounds__(SCAN_THREADS) void k_sp_scan_tiles(int *__restrict__ tile_sums, int n_tiles, int *__restrict__ counters, long long capacity,
+                                                              int *__restrict__ err, int err_bit) {
   __shared__ int lds_wave[SCAN_THREADS / 64];
   __shared__ int carry_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -350,7 +393,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_sp_scan_tiles(int *__restrict_
   }
   if (threadIdx.x == 0) {
     tile_sums[n_tiles] = carry_s;
-    counters[0] = carry_s;
+    if (DEV) {
+      counters[0] = carry_s > capacity ? (int)capacity : carry_s;
+      counters[2] = carry_s;
+      if (carry_s > capacity && err) *err = *err | err_bit;
+    } else {
+      counters[0] = carry_s;
+    }
   }
 }
 
@@ -371,9 +420,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_sp_prefix(const u64 *__restric
 }
 
 // perm[rank of row i's site] = i (the sites of a valid set are distinct: one writer per entry)
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_sp_perm(const int *__restrict__ coords, long long n, SpShape s, const u64 *__restrict__ bits,
-                                                 const int *__restrict__ prefix, int *__restrict__ perm) {
+                                                 const int *__restrict__ prefix, int *__restrict__ perm, const int *__restrict__ n_dev) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (DEV) n = dev_rows(n_dev, n);
   if (i >= n) return;
   const int4 c = *reinterpret_cast<const int4 *>(coords + 4 * i);
   if (c.x < 0 || c.x >= s.B) return;
@@ -381,23 +432,34 @@ __global__ __launch_bounds__(256) void k_sp_perm(const int *__restrict__ coords,
   if (rank >= 0 && rank < n) perm[rank] = (int)i;
 }
 
+// nbr[k][row] sits at k * ld + row: ld is the row count, or (DEV) the capacity n, with the count in *n_dev
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_sp_subm_nbr(const int *__restrict__ coords, long long n, SpShape s, const u64 *__restrict__ bits,
-                                                     const int *__restrict__ prefix, const int *__restrict__ perm, int *__restrict__ nbr) {
+                                                     const int *__restrict__ prefix, const int *__restrict__ perm, int *__restrict__ nbr,
+                                                     const int *__restrict__ n_dev) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long ld = n;
+  if (DEV) n = dev_rows(n_dev, n);
   if (i >= n) return;
   const int4 c = *reinterpret_cast<const int4 *>(coords + 4 * i);
   const bool ok = c.x >= 0 && c.x < s.B;
   int k = 0;
   for (int dz = -1; dz <= 1; dz++)
     for (int dy = -1; dy <= 1; dy++)
-      for (int dx = -1; dx <= 1; dx++, k++) nbr[(long long)k * n + i] = ok ? sp_lookup(s, bits, prefix, perm, c.x, c.y + dz, c.z + dy, c.w + dx) : -1;
+      for (int dx = -1; dx <= 1; dx++, k++) {
+        int r = -1;
+        if (ok) r = DEV ? sp_lookup_below(s, bits, prefix, perm, c.x, c.y + dz, c.z + dy, c.w + dx, ld) : sp_lookup(s, bits, prefix, perm, c.x, c.y + dz, c.z + dy, c.w + dx);
+        nbr[(long long)k * ld + i] = r;
+      }
 }
 
 // the coordinates of a table's sites in rank order: a thread per 64-bit word
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_sp_table_coords(SpShape s, const u64 *__restrict__ bits, const int *__restrict__ prefix, long long words,
-                                                         long long n_out, int *__restrict__ coords) {
+                                                         long long n_out, int *__restrict__ coords, const int *__restrict__ n_dev) {
   const long long w = (long long)blockIdx.x * 256 + threadIdx.x;
   if (w >= words) return;
+  if (DEV) n_out = dev_rows(n_dev, n_out);
   u64 word = bits[w];
   long long rank = prefix[w];
   while (word) {
@@ -415,26 +477,37 @@ __global__ __launch_bounds__(256) void k_sp_table_coords(SpShape s, const u64 *_
   }
 }
 
+// DEV: n_out is the capacity (and the stride of nbr), the count is *n_dev, and an input row at or past in_limit is absent
+template <bool DEV>
 __global__ __launch_bounds__(256) void k_sp_strided_nbr(const int *__restrict__ out_coords, long long n_out, SpShape si, SpConvGeom g,
                                                         const u64 *__restrict__ bits, const int *__restrict__ prefix, const int *__restrict__ perm,
-                                                        int *__restrict__ nbr) {
+                                                        int *__restrict__ nbr, const int *__restrict__ n_dev, long long in_limit) {
   const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long ld = n_out;
+  if (DEV) n_out = dev_rows(n_dev, n_out);
   if (o >= n_out) return;
   const int4 c = *reinterpret_cast<const int4 *>(out_coords + 4 * o);
   const bool ok = c.x >= 0 && c.x < si.B;
   int k = 0;
   for (int dz = 0; dz < g.kz; dz++)
     for (int dy = 0; dy < g.ky; dy++)
-      for (int dx = 0; dx < g.kx; dx++, k++)
-        nbr[(long long)k * n_out + o] =
-            ok ? sp_lookup(si, bits, prefix, perm, c.x, c.y * g.sz - g.pz + dz, c.z * g.sy - g.py + dy, c.w * g.sx - g.px + dx) : -1;
+      for (int dx = 0; dx < g.kx; dx++, k++) {
+        const int z = c.y * g.sz - g.pz + dz, y = c.z * g.sy - g.py + dy, x = c.w * g.sx - g.px + dx;
+        int r = -1;
+        if (ok) r = DEV ? sp_lookup_below(si, bits, prefix, perm, c.x, z, y, x, in_limit) : sp_lookup(si, bits, prefix, perm, c.x, z, y, x);
+        nbr[(long long)k * ld + o] = r;
+      }
 }
 
 // bits are set; tile sums, their scan (total -> counters[0]) and the per-word prefix
-int sp_finish_table(const SpTable &t, int *counters, hipStream_t stream) {
+// capacity >= 0: the device-count form of the scan (clamped count, overflow bit)
+int sp_finish_table(const SpTable &t, int *counters, hipStream_t stream, long long capacity = -1, int *err = nullptr, int err_bit = 0) {
   hipLaunchKernelGGL(k_sp_tile_sums, dim3(t.n_tiles), dim3(SCAN_THREADS), 0, stream, (const u64 *)t.bits, t.words, t.tile_sums);
   PCP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_sp_scan_tiles, dim3(1), dim3(SCAN_THREADS), 0, stream, t.tile_sums, t.n_tiles, counters);
+  if (capacity >= 0)
+    hipLaunchKernelGGL(k_sp_scan_tiles<true>, dim3(1), dim3(SCAN_THREADS), 0, stream, t.tile_sums, t.n_tiles, counters, capacity, err, err_bit);
+  else
+    hipLaunchKernelGGL(k_sp_scan_tiles<false>, dim3(1), dim3(SCAN_THREADS), 0, stream, t.tile_sums, t.n_tiles, counters, 0LL, (int *)nullptr, 0);
   PCP_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_sp_prefix, dim3(t.n_tiles), dim3(SCAN_THREADS), 0, stream, (const u64 *)t.bits, t.words, (const int *)t.tile_sums, t.prefix);
   PCP_CHECK_LAUNCH();
@@ -459,8 +532,10 @@ extern "C" size_t pcp_spconv_table_bytes(int32_t batch, int32_t d, int32_t h, in
   return sp_shape_ok(s) ? sp_table_bytes(s) : 0;
 }
 
-extern "C" int pcp_spconv_table_build(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, void *table,
-                                      size_t table_bytes, int32_t *perm, int32_t *counters, void *stream_) {
+// n_dev NULL: n is the count.  Otherwise n is the capacity (launch size) and *n_dev the count.
+template <bool DEV>
+static int spconv_table_build(const int32_t *coords, int64_t n, const int32_t *n_dev, int32_t batch, int32_t d, int32_t h, int32_t w, void *table,
+                              size_t table_bytes, int32_t *perm, int32_t *counters, void *stream_) {
   const SpShape s{batch, d, h, w};
   if (!sp_shape_ok(s) || n < 0 || n >= (1LL << 31) || !table || !counters || (n > 0 && (!coords || !perm))) return PCP_ERR_ARG;
   if ((((uintptr_t)coords) & 15) || (((uintptr_t)table) & 255)) return PCP_ERR_ARG;
@@ -471,35 +546,61 @@ extern "C" int pcp_spconv_table_build(const int32_t *coords, int64_t n, int32_t 
   if (pcp_zero_async(counters, 16, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   const unsigned nb = (unsigned)((n + 255) / 256);
   if (n > 0) {
-    hipLaunchKernelGGL(k_sp_mark, dim3(nb), dim3(256), 0, stream, coords, (long long)n, s, t.bits, counters);
+    hipLaunchKernelGGL(k_sp_mark<DEV>, dim3(nb), dim3(256), 0, stream, coords, (long long)n, s, t.bits, counters, (const int *)n_dev);
     PCP_CHECK_LAUNCH();
   }
   const int st = sp_finish_table(t, counters, stream);
   if (st != PCP_OK) return st;
   if (n > 0) {
-    hipLaunchKernelGGL(k_sp_perm, dim3(nb), dim3(256), 0, stream, coords, (long long)n, s, (const u64 *)t.bits, (const int *)t.prefix, perm);
+    hipLaunchKernelGGL(k_sp_perm<DEV>, dim3(nb), dim3(256), 0, stream, coords, (long long)n, s, (const u64 *)t.bits, (const int *)t.prefix, perm,
+                       (const int *)n_dev);
     PCP_CHECK_LAUNCH();
   }
   return PCP_OK;
 }
 
-extern "C" int pcp_spconv_build_subm(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table,
-                                     size_t table_bytes, const int32_t *perm, int32_t *nbr, void *stream_) {
+extern "C" int pcp_spconv_table_build(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, void *table,
+                                      size_t table_bytes, int32_t *perm, int32_t *counters, void *stream_) {
+  return spconv_table_build<false>(coords, n, nullptr, batch, d, h, w, table, table_bytes, perm, counters, stream_);
+}
+
+extern "C" int pcp_spconv_table_build_dev(const int32_t *coords, const int32_t *n_dev, int64_t capacity, int32_t batch, int32_t d, int32_t h,
+                                          int32_t w, void *table, size_t table_bytes, int32_t *perm, int32_t *counters, void *stream_) {
+  if (!n_dev) return PCP_ERR_ARG;
+  return spconv_table_build<true>(coords, capacity, n_dev, batch, d, h, w, table, table_bytes, perm, counters, stream_);
+}
+
+template <bool DEV>
+static int spconv_build_subm(const int32_t *coords, int64_t n, const int32_t *n_dev, int32_t batch, int32_t d, int32_t h, int32_t w,
+                             const void *table, size_t table_bytes, const int32_t *perm, int32_t *nbr, void *stream_) {
   const SpShape s{batch, d, h, w};
   if (!sp_shape_ok(s) || n < 0 || n >= (1LL << 31) || !table) return PCP_ERR_ARG;
   if (n == 0) return PCP_OK;
   if (!coords || !nbr || (((uintptr_t)coords) & 15) || (((uintptr_t)table) & 255)) return PCP_ERR_ARG;
   if (table_bytes < sp_table_bytes(s)) return PCP_ERR_WORKSPACE;
   const SpTable t = sp_table(const_cast<void *>(table), s);
-  hipLaunchKernelGGL(k_sp_subm_nbr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, coords, (long long)n, s,
-                     (const u64 *)t.bits, (const int *)t.prefix, perm, nbr);
+  hipLaunchKernelGGL(k_sp_subm_nbr<DEV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, coords, (long long)n, s,
+                     (const u64 *)t.bits, (const int *)t.prefix, perm, nbr, (const int *)n_dev);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
 }
 
-extern "C" int pcp_spconv_strided_sites(const int32_t *in_coords, int64_t n_in, int32_t batch, int32_t d, int32_t h, int32_t w,
-                                        const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, void *out_table,
-                                        size_t out_table_bytes, int32_t *counters, void *stream_) {
+extern "C" int pcp_spconv_build_subm(const int32_t *coords, int64_t n, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table,
+                                     size_t table_bytes, const int32_t *perm, int32_t *nbr, void *stream_) {
+  return spconv_build_subm<false>(coords, n, nullptr, batch, d, h, w, table, table_bytes, perm, nbr, stream_);
+}
+
+extern "C" int pcp_spconv_build_subm_dev(const int32_t *coords, const int32_t *n_dev, int64_t capacity, int32_t batch, int32_t d, int32_t h,
+                                         int32_t w, const void *table, size_t table_bytes, const int32_t *perm, int32_t *nbr, void *stream_) {
+  if (!n_dev) return PCP_ERR_ARG;
+  return spconv_build_subm<true>(coords, capacity, n_dev, batch, d, h, w, table, table_bytes, perm, nbr, stream_);
+}
+
+// out_capacity < 0: the host-count form
+template <bool DEV>
+static int spconv_strided_sites(const int32_t *in_coords, int64_t n_in, const int32_t *n_in_dev, int32_t batch, int32_t d, int32_t h, int32_t w,
+                                const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, void *out_table, size_t out_table_bytes,
+                                int64_t out_capacity, int32_t *counters, int32_t *err, int32_t err_bit, void *stream_) {
   if (!kernel3 || !stride3 || !pad3) return PCP_ERR_ARG;
   const SpShape si{batch, d, h, w};
   const SpConvGeom g{kernel3[0], kernel3[1], kernel3[2], stride3[0], stride3[1], stride3[2], pad3[0], pad3[1], pad3[2]};
@@ -513,17 +614,35 @@ extern "C" int pcp_spconv_strided_sites(const int32_t *in_coords, int64_t n_in, 
   if (pcp_zero_async(t.bits, (size_t)t.words * 8, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (pcp_zero_async(counters, 16, stream) != PCP_OK) return PCP_ERR_LAUNCH;
   if (n_in > 0) {
-    hipLaunchKernelGGL(k_sp_mark_strided, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, in_coords, (long long)n_in, si, so, g, t.bits,
-                       counters);
+    hipLaunchKernelGGL(k_sp_mark_strided<DEV>, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, in_coords, (long long)n_in, si, so, g,
+                       t.bits, counters, (const int *)n_in_dev);
     PCP_CHECK_LAUNCH();
   }
-  return sp_finish_table(t, counters, stream);
+  return DEV ? sp_finish_table(t, counters, stream, out_capacity, err, err_bit) : sp_finish_table(t, counters, stream);
 }
 
-extern "C" int pcp_spconv_build_strided(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes,
-                                        const int32_t *in_perm, const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3,
-                                        const void *out_table, size_t out_table_bytes, int64_t n_out, int32_t *out_coords, int32_t *nbr,
-                                        void *stream_) {
+extern "C" int pcp_spconv_strided_sites(const int32_t *in_coords, int64_t n_in, int32_t batch, int32_t d, int32_t h, int32_t w,
+                                        const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, void *out_table,
+                                        size_t out_table_bytes, int32_t *counters, void *stream_) {
+  return spconv_strided_sites<false>(in_coords, n_in, nullptr, batch, d, h, w, kernel3, stride3, pad3, out_table, out_table_bytes, -1, counters,
+                                     nullptr, 0, stream_);
+}
+
+extern "C" int pcp_spconv_strided_sites_dev(const int32_t *in_coords, const int32_t *n_in_dev, int64_t in_capacity, int32_t batch, int32_t d,
+                                            int32_t h, int32_t w, const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3,
+                                            void *out_table, size_t out_table_bytes, int64_t out_capacity, int32_t *counters, int32_t *err,
+                                            int32_t err_bit, void *stream_) {
+  if (!n_in_dev || out_capacity < 0 || out_capacity >= (1LL << 31)) return PCP_ERR_ARG;
+  return spconv_strided_sites<true>(in_coords, in_capacity, n_in_dev, batch, d, h, w, kernel3, stride3, pad3, out_table, out_table_bytes,
+                                    out_capacity, counters, err, err_bit, stream_);
+}
+
+// in_limit: rows of the input set the caller's buffers hold (DEV only)
+template <bool DEV>
+static int spconv_build_strided(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes, const int32_t *in_perm,
+                                int64_t in_limit, const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3, const void *out_table,
+                                size_t out_table_bytes, int64_t n_out, const int32_t *n_out_dev, int32_t *out_coords, int32_t *nbr,
+                                void *stream_) {
   if (!kernel3 || !stride3 || !pad3) return PCP_ERR_ARG;
   const SpShape si{batch, d, h, w};
   const SpConvGeom g{kernel3[0], kernel3[1], kernel3[2], stride3[0], stride3[1], stride3[2], pad3[0], pad3[1], pad3[2]};
@@ -535,13 +654,30 @@ extern "C" int pcp_spconv_build_strided(int32_t batch, int32_t d, int32_t h, int
   if (in_table_bytes < sp_table_bytes(si) || out_table_bytes < sp_table_bytes(so)) return PCP_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const SpTable ti = sp_table(const_cast<void *>(in_table), si), to = sp_table(const_cast<void *>(out_table), so);
-  hipLaunchKernelGGL(k_sp_table_coords, dim3((unsigned)((to.words + 255) / 256)), dim3(256), 0, stream, so, (const u64 *)to.bits, (const int *)to.prefix,
-                     to.words, (long long)n_out, out_coords);
+  hipLaunchKernelGGL(k_sp_table_coords<DEV>, dim3((unsigned)((to.words + 255) / 256)), dim3(256), 0, stream, so, (const u64 *)to.bits,
+                     (const int *)to.prefix, to.words, (long long)n_out, out_coords, (const int *)n_out_dev);
   PCP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_sp_strided_nbr, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, (const int *)out_coords, (long long)n_out, si, g,
-                     (const u64 *)ti.bits, (const int *)ti.prefix, in_perm, nbr);
+  hipLaunchKernelGGL(k_sp_strided_nbr<DEV>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, (const int *)out_coords, (long long)n_out, si,
+                     g, (const u64 *)ti.bits, (const int *)ti.prefix, in_perm, nbr, (const int *)n_out_dev, (long long)in_limit);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
+}
+
+extern "C" int pcp_spconv_build_strided(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes,
+                                        const int32_t *in_perm, const int32_t *kernel3, const int32_t *stride3, const int32_t *pad3,
+                                        const void *out_table, size_t out_table_bytes, int64_t n_out, int32_t *out_coords, int32_t *nbr,
+                                        void *stream_) {
+  return spconv_build_strided<false>(batch, d, h, w, in_table, in_table_bytes, in_perm, 0, kernel3, stride3, pad3, out_table, out_table_bytes, n_out,
+                                     nullptr, out_coords, nbr, stream_);
+}
+
+extern "C" int pcp_spconv_build_strided_dev(int32_t batch, int32_t d, int32_t h, int32_t w, const void *in_table, size_t in_table_bytes,
+                                            const int32_t *in_perm, int64_t in_capacity, const int32_t *kernel3, const int32_t *stride3,
+                                            const int32_t *pad3, const void *out_table, size_t out_table_bytes, const int32_t *n_out_dev,
+                                            int64_t out_capacity, int32_t *out_coords, int32_t *nbr, void *stream_) {
+  if (!n_out_dev || in_capacity < 0) return PCP_ERR_ARG;
+  return spconv_build_strided<true>(batch, d, h, w, in_table, in_table_bytes, in_perm, in_capacity, kernel3, stride3, pad3, out_table,
+                                    out_table_bytes, out_capacity, n_out_dev, out_coords, nbr, stream_);
 }
 
 // ---- the convolution ---------------------------------------------------------------------------------------------------------------------------
@@ -551,22 +687,26 @@ namespace {
 // A[row m][k = q] and B[k = q][column m]; step (j, kk) of the reduction covers input channels 16 j + 4 q + kk, q = 0 .. 3, so the order over
 // cin is fixed: j ascending, kk ascending.  acc[c][i] is output row 4 q + i, channel 16 c + m.
 // VEC: cin == CI16 * 16 and 16-byte aligned rows; otherwise (the first layer's 3 .. 16 columns) guarded scalar loads, zeros behind cin.
-template <int CI16, int CO16, bool VEC>
+// DEV: n_out is the capacity (the launch size), the row count is *n_dev and nbr[k][row] sits at k * ld_nbr + row; otherwise the stride of nbr
+// is n_out itself.  One body: a row's bits depend on its own neighbour list only, so the two forms give a row the same bits.
+template <int CI16, int CO16, bool VEC, bool DEV>
 __global__ __launch_bounds__(256) void k_spconv3d(const float *__restrict__ feat, int cin, int ld_in, const int *__restrict__ nbr, int K, long long n_out,
                                                   const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ residual,
-                                                  int relu, float *__restrict__ out) {
+                                                  int relu, float *__restrict__ out, const int *__restrict__ n_dev, long long ld_nbr) {
   constexpr int CI = CI16 * 16, CO = CO16 * 16;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m = lane & 15, q = lane >> 4;
   const long long row0 = ((long long)blockIdx.x * 4 + wave) * 16;
+  if (DEV) n_out = dev_rows(n_dev, n_out);
   if (row0 >= n_out) return;
+  const long long ld = DEV ? ld_nbr : n_out;
   const long long row = row0 + m;
   f32x4 acc[CO16];
 #pragma unroll
   for (int c = 0; c < CO16; c++) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k = 0; k < K; k++) {
-    const int idx = row < n_out ? nbr[(long long)k * n_out + row] : -1;
+    const int idx = row < n_out ? nbr[(long long)k * ld + row] : -1;
     if (__ballot(idx >= 0) == 0ULL) continue;              // none of the 16 rows has this neighbour: wave-uniform
     f32x4 a[CI16];
 #pragma unroll
@@ -612,14 +752,17 @@ __global__ __launch_bounds__(256) void k_spconv3d(const float *__restrict__ feat
 }
 
 // every element of the (B, H, W, C * D) canvas is written: channel c * D + d of pixel (b, y, x) is feature c of site (b, d, y, x), or zero
+// LIM: a site whose row lies at or past `limit` (the tail a clamped build dropped) reads as empty
+template <bool LIM>
 __global__ __launch_bounds__(256) void k_sp_dense(const float *__restrict__ feat, int C, SpShape s, const u64 *__restrict__ bits,
-                                                  const int *__restrict__ prefix, const int *__restrict__ perm, float *__restrict__ out) {
+                                                  const int *__restrict__ prefix, const int *__restrict__ perm, float *__restrict__ out, long long limit) {
   __shared__ int rows[PCP_MEAN_VFE_MAX_NZ];
   const long long pix = blockIdx.x;                               // (b * H + y) * W + x
   const int x = (int)(pix % s.W);
   const int y = (int)((pix / s.W) % s.H);
   const int b = (int)(pix / ((long long)s.W * s.H));
-  if ((int)threadIdx.x < s.D) rows[threadIdx.x] = sp_lookup(s, bits, prefix, perm, b, (int)threadIdx.x, y, x);
+  if ((int)threadIdx.x < s.D)
+    rows[threadIdx.x] = LIM ? sp_lookup_below(s, bits, prefix, perm, b, (int)threadIdx.x, y, x, limit) : sp_lookup(s, bits, prefix, perm, b, (int)threadIdx.x, y, x);
   __syncthreads();
   const int CD = C * s.D;
   for (int ch = threadIdx.x; ch < CD; ch += 256) {
@@ -631,9 +774,11 @@ __global__ __launch_bounds__(256) void k_sp_dense(const float *__restrict__ feat
 
 }  // namespace
 
-extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, int32_t ld_in, const int32_t *nbr, int32_t num_offsets, int64_t n_out,
-                            const float *w_packed, const float *bias, const float *residual, int32_t relu, int32_t cout, float *out,
-                            void *stream_) {
+// n_dev NULL: n_out is the count and the stride of nbr
+template <bool DEV>
+static int spconv3d(const float *features, int64_t n_in, int32_t cin, int32_t ld_in, const int32_t *nbr, int64_t ld_nbr, int32_t num_offsets,
+                    int64_t n_out, const int32_t *n_dev, const float *w_packed, const float *bias, const float *residual, int32_t relu, int32_t cout,
+                    float *out, void *stream_) {
   if (n_in < 0 || n_out < 0 || n_in >= (1LL << 31) || n_out >= (1LL << 31) || num_offsets < 1 || num_offsets > 27 || ld_in < cin) return PCP_ERR_ARG;
   const int cin_pad = cin <= 16 ? 16 : cin;
   // (32 -> 16), (64 -> 32), (128 -> 64): the data gradients of the strided layers (csrc/spconv3d_train.hip)
@@ -648,8 +793,8 @@ extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, in
   const long long blocks = (n_out + 63) / 64;
   hipStream_t stream = (hipStream_t)stream_;
 #define PCP_SPCONV(CI_, CO_, V_)                                                                                                                \
-  hipLaunchKernelGGL((k_spconv3d<CI_, CO_, V_>), dim3((unsigned)blocks), dim3(256), 0, stream, features, (int)cin, (int)ld_in, nbr, (int)num_offsets, \
-                     (long long)n_out, w_packed, bias, residual, (int)relu, out)
+  hipLaunchKernelGGL((k_spconv3d<CI_, CO_, V_, DEV>), dim3((unsigned)blocks), dim3(256), 0, stream, features, (int)cin, (int)ld_in, nbr,           \
+                     (int)num_offsets, (long long)n_out, w_packed, bias, residual, (int)relu, out, (const int *)n_dev, (long long)ld_nbr)
   if (cin_pad == 16 && cout == 16) { if (vec) PCP_SPCONV(1, 1, true); else PCP_SPCONV(1, 1, false); }
   else if (cin_pad == 16 && cout == 32) { if (vec) PCP_SPCONV(1, 2, true); else PCP_SPCONV(1, 2, false); }
   else if (cin_pad == 32 && cout == 16) PCP_SPCONV(2, 1, true);
@@ -665,8 +810,23 @@ extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, in
   return PCP_OK;
 }
 
-extern "C" int pcp_spconv_dense(const float *features, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w,
-                                const void *table, size_t table_bytes, const int32_t *perm, float *out, void *stream_) {
+extern "C" int pcp_spconv3d(const float *features, int64_t n_in, int32_t cin, int32_t ld_in, const int32_t *nbr, int32_t num_offsets, int64_t n_out,
+                            const float *w_packed, const float *bias, const float *residual, int32_t relu, int32_t cout, float *out,
+                            void *stream_) {
+  return spconv3d<false>(features, n_in, cin, ld_in, nbr, n_out, num_offsets, n_out, nullptr, w_packed, bias, residual, relu, cout, out, stream_);
+}
+
+extern "C" int pcp_spconv3d_dev(const float *features, int64_t in_capacity, int32_t cin, int32_t ld_in, const int32_t *nbr, int64_t ld_nbr,
+                                int32_t num_offsets, const int32_t *n_dev, int64_t capacity, const float *w_packed, const float *bias,
+                                const float *residual, int32_t relu, int32_t cout, float *out, void *stream_) {
+  if (!n_dev || ld_nbr < capacity) return PCP_ERR_ARG;
+  return spconv3d<true>(features, in_capacity, cin, ld_in, nbr, ld_nbr, num_offsets, capacity, n_dev, w_packed, bias, residual, relu, cout, out,
+                        stream_);
+}
+
+template <bool LIM>
+static int spconv_dense(const float *features, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w, const void *table,
+                        size_t table_bytes, const int32_t *perm, float *out, void *stream_) {
   const SpShape s{batch, d, h, w};
   if (!sp_shape_ok(s) || n < 0 || channels < 1 || !table || !out || (n > 0 && !features)) return PCP_ERR_ARG;
   if (d > PCP_MEAN_VFE_MAX_NZ) return PCP_ERR_UNSUPPORTED;
@@ -675,8 +835,18 @@ extern "C" int pcp_spconv_dense(const float *features, int64_t n, int32_t channe
   const long long pixels = (long long)batch * h * w;
   if (pixels >= (1LL << 31)) return PCP_ERR_UNSUPPORTED;
   const SpTable t = sp_table(const_cast<void *>(table), s);
-  hipLaunchKernelGGL(k_sp_dense, dim3((unsigned)pixels), dim3(256), 0, (hipStream_t)stream_, features, (int)channels, s, (const u64 *)t.bits,
-                     (const int *)t.prefix, perm, out);
+  hipLaunchKernelGGL(k_sp_dense<LIM>, dim3((unsigned)pixels), dim3(256), 0, (hipStream_t)stream_, features, (int)channels, s, (const u64 *)t.bits,
+                     (const int *)t.prefix, perm, out, (long long)n);
   PCP_CHECK_LAUNCH();
   return PCP_OK;
+}
+
+extern "C" int pcp_spconv_dense(const float *features, int64_t n, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w,
+                                const void *table, size_t table_bytes, const int32_t *perm, float *out, void *stream_) {
+  return spconv_dense<false>(features, n, channels, batch, d, h, w, table, table_bytes, perm, out, stream_);
+}
+
+extern "C" int pcp_spconv_dense_below(const float *features, int64_t capacity, int32_t channels, int32_t batch, int32_t d, int32_t h, int32_t w,
+                                      const void *table, size_t table_bytes, const int32_t *perm, float *out, void *stream_) {
+  return spconv_dense<true>(features, capacity, channels, batch, d, h, w, table, table_bytes, perm, out, stream_);
 }

@@ -7,6 +7,13 @@ conv_out.0.weight), so a published SECOND checkpoint loads by name.
 Every conv runs with its BatchNorm (and its own bias) folded and its ReLU / residual add in the kernel's epilogue: 21 conv launches per forward.
 The submanifold layers of one stage share one neighbour table (`subm1` and `res1` have the same sites); each of the four strided layers
 reads its output row count back once.
+
+MODEL.BACKBONE_3D.DEVICE_COUNTS (opt-in, with MODEL.VFE.DEVICE_COUNTS): no read-back.  Every level's row count stays on the device and its
+launches and buffers are sized by a capacity: the input's row count for the voxels, the exact bound min(capacity_in * prod(ceil(k / s)),
+output sites) for a strided layer, or the entry of the optional ROW_CAPACITY list (level 0 = voxels, 1 .. 4 = spconv2, spconv3, spconv4,
+spconv_down2; a null entry keeps the bound).  A level that holds more rows than its ROW_CAPACITY drops its tail and sets a bit of
+batch_dict['_pcp_dev_status'], which the forward's final read turns into a RuntimeError.  The buffers belong to the module (one set per model
+replica): a forward overwrites the previous forward's sparse tensors.
 """
 from functools import partial
 
@@ -98,6 +105,16 @@ class VoxelResBackBone8x(nn.Module):
         self.backbone_channels = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': 128}
         self.hip_train = bool(self.model_cfg.get('HIP_TRAIN', False))         # opt-in: the HIP training path (second_train_path.py)
         self._pcp_train = None
+        self.device_counts = bool(self.model_cfg.get('DEVICE_COUNTS', False))
+        cap = self.model_cfg.get('ROW_CAPACITY', None)
+        self.row_capacity = None if cap is None else [None if v is None else int(v) for v in cap]
+        if self.device_counts and self.hip_train:
+            raise NotImplementedError('MODEL.BACKBONE_3D: DEVICE_COUNTS is an inference form; it cannot be combined with HIP_TRAIN')
+        if self.row_capacity is not None and not self.device_counts:
+            raise ValueError('MODEL.BACKBONE_3D.ROW_CAPACITY belongs to DEVICE_COUNTS True')
+        if self.row_capacity is not None and (len(self.row_capacity) != 5 or any(v is not None and v < 1 for v in self.row_capacity)):
+            raise ValueError('MODEL.BACKBONE_3D.ROW_CAPACITY: five entries (voxels, spconv2, spconv3, spconv4, spconv_down2), each null or >= 1')
+        self._dev_bufs = spconv.ops.DevBuffers()
 
     def train(self, mode=True):
         if mode and not self.hip_train:
@@ -128,6 +145,16 @@ class VoxelResBackBone8x(nn.Module):
         x = spconv.SparseConvTensor(features=feats.float().contiguous(), indices=coords.int().contiguous(), spatial_shape=self.sparse_shape,
                                     batch_size=batch_dict['batch_size'])
         x.trusted_indices = bool(batch_dict.get('_pcp_voxels_trusted', False))
+        dev = None
+        if self.device_counts:
+            if batch_dict.get('_pcp_voxel_count', None) is None or not x.trusted_indices:
+                raise RuntimeError('VoxelResBackBone8x with DEVICE_COUNTS needs the voxels of a DynMeanVFE built with DEVICE_COUNTS '
+                                   '(a device-side count, distinct sites inside the grid)')
+            dev = spconv.DeviceCounts(batch_dict['_pcp_dev_status'], self._dev_bufs, self.row_capacity, input_capacity=int(coords.shape[0]))
+            if dev.capacity_of(0) is not None and dev.capacity_of(0) < int(coords.shape[0]):
+                raise RuntimeError('sparse backbone: %d voxel rows exceed ROW_CAPACITY[0] = %d' % (int(coords.shape[0]), dev.capacity_of(0)))
+            x.with_device_count(batch_dict['_pcp_voxel_count'], dev)
+            batch_dict['_pcp_dev_levels'] = dev.levels
         x = self.conv_input(x)
         x_conv1 = self.conv1(x)
         x_conv2 = self.conv2(x_conv1)

@@ -1,7 +1,12 @@
 """DynMeanVFE on gfx950 (pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py of the reference): the mean of every point column per voxel of the 3D
 grid, voxels in ascending merged id (what torch.unique returns), on pcp_mean_vfe -- no sort, no float atomics.  No parameters.  Inference only
 unless the model config sets MODEL.VFE.HIP_TRAIN: then train() is allowed, the forward is the same and its backward closure returns None (the
-points carry no gradient)."""
+points carry no gradient).
+
+MODEL.VFE.DEVICE_COUNTS (opt-in, with MODEL.BACKBONE_3D.DEVICE_COUNTS): the forward reads nothing back.  `voxel_features` / `voxel_coords` then
+hold max(N, 1) rows, the voxel count stays on the device (batch_dict['_pcp_voxel_count']) and the error word (frames out of order) travels in
+batch_dict['_pcp_dev_status'] to the forward's final read, which raises the same ValueError.  The buffers belong to the module (one set per
+model replica) and are overwritten by its next forward."""
 import torch
 
 from pcp_amd import ops
@@ -23,6 +28,10 @@ class DynamicMeanVFE(VFETemplate):
         self.point_cloud_range = [float(v) for v in point_cloud_range]
         self._workspace = None
         self.hip_train = bool(self.model_cfg.get('HIP_TRAIN', False))
+        self.device_counts = bool(self.model_cfg.get('DEVICE_COUNTS', False))
+        if self.device_counts and self.hip_train:
+            raise NotImplementedError('MODEL.VFE: DEVICE_COUNTS is an inference form; it cannot be combined with HIP_TRAIN')
+        self._dev_bufs = ops.DevBuffers()
 
     def get_output_feature_dim(self):
         return self.num_raw_point_features
@@ -49,6 +58,11 @@ class DynamicMeanVFE(VFETemplate):
             batch_size = int(points[:, 0].max().item()) + 1 if points.shape[0] else 1
             batch_dict['batch_size'] = batch_size
         grid = ops.make_grid(self.point_cloud_range, self.voxel_size, self.grid_size, int(batch_size))
+        if self.device_counts:
+            feats, coords, status = ops.mean_vfe_dev(points, grid, self.num_raw_point_features, nz=self.grid_size[2], bufs=self._dev_bufs)
+            batch_dict.update({'voxel_features': feats, 'voxel_coords': coords, '_pcp_voxels_trusted': True, '_pcp_voxel_count': status[0:1],
+                               '_pcp_dev_status': status})
+            return batch_dict
         feats, coords, _ = ops.mean_vfe(points, grid, self.num_raw_point_features, nz=self.grid_size[2], workspace=self._workspace)
         batch_dict['voxel_features'] = feats
         batch_dict['voxel_coords'] = coords

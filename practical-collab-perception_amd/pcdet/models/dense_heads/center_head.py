@@ -212,11 +212,17 @@ class CenterHead(PackedModule):
             per_head.append((boxes, scores, labels, keep, kcnt, idx) if vel is None else (boxes, scores, labels, keep, kcnt, idx, vel))
         return per_head
 
-    def finalize(self, per_head, batch_size):
+    def finalize(self, per_head, batch_size, dev_status=None, dev_levels=None):
         """one gather launch for all frames and heads (boxes[keep], scores[keep], class_id_mapping[labels[keep]] + 1, concatenated over
-        heads: reference :335-357), then the one host sync of the path: how many boxes survive per frame -> exact-shape views."""
+        heads: reference :335-357), then the one host sync of the path: how many boxes survive per frame -> exact-shape views.
+        dev_status: the status words of a device-count SECOND forward, read in the same copy and examined first."""
         ob, os_, ol, cnt = self.gather_pending(per_head, batch_size)
-        counts = cnt.cpu().numpy()
+        if dev_status is not None:
+            both = torch.cat([cnt.reshape(-1).to(torch.int32), dev_status.reshape(-1)]).cpu().numpy()
+            ops.dev_status_check(both[batch_size:], batch_size, dev_levels)
+            counts = both[:batch_size]
+        else:
+            counts = cnt.cpu().numpy()
         return [dict(pred_boxes=ob[b, :int(counts[b])], pred_scores=os_[b, :int(counts[b])], pred_labels=ol[b, :int(counts[b])])
                 for b in range(batch_size)]
 
@@ -239,8 +245,8 @@ class CenterHead(PackedModule):
             return ops.gather_detections_ext(heads, batch_size)
         return ops.gather_detections(heads, batch_size)
 
-    def generate_predicted_boxes(self, batch_size, head_bufs, pk):
-        return self.finalize(self.device_postprocess(head_bufs, pk), batch_size)
+    def generate_predicted_boxes(self, batch_size, head_bufs, pk, dev_status=None, dev_levels=None):
+        return self.finalize(self.device_postprocess(head_bufs, pk), batch_size, dev_status, dev_levels)
 
     @staticmethod
     def _pred_dict(buf, names, starts, outs):
@@ -259,7 +265,8 @@ class CenterHead(PackedModule):
         if getattr(self, 'defer_finalize', False):                   # graph capture: keep the host sync outside
             data_dict['_pcp_pending_head'] = self.device_postprocess(head_bufs, pk)
             return data_dict
-        final = self.generate_predicted_boxes(data_dict['batch_size'], head_bufs, pk)
+        final = self.generate_predicted_boxes(data_dict['batch_size'], head_bufs, pk, data_dict.get('_pcp_dev_status', None),
+                                              data_dict.get('_pcp_dev_levels', None))
         data_dict['final_box_dicts'] = final
         if self.model_cfg.get('GENERATING_EXCHANGE_DATA', False) or self.model_cfg.get('RETURN_MODAR_POINTS', False):
             # MoDAR "points": the wire / on-disk format that feeds config 3 (reference :409-427)

@@ -72,9 +72,19 @@ class Detector3DTemplate(nn.Module):
     def build_bev_maker_early(self, model_info_dict):
         return self._build_bev_maker('BEV_MAKER_EARLY', model_info_dict)
 
+    def _check_device_counts(self):
+        """MODEL.VFE.DEVICE_COUNTS and MODEL.BACKBONE_3D.DEVICE_COUNTS select one form of the SECOND front end together"""
+        vfe_cfg, b3d_cfg = self.model_cfg.get('VFE', None), self.model_cfg.get('BACKBONE_3D', None)
+        a = bool(vfe_cfg.get('DEVICE_COUNTS', False)) if vfe_cfg is not None else False
+        b = bool(b3d_cfg.get('DEVICE_COUNTS', False)) if b3d_cfg is not None else False
+        if a != b:
+            raise ValueError('MODEL.VFE.DEVICE_COUNTS is %s and MODEL.BACKBONE_3D.DEVICE_COUNTS is %s: the device-count form needs both '
+                             '(the backbone reads the voxel count the VFE leaves on the device)' % (a, b))
+
     def build_vfe(self, model_info_dict):
         if self.model_cfg.get('VFE', None) is None:
             return None, model_info_dict
+        self._check_device_counts()
         module = vfe.__all__[self.model_cfg.VFE.NAME](
             model_cfg=self.model_cfg.VFE, num_point_features=model_info_dict['num_rawpoint_features'],
             point_cloud_range=model_info_dict['point_cloud_range'], voxel_size=model_info_dict['voxel_size'],
@@ -144,6 +154,7 @@ class Detector3DTemplate(nn.Module):
             return None, model_info_dict
         if self.model_cfg.BACKBONE_3D.NAME not in backbones_3d.__all__:
             return self._off_path('BACKBONE_3D', model_info_dict)
+        self._check_device_counts()
         module = backbones_3d.__all__[self.model_cfg.BACKBONE_3D.NAME](
             model_cfg=self.model_cfg.BACKBONE_3D, input_channels=model_info_dict['num_point_features'],
             grid_size=model_info_dict['grid_size'], voxel_size=model_info_dict['voxel_size'],

@@ -111,8 +111,13 @@ class PipelinedDetector:
 
     @staticmethod
     def _sparse_backbone(model):
-        # VoxelResBackBone8x reads the row count of each strided sparse conv back (and DynMeanVFE its voxel count) in the middle of the forward
-        return any(type(m).__name__ == 'VoxelResBackBone8x' for m in model.modules())
+        # VoxelResBackBone8x reads the row count of each strided sparse conv back (and DynMeanVFE its voxel count) in the middle of the forward,
+        # unless it was built with DEVICE_COUNTS
+        return any(type(m).__name__ == 'VoxelResBackBone8x' and not getattr(m, 'device_counts', False) for m in model.modules())
+
+    @staticmethod
+    def _device_count_backbone(model):
+        return any(type(m).__name__ == 'VoxelResBackBone8x' and getattr(m, 'device_counts', False) for m in model.modules())
 
     @staticmethod
     def _head_writes_exchange_data(head):
@@ -145,6 +150,8 @@ class PipelinedDetector:
             raise NotImplementedError('PipelinedDetector: VoxelResBackBone8x (every strided sparse conv reads its row count back) runs batch by batch')
         if self._head_writes_exchange_data(model.dense_head):
             raise NotImplementedError('PipelinedDetector: a head that writes exchange data (MoDAR) runs batch by batch')
+        if graph and self._device_count_backbone(model):
+            raise NotImplementedError('PipelinedDetector: graph capture of the device-count sparse backbone is not built; use graph=False')
         self.model = model
         self.models = [model]
         if replicas > 1:
@@ -237,8 +244,17 @@ class PipelinedDetector:
             if ev is None:
                 self._events = [torch.cuda.Event(blocking=True), torch.cuda.Event(blocking=True)]
                 ev = self._events[self._n & 1]
+            status = bd.get('_pcp_dev_status', None)
+            status_host = None
+            if status is not None:
+                # the status words of a device-count SECOND forward ride behind the counts: read at the same event
+                skey = ('status', tuple(status.shape))
+                if skey not in self._pinned:
+                    self._pinned[skey] = [torch.empty(status.shape, dtype=status.dtype, pin_memory=True) for _ in range(2)]
+                status_host = self._pinned[skey][(self._n - 1) & 1]
+                status_host.copy_(status, non_blocking=True)
             ev.record(main)
-        prev, self._pending = self._pending, (ob, os_, ol, counts_host, ev, batch_size, False)
+        prev, self._pending = self._pending, (ob, os_, ol, counts_host, ev, batch_size, False, status_host, bd.get('_pcp_dev_levels', None))
         return self._finish(prev)
 
     # ---- graph mode ---------------------------------------------------------------------------------------------------------------------
@@ -347,8 +363,10 @@ class PipelinedDetector:
     def _finish(cls, p):
         if p is None:
             return None
-        ob, os_, ol, counts_host, ev, batch_size, static = p
+        ob, os_, ol, counts_host, ev, batch_size, static = p[:7]
         cls._wait(ev)
+        if len(p) > 7 and p[7] is not None:
+            ops.dev_status_check(p[7].numpy().copy(), batch_size, p[8])
         cur = torch.cuda.current_stream()
         if static:
             # graph mode: copies, queued on the caller's stream now (the data are complete: the event was waited for) -- the replica's next

@@ -64,7 +64,7 @@ class _SpConvBN:
             osp = list(x.spatial_shape) if conv.subm else list(ops.spconv_out_shape(x.spatial_shape, conv.kernel_size, conv.stride, conv.padding))
             oc, nbr, ot = _empty((0, 4), dev, torch.int32), None, None
         else:
-            oc, osp, nbr, ot = conv.indices_of(x)
+            oc, osp, nbr, ot = conv.indices_of(x)[:4]
         n_out = int(oc.shape[0])
         if n_out == 0:
             self.saved = None

@@ -1259,6 +1259,7 @@ class SpconvTable:
 
     def __init__(self, shape4, mem, perm):
         self.shape4, self.mem, self.perm = tuple(int(v) for v in shape4), mem, perm
+        self.capacity = None                  # set by the device-count forms: the rows the set's buffers hold
 
 
 def _spconv_table_mem(shape4, dev):
@@ -1383,6 +1384,195 @@ def spconv_dense(features, table):
         raise NotImplementedError('pcp_spconv_dense: at most %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, D))
     n, C = int(features.shape[0]), int(features.shape[1])
     out = torch.empty((B, H, W, C * D), dtype=torch.float32, device=features.device)
+    if table.capacity is not None:
+        # a table of the device-count forms: a site whose row lies at or past the capacity (a dropped tail) reads as empty
+        assert n == table.capacity, (n, table.capacity)
+        check(_lib.load().pcp_spconv_dense_below(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()),
+              'pcp_spconv_dense_below')
+        return out
     check(_lib.load().pcp_spconv_dense(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()),
           'pcp_spconv_dense')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the SECOND family without a host read in the middle of the forward: the device-count forms (include/pcp_hip.h, `_dev`)
+# ---------------------------------------------------------------------------------------------------------------------
+# the status words of one forward, read once at its end: [0 .. 3] pcp_mean_vfe's counters (M, error word, rows kept), [4] bit L set: level L
+# of the sparse backbone held more rows than its capacity
+DEV_STATUS_WORDS = 8
+DEV_STATUS_OVERFLOW = 4
+
+
+class DevBuffers:
+    """grow-only device buffers of one model replica, by name: a steady-state forward allocates nothing of a data-dependent size.  A deep
+    copy starts empty (every replica of a PipelinedDetector owns its buffers)."""
+
+    def __init__(self):
+        self._t = {}
+
+    def __deepcopy__(self, memo):
+        return DevBuffers()
+
+    def get(self, name, shape, dtype, device):
+        need = 1
+        for v in shape:
+            need *= int(v)
+        t = self._t.get(name)
+        if t is None or t.numel() < need or t.dtype != dtype or t.device != device:
+            t = self._t[name] = torch.empty(max(need, 1), dtype=dtype, device=device)
+        return t[:need].view(*shape)
+
+
+def _buf(bufs, name, shape, dtype, device):
+    if bufs is None:
+        return torch.empty(tuple(int(v) for v in shape), dtype=dtype, device=device)
+    return bufs.get(name, shape, dtype, device)
+
+
+def mean_vfe_dev(points, grid, num_features, *, nz, bufs=None):
+    """mean_vfe without its host read.  Returns voxel_features (cap, num_features), voxel_coords (cap, 4) with cap = max(N, 1) rows, of
+    which the first M are written, and the (DEV_STATUS_WORDS,) int32 status tensor: status[0:1] is M on the device, status[1] the error word
+    (dev_status_check raises on it at the forward's final read)."""
+    _need_cuda(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
+        raise ValueError('mean_vfe: points must be a contiguous (N, 1 + C) float32 tensor, got %s %s' % (tuple(points.shape), points.dtype))
+    n, stride = int(points.shape[0]), int(points.shape[1])
+    C, B, nz = int(num_features), int(grid.batch_size), int(nz)
+    if not MEAN_VFE_MIN_FEATURES <= C <= MEAN_VFE_MAX_FEATURES:
+        raise ValueError('mean_vfe: %d to %d feature columns behind the frame index, got %d' % (MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, C))
+    if stride < 1 + C:
+        raise ValueError('mean_vfe: rows of %d columns cannot hold the frame index and %d features' % (stride, C))
+    if not 1 <= B <= MEAN_VFE_MAX_BATCH:
+        raise ValueError('mean_vfe: at most %d frames per call, got %d' % (MEAN_VFE_MAX_BATCH, B))
+    if not 1 <= nz <= MEAN_VFE_MAX_NZ:
+        raise ValueError('mean_vfe: 1 to %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, nz))
+    L = _lib.load()
+    dev = points.device
+    need = L.pcp_mean_vfe_workspace_bytes(ctypes.byref(grid), n)
+    if need == 0:
+        raise _lib.PcpError('pcp_mean_vfe: unsupported grid')
+    cap = max(n, 1)
+    workspace = _buf(bufs, 'mv_ws', (need,), torch.uint8, dev)
+    coords = _buf(bufs, 'mv_coords', (cap, 4), torch.int32, dev)
+    feats = _buf(bufs, 'mv_feats', (cap, C), torch.float32, dev)
+    status = torch.zeros((DEV_STATUS_WORDS,), dtype=torch.int32, device=dev)
+    check(L.pcp_mean_vfe(_p(points), n, stride, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(coords), _p(status), _stream()),
+          'pcp_mean_vfe')
+    check(L.pcp_mean_vfe_features_dev(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(status), n, _p(feats),
+                                      _stream()), 'pcp_mean_vfe_features_dev')
+    return feats, coords, status
+
+
+def dev_status_check(words, batch_size, levels=None):
+    """words: the status tensor's values on the host (the forward's final read).  ValueError for the mean VFE's error word (as mean_vfe
+    raises it), RuntimeError for a sparse level that held more rows than its ROW_CAPACITY; levels: [(name, capacity)] by bit."""
+    words = [int(v) for v in words]
+    err, over = words[1], words[DEV_STATUS_OVERFLOW]
+    if err:
+        raise ValueError('mean_vfe: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (int(batch_size), err))
+    if over:
+        hit = [i for i in range(31) if over >> i & 1]
+        names = ', '.join('level %d (%s, ROW_CAPACITY %d)' % ((i,) + tuple(levels[i])) if levels and i < len(levels) else 'level %d' % i for i in hit)
+        raise RuntimeError('sparse backbone: more rows than the capacity at %s; the rows behind it were dropped (overflow word %d)' % (names, over))
+
+
+def spconv_table_dev(coords, n_dev, batch_size, spatial_shape, bufs=None):
+    """spconv_table of the first *n_dev rows of the capacity-sized coords; the sites must be distinct and inside the grid (mean_vfe_dev's
+    are): nothing is read back to check"""
+    _need_cuda(coords, n_dev)
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4 or not coords.is_contiguous():
+        raise ValueError('sparse conv tables: indices must be a contiguous (N, 4) int32 tensor, got %s %s' % (tuple(coords.shape), coords.dtype))
+    shape4 = (int(batch_size),) + tuple(int(v) for v in spatial_shape)
+    cap, dev = int(coords.shape[0]), coords.device
+    need = _lib.load().pcp_spconv_table_bytes(*shape4)
+    if need == 0:
+        raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % (tuple(shape4),))
+    mem = _buf(bufs, 'table0', (need,), torch.uint8, dev)
+    perm = _buf(bufs, 'perm0', (max(cap, 1),), torch.int32, dev)
+    counters = torch.empty((4,), dtype=torch.int32, device=dev)
+    check(_lib.load().pcp_spconv_table_build_dev(_p(coords), _p(n_dev), cap, *shape4, _p(mem), mem.numel(), _p(perm), _p(counters), _stream()),
+          'pcp_spconv_table_build_dev')
+    t = SpconvTable(shape4, mem, perm)
+    t.capacity = cap
+    return t
+
+
+def spconv_build_subm_dev(coords, table, n_dev, bufs=None, name='subm'):
+    """neighbour table (27, cap) of the first *n_dev rows: entry [k][row] at k * cap + row"""
+    cap = int(coords.shape[0])
+    nbr = _buf(bufs, 'nbr_' + name, (27, cap), torch.int32, coords.device)
+    check(_lib.load().pcp_spconv_build_subm_dev(_p(coords), _p(n_dev), cap, *table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), _p(nbr),
+                                                _stream()), 'pcp_spconv_build_subm_dev')
+    return nbr
+
+
+def spconv_strided_bound(capacity_in, kernel, stride, out_shape4):
+    """the most output rows capacity_in input rows can reach: an input touches at most ceil(k / s) output positions per axis"""
+    k, s = _i3(kernel), _i3(stride)
+    reach = 1
+    for a in range(3):
+        reach *= -(-k[a] // s[a])
+    sites = 1
+    for v in out_shape4:
+        sites *= int(v)
+    return max(min(int(capacity_in) * reach, sites), 1)
+
+
+def spconv_build_strided_dev(coords, table, n_dev, kernel, stride, padding, capacity=None, status=None, level=0, bufs=None, name='spconv'):
+    """spconv_build_strided without its host read -> (out_coords (cap, 4), nbr (K, cap), out_table, n_out_dev).  cap: `capacity`, or the exact
+    bound (spconv_strided_bound), which cannot overflow.  More rows than cap: the tail of the ascending linear order is dropped and bit
+    `level` of status[DEV_STATUS_OVERFLOW] is set."""
+    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
+    for what, v, lo, hi in (('kernel', k, 1, 3), ('stride', s, 1, 3), ('padding', p, 0, 2)):
+        if not all(lo <= x <= hi for x in v):
+            raise NotImplementedError('sparse conv: %s %s outside [%d, %d]' % (what, tuple(v), lo, hi))
+    B = table.shape4[0]
+    out_sp = spconv_out_shape(table.shape4[1:], k, s, p)
+    if min(out_sp) < 1:
+        raise ValueError('sparse conv: kernel %s stride %s padding %s leaves no output on the grid %s' % (k, s, p, table.shape4[1:]))
+    L = _lib.load()
+    dev = coords.device
+    cap_in = int(coords.shape[0])
+    bound = spconv_strided_bound(cap_in, k, s, (B,) + out_sp)
+    cap = bound if capacity is None else max(min(int(capacity), bound), 1)
+    need = L.pcp_spconv_table_bytes(B, *out_sp)
+    if need == 0:
+        raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % ((B,) + out_sp,))
+    out_mem = _buf(bufs, 'table_' + name, (need,), torch.uint8, dev)
+    counters = torch.empty((4,), dtype=torch.int32, device=dev)
+    err = status[DEV_STATUS_OVERFLOW:] if status is not None else None
+    k3, s3, p3 = (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*s), (ctypes.c_int32 * 3)(*p)
+    check(L.pcp_spconv_strided_sites_dev(_p(coords), _p(n_dev), cap_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), cap, _p(counters),
+                                         _p(err), 1 << int(level), _stream()), 'pcp_spconv_strided_sites_dev')
+    K = k[0] * k[1] * k[2]
+    out_coords = _buf(bufs, 'coords_' + name, (cap, 4), torch.int32, dev)
+    nbr = _buf(bufs, 'nbr_' + name, (K, cap), torch.int32, dev)
+    check(L.pcp_spconv_build_strided_dev(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), cap_in, k3, s3, p3, _p(out_mem),
+                                         out_mem.numel(), _p(counters), cap, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided_dev')
+    ot = SpconvTable((B,) + out_sp, out_mem, None)
+    ot.capacity = cap
+    return out_coords, nbr, ot, counters[0:1]
+
+
+def spconv3d_dev(features, nbr, n_dev, w_packed, bias, residual=None, relu=False, bufs=None, name='conv'):
+    """spconv3d over the first *n_dev output rows of a (K, cap) neighbour table; out (cap, Cout), rows at or past the count not written"""
+    _need_cuda(features, nbr, w_packed, bias, residual, n_dev)
+    _need_f32('pcp_spconv3d_dev', features, w_packed, bias, residual)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise _lib.PcpError('pcp_spconv3d_dev reads an int32 (K, capacity) neighbour table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
+    for t in (nbr, w_packed, bias, residual):
+        assert t is None or t.is_contiguous()
+    assert features.dim() == 2 and features.stride(1) == 1
+    n_in, cin, ld_in = int(features.shape[0]), int(features.shape[1]), int(features.stride(0)) if features.shape[0] > 1 else int(features.shape[1])
+    K, cap = int(nbr.shape[0]), int(nbr.shape[1])
+    cout, cin_pad = int(w_packed.shape[1]), int(w_packed.shape[2])
+    if cin < 3 or (16 if cin <= 16 else cin) != cin_pad or (cin_pad, cout) not in SPCONV_CHANNEL_PAIRS:
+        raise NotImplementedError('pcp_spconv3d: the channel pair (Cin, Cout) = (%d, %d) has no kernel; supported: Cin 3..16 -> 16, and %s'
+                                  % (cin, cout, ', '.join('%d -> %d' % p for p in SPCONV_CHANNEL_PAIRS)))
+    assert int(w_packed.shape[0]) == K and tuple(bias.shape) == (cout,), (tuple(w_packed.shape), K, tuple(bias.shape))
+    assert residual is None or tuple(residual.shape) == (cap, cout)
+    out = _buf(bufs, 'feat_' + name, (cap, cout), torch.float32, features.device)
+    check(_lib.load().pcp_spconv3d_dev(_p(features), n_in, cin, ld_in, _p(nbr), cap, K, _p(n_dev), cap, _p(w_packed), _p(bias), _p(residual),
+                                       1 if relu else 0, cout, _p(out), _stream()), 'pcp_spconv3d_dev')
     return out

@@ -22,13 +22,29 @@ class SparseConvTensor:
         self._table = table                   # ops.SpconvTable of `indices`, built on first use
         self.indice_dict = indice_dict if indice_dict is not None else {}
         self.trusted_indices = False          # set by a producer that guarantees distinct in-range sites (no read-back to validate)
+        # the device-count form (ops.*_dev): `features` / `indices` hold `capacity` rows of which the first *n_dev are real; `dev` is what
+        # the layers share over one forward (status words, the replica's buffers, per-level capacities)
+        self.n_dev = None
+        self.dev = None
+
+    @property
+    def capacity(self):
+        return int(self.indices.shape[0]) if self.n_dev is not None else None
+
+    def with_device_count(self, n_dev, dev):
+        self.n_dev, self.dev = n_dev, dev
+        self.trusted_indices = True
+        return self
 
     def replace_feature(self, new_features):
         out = SparseConvTensor(new_features, self.indices, self.spatial_shape, self.batch_size, self._table, self.indice_dict)
         out.trusted_indices = self.trusted_indices
+        out.n_dev, out.dev = self.n_dev, self.dev
         return out
 
     def table(self):
+        if self._table is None and self.n_dev is not None:
+            self._table = ops.spconv_table_dev(self.indices, self.n_dev, self.batch_size, self.spatial_shape, bufs=self.dev.bufs)
         if self._table is None:
             idx = self.indices if self.indices.dtype == torch.int32 and self.indices.is_contiguous() else self.indices.int().contiguous()
             self._table = ops.spconv_table(idx, self.batch_size, self.spatial_shape, check_input=not self.trusted_indices)
@@ -43,6 +59,24 @@ class SparseConvTensor:
         B, (D, H, W), C = self.batch_size, self.spatial_shape, int(self.features.shape[1])
         x = self.dense_nhwc().view(B, H, W, C, D).permute(0, 3, 4, 1, 2)
         return x if channels_first else x.permute(0, 2, 3, 4, 1)
+
+
+class DeviceCounts:
+    """what the layers of one device-count forward share: the status words the forward's final read examines, the replica's grow-only
+    buffers, the optional per-level row capacities (level 0 = the input voxels, level L = the output of the L-th strided layer; None: the
+    exact bound) and, filled as the forward goes, the (name, capacity) of every level for the overflow message"""
+
+    def __init__(self, status, bufs=None, row_capacity=None, input_capacity=0):
+        self.status, self.bufs = status, bufs
+        self.row_capacity = list(row_capacity) if row_capacity is not None else None
+        self.level = 0
+        self.convs = 0
+        self.levels = [('voxels', int(input_capacity))]
+
+    def capacity_of(self, level):
+        if self.row_capacity is None or level >= len(self.row_capacity) or self.row_capacity[level] is None:
+            return None
+        return int(self.row_capacity[level])
 
 
 class SparseModule(nn.Module):
@@ -75,21 +109,34 @@ class SparseConvolution(SparseModule):
             self.register_parameter('bias', None)
 
     def indices_of(self, x):
-        """-> (out_indices, out_spatial_shape, nbr, out_table)"""
+        """-> (out_indices, out_spatial_shape, nbr, out_table, n_out_dev); n_out_dev None in the host-count form"""
+        dev = x.dev if x.n_dev is not None else None
         if self.subm:
             hit = x.indice_dict.get(('subm', id(x.indices)))
             if hit is None or hit[0] is not x.indices:
-                hit = (x.indices, ops.spconv_build_subm(x.indices, x.table()))
+                if dev is not None:
+                    nbr = ops.spconv_build_subm_dev(x.indices, x.table(), x.n_dev, bufs=dev.bufs, name='subm%d' % dev.level)
+                else:
+                    nbr = ops.spconv_build_subm(x.indices, x.table())
+                hit = (x.indices, nbr)
                 x.indice_dict[('subm', id(x.indices))] = hit
-            return x.indices, x.spatial_shape, hit[1], x.table()
+            return x.indices, x.spatial_shape, hit[1], x.table(), x.n_dev
         key = self.indice_key if self.indice_key is not None else ('anon', id(self))
         hit = x.indice_dict.get(key)
         if hit is None or hit[0] is not x.indices:
-            oc, nbr, ot = ops.spconv_build_strided(x.indices, x.table(), self.kernel_size, self.stride, self.padding)
-            hit = (x.indices, oc, nbr, ot)
+            if dev is not None:
+                dev.level += 1
+                oc, nbr, ot, n_out = ops.spconv_build_strided_dev(x.indices, x.table(), x.n_dev, self.kernel_size, self.stride, self.padding,
+                                                                  capacity=dev.capacity_of(dev.level), status=dev.status, level=dev.level,
+                                                                  bufs=dev.bufs, name='strided%d' % dev.level)
+                dev.levels.append((str(key), int(oc.shape[0])))
+            else:
+                oc, nbr, ot = ops.spconv_build_strided(x.indices, x.table(), self.kernel_size, self.stride, self.padding)
+                n_out = None
+            hit = (x.indices, oc, nbr, ot, n_out)
             x.indice_dict[key] = hit
-        _, oc, nbr, ot = hit
-        return oc, list(ot.shape4[1:]), nbr, ot
+        _, oc, nbr, ot, n_out = hit
+        return oc, list(ot.shape4[1:]), nbr, ot, n_out
 
     def packed_weight(self, bn=None):
         """[K][Cout][cin_pad] weights and (Cout,) bias with `bn` (eval BatchNorm1d) and the conv's own bias folded"""
@@ -106,10 +153,16 @@ class SparseConvolution(SparseModule):
             raise TypeError('sparse conv layers take a SparseConvTensor')
         if x.indices.dtype != torch.int32 or not x.indices.is_contiguous():
             x = SparseConvTensor(x.features, x.indices.int().contiguous(), x.spatial_shape, x.batch_size, x._table, x.indice_dict)
-        oc, osp, nbr, ot = self.indices_of(x)
-        f = ops.spconv3d(x.features, nbr, w_packed, bias, residual=residual, relu=relu)
+        oc, osp, nbr, ot, n_out = self.indices_of(x)
+        if n_out is not None:
+            x.dev.convs += 1
+            f = ops.spconv3d_dev(x.features, nbr, n_out, w_packed, bias, residual=residual, relu=relu, bufs=x.dev.bufs, name='conv%d' % x.dev.convs)
+        else:
+            f = ops.spconv3d(x.features, nbr, w_packed, bias, residual=residual, relu=relu)
         out = SparseConvTensor(f, oc, osp, x.batch_size, ot, x.indice_dict)
         out.trusted_indices = True
+        if n_out is not None:
+            out.with_device_count(n_out, x.dev)
         return out
 
     def forward(self, x):

@@ -5,6 +5,12 @@ minimum of 30.
     python tools/bench_spconv.py [--out ../../profiles/spconv_bench.txt]
     python tools/bench_spconv.py --train [--out ../../profiles/spconv_train_bench.txt]
 
+    python tools/bench_spconv.py --devcount [--out ../../profiles/spconv_devcount_bench.txt]
+
+--devcount: the whole model on the B = 1 uniform cloud three ways, in alternating rounds -- batch by batch, the device-count form
+(MODEL.VFE / BACKBONE_3D.DEVICE_COUNTS) batch by batch, and the device-count form through PipelinedDetector(replicas=2) -- with the peak
+allocated bytes of each, then the conv layers of the two forms side by side on the same rows.
+
 --train: one training iteration of the sparse 3D stage (VoxelBackboneTrain + HeightCompression, forward and backward behind a seeded canvas
 gradient) on the B = 1 uniform cloud: every conv forward, BatchNorm, weight-gradient and data-gradient call in order, the sums per kind and
 the whole iteration (3 warm-up iterations, mean and minimum of 10).
@@ -66,7 +72,7 @@ class Recorder:
         return timed
 
 
-def build_model():
+def build_model(device_counts=False):
     from pcdet.config import EasyDict, cfg_from_yaml_file
     from pcdet.datasets import SyntheticV2XDataset
     from pcdet.models import build_network
@@ -77,6 +83,9 @@ def build_model():
     finally:
         os.chdir(cwd)
     cfg.DATA_CONFIG.SYNTHETIC = EasyDict(POINTS_PER_AGENT=1000, NUM_FRAMES=1, DISTRIBUTION='uniform')
+    if device_counts:
+        cfg.MODEL.VFE.DEVICE_COUNTS = True
+        cfg.MODEL.BACKBONE_3D.DEVICE_COUNTS = True
     ds = SyntheticV2XDataset(cfg.DATA_CONFIG, cfg.CLASS_NAMES)
     model = build_network(cfg.MODEL, len(cfg.CLASS_NAMES), ds)
     st = synth.fill_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()})
@@ -183,13 +192,105 @@ def train_main(args):
             f.write(text)
 
 
+DEV_ROUNDS, DEV_BATCHES = 5, 20
+
+
+def _conv_times(model, pts, name):
+    """mean ms of every conv call of one forward form (ops.spconv3d or ops.spconv3d_dev), HIP events, RUNS forwards after WARMUP"""
+    acc, orig = None, getattr(ops, name)
+    calls = []
+
+    def timed(*a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = orig(*a, **k)
+        e1.record()
+        calls.append(('%3d -> %3d K=%2d' % (a[0].shape[1], out.shape[1], a[1].shape[0]), int(a[1].shape[1]), e0, e1))
+        return out
+    setattr(ops, name, timed)
+    try:
+        with torch.no_grad():
+            for it in range(WARMUP + RUNS):
+                del calls[:]
+                model({'points': pts, 'batch_size': 1, 'metadata': [{}]})
+                torch.cuda.synchronize()
+                if it >= WARMUP:
+                    acc = acc or [(label, rows, []) for label, rows, _, _ in calls]
+                    for (_, _, v), (_, _, e0, e1) in zip(acc, calls):
+                        v.append(e0.elapsed_time(e1))
+    finally:
+        setattr(ops, name, orig)
+    return [(label, rows, float(np.mean(v)), float(np.min(v))) for label, rows, v in acc]
+
+
+def devcount_main(args):
+    from pcdet.models.pipelined import PipelinedDetector
+    host, dev, dev_p = build_model(False), build_model(True), build_model(True)
+    pts = make_cloud(1, 'uniform')
+    meta = [{}]
+    pipe = PipelinedDetector(dev_p, replicas=2)
+
+    def run_model(model):
+        for _ in range(DEV_BATCHES):
+            model({'points': pts, 'batch_size': 1, 'metadata': meta})
+
+    def run_pipe():
+        for _ in range(DEV_BATCHES):
+            pipe.submit(pts, 1, meta)
+        pipe.flush()
+    modes = [('batch by batch (host counts)', lambda: run_model(host)), ('device counts, batch by batch', lambda: run_model(dev)),
+             ('device counts, PipelinedDetector(replicas=2)', run_pipe)]
+    ms = {name: [] for name, _ in modes}
+    peak = {}
+    with torch.no_grad():
+        for name, fn in modes:                              # warm-up and peak allocation of each form on its own
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            fn()
+            torch.cuda.synchronize()
+            peak[name] = (torch.cuda.max_memory_allocated(), base)
+        for _ in range(DEV_ROUNDS):                         # alternating rounds
+            for name, fn in modes:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) * 1e3 / DEV_BATCHES)
+    lines = ['v2x_second_ego, whole model, uniform cloud, B = 1, %d rows: ms per batch (wall clock, host included), %d alternating rounds of %d '
+             'batches each' % (pts.shape[0], DEV_ROUNDS, DEV_BATCHES), '']
+    for name, _ in modes:
+        v = ms[name]
+        lines.append('  %-46s mean %7.3f  min %7.3f  max %7.3f   rounds: %s' % (name, np.mean(v), np.min(v), np.max(v), ' '.join('%.3f' % x for x in v)))
+    lines.append('')
+    lines.append('peak allocated bytes during the form\'s first %d batches (allocated before them: all three models and the cloud)' % DEV_BATCHES)
+    for name, _ in modes:
+        lines.append('  %-46s peak %14d   above what was allocated before: %14d' % (name, peak[name][0], peak[name][0] - peak[name][1]))
+    lines.append('')
+    lines.append('conv layers, ms mean (min) of %d forwards: host-count form | device-count form (launch sized by the capacity)' % RUNS)
+    h, d = _conv_times(host, pts, 'spconv3d'), _conv_times(dev, pts, 'spconv3d_dev')
+    th = td = 0.0
+    for (label, rows, hm, hn), (_, cap, dm, dn) in zip(h, d):
+        lines.append('  conv %s rows %8d: %7.3f (%7.3f) | capacity %8d: %7.3f (%7.3f)' % (label, rows, hm, hn, cap, dm, dn))
+        th, td = th + hm, td + dm
+    lines.append('  sum of the 21 convs: %7.3f | %7.3f' % (th, td))
+    text = '\n'.join(lines) + '\n'
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--devcount', action='store_true', help='the whole model three ways: host counts, device counts, device counts pipelined')
     ap.add_argument('--train', action='store_true', help='time one training iteration of the sparse 3D stage instead of the forward')
     args = ap.parse_args()
     if args.train:
         return train_main(args)
+    if args.devcount:
+        return devcount_main(args)
     model = build_model()
     front = [model.vfe, model.backbone_3d, model.map_to_bev_module]
     lines = ['v2x_second_ego on the device, milliseconds: mean (min) of %d after %d warm-up forwards; 6 agents x 60 000 rows per frame' % (RUNS, WARMUP)]

@@ -25,8 +25,14 @@ def eval_one_epoch(cfg, args, model, dataloader, epoch_id, logger, dist_test=Fal
             # batches alternate between the model and a copy on their own streams.  --fast_capacity N (round 6): every batch is padded to N rows
             # (frame index -1 behind the real ones) and each replica's forward is replayed as ONE hipGraph -- the poses of a DiscoNet batch are
             # device-side data refreshed per batch, so one capture per (batch size, set of agents) serves the whole epoch
+            if capacity > 0 and PipelinedDetector._device_count_backbone(model):
+                logger.info('--fast_capacity: the device-count sparse backbone has no captured form: eager launches')
+                capacity = 0
             pipe = PipelinedDetector(model, replicas=2, graph=capacity > 0)
             padded = PaddedPoints(capacity) if capacity > 0 else None
+            logger.info('--fast: batches pipelined over %d model replicas' % len(pipe.models))
+        else:
+            logger.info('--fast: this model runs batch by batch (PipelinedDetector does not support it)')
     # --device_eval: detections scored against the batch's gt_boxes where both lie (pcp_amd/det_eval.py: nuScenes-protocol mAP and TP
     # errors); the evaluator is built on the first batch that carries gt_boxes and fed the device tensors of both loops below
     dev_eval = None

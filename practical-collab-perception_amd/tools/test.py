@@ -50,6 +50,9 @@ def parse_config():
         cfg.DATA_CONFIG.SYNTHETIC = {}
     if 'EVAL_GT' not in cfg.DATA_CONFIG.SYNTHETIC:
         cfg.DATA_CONFIG.SYNTHETIC.EVAL_GT = False              # present before --set, which only takes keys that exist
+    for section in ('VFE', 'BACKBONE_3D'):                      # the opt-in device-count form of the SECOND models, settable with --set
+        if cfg.MODEL.get(section, None) is not None and 'DEVICE_COUNTS' not in cfg.MODEL[section]:
+            cfg.MODEL[section].DEVICE_COUNTS = False
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
     return args, cfg
