@@ -25,11 +25,17 @@ pcp_select_transform_compact_dev / pcp_warp_nearest_batch_dev) that the runner r
 one capture serves every pose set.  The mode suits fixed-shape streams (bench.py; a dataloader that pads its clouds to a capacity with
 frame index -1 rows).
 """
+import collections
 import os
 
 import torch
 
 from pcp_amd import ops
+
+
+# a submitted batch whose counts are not read yet.  static: the outputs are a graph's (the replica's next replay overwrites them); status_host
+# / dev_levels: the status words of a device-count SECOND forward (pinned copy, read at the same event) and its (name, capacity) per level
+_Pending = collections.namedtuple('_Pending', 'ob os_ ol counts_host event batch_size static status_host dev_levels', defaults=(None, None))
 
 
 class PoseTable:
@@ -169,7 +175,7 @@ class PipelinedDetector:
         self.mains = None
         self.head = model.dense_head
         self.side = None
-        self._pending = None          # (ob, os_, ol, counts_host, event, batch_size, outputs are static)
+        self._pending = None          # the _Pending of the newest batch
         self._pinned = {}             # two pinned count buffers per batch size, used alternately
         self._events = None           # two blocking events, used alternately (at most two batches are pending: the one being read and the newest)
         self._n = 0
@@ -254,7 +260,7 @@ class PipelinedDetector:
                 status_host = self._pinned[skey][(self._n - 1) & 1]
                 status_host.copy_(status, non_blocking=True)
             ev.record(main)
-        prev, self._pending = self._pending, (ob, os_, ol, counts_host, ev, batch_size, False, status_host, bd.get('_pcp_dev_levels', None))
+        prev, self._pending = self._pending, _Pending(ob, os_, ol, counts_host, ev, batch_size, False, status_host, bd.get('_pcp_dev_levels', None))
         return self._finish(prev)
 
     # ---- graph mode ---------------------------------------------------------------------------------------------------------------------
@@ -335,7 +341,7 @@ class PipelinedDetector:
             ev = self._events[self._n & 1]
             ev.record(main)
         # the graph's output tensors are static (the replica's next replay overwrites them): _finish hands out copies
-        prev, self._pending = self._pending, (ent['ob'], ent['os'], ent['ol'], counts_host, ev, batch_size, True)
+        prev, self._pending = self._pending, _Pending(ent['ob'], ent['os'], ent['ol'], counts_host, ev, batch_size, True)
         return self._finish(prev)
 
     def prepare(self, points, batch_size, metadata):
@@ -363,12 +369,12 @@ class PipelinedDetector:
     def _finish(cls, p):
         if p is None:
             return None
-        ob, os_, ol, counts_host, ev, batch_size, static = p[:7]
-        cls._wait(ev)
-        if len(p) > 7 and p[7] is not None:
-            ops.dev_status_check(p[7].numpy().copy(), batch_size, p[8])
+        ob, os_, ol, counts_host, batch_size = p.ob, p.os_, p.ol, p.counts_host, p.batch_size
+        cls._wait(p.event)
+        if p.status_host is not None:
+            ops.dev_status_check(p.status_host.numpy().copy(), batch_size, p.dev_levels)
         cur = torch.cuda.current_stream()
-        if static:
+        if p.static:
             # graph mode: copies, queued on the caller's stream now (the data are complete: the event was waited for) -- the replica's next
             # replay waits for the caller's stream at its submit(), i.e. for these copies
             ob, os_, ol = ob.clone(), os_.clone(), ol.clone()

@@ -1206,200 +1206,15 @@ def pillar_vfe(voxels, voxel_num_points, voxel_coords, voxel_size, offset, w, b,
 # ---------------------------------------------------------------------------------------------------------------------
 # the SECOND family: per-voxel mean, sparse 3D convolution index tables, the convolution, dense() (csrc/spconv3d.hip)
 # ---------------------------------------------------------------------------------------------------------------------
+# Five ops come in two forms over ONE private body each.  Host counts (n_dev None): every tensor has exactly its rows, the buffers are fresh
+# torch.empty ones, the host symbols run, and the row count a later size depends on is read back.  Device counts (`_dev`: no host read in
+# the middle of the forward): the first *n_dev rows of capacity-sized tensors are real, the buffers come by name from the replica's
+# DevBuffers, the `_dev` symbols run (include/pcp_hip.h), and nothing is read back.  A body differs between the forms only in that.
+
 # (cin padded to 16, cout); (32, 16), (64, 32), (128, 64) are the data gradients of the strided layers (train_ops.spconv3d_wgrad takes the others)
 SPCONV_CHANNEL_PAIRS = ((16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64), (64, 128), (128, 64), (128, 128))
-
-
-def mean_vfe(points, grid, num_features, *, nz, workspace=None):
-    """the reference's DynamicMeanVFE on the device (include/pcp_hip.h: pcp_mean_vfe).  points: (N, >= 1 + num_features) float32 CUDA rows
-    [b, x, y, z, f...] grouped by ascending frame (ValueError otherwise); grid: make_grid(...), which carries the x / y extent and the z
-    origin and cell height only, hence the keyword nz = cells along z (grid_size[2]).  Returns voxel_features
-    (M, num_features), voxel_coords (M, 4) int32 [b, z, y, x] in ascending merged id, M.  One host read."""
-    _need_cuda(points)
-    if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
-        raise ValueError('mean_vfe: points must be a contiguous (N, 1 + C) float32 tensor, got %s %s' % (tuple(points.shape), points.dtype))
-    n, stride = int(points.shape[0]), int(points.shape[1])
-    C, B, nz = int(num_features), int(grid.batch_size), int(nz)
-    if not MEAN_VFE_MIN_FEATURES <= C <= MEAN_VFE_MAX_FEATURES:
-        raise ValueError('mean_vfe: %d to %d feature columns behind the frame index, got %d' % (MEAN_VFE_MIN_FEATURES, MEAN_VFE_MAX_FEATURES, C))
-    if stride < 1 + C:
-        raise ValueError('mean_vfe: rows of %d columns cannot hold the frame index and %d features' % (stride, C))
-    if not 1 <= B <= MEAN_VFE_MAX_BATCH:
-        raise ValueError('mean_vfe: at most %d frames per call, got %d' % (MEAN_VFE_MAX_BATCH, B))
-    if not 1 <= nz <= MEAN_VFE_MAX_NZ:
-        raise ValueError('mean_vfe: 1 to %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, nz))
-    L = _lib.load()
-    dev = points.device
-    need = L.pcp_mean_vfe_workspace_bytes(ctypes.byref(grid), n)
-    if need == 0:
-        raise _lib.PcpError('pcp_mean_vfe: unsupported grid')
-    if workspace is None or workspace.numel() < need or workspace.device != dev:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    coords = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
-    counters = torch.empty((MEAN_VFE_COUNTERS,), dtype=torch.int32, device=dev)
-    check(L.pcp_mean_vfe(_p(points), n, stride, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(coords), _p(counters), _stream()),
-          'pcp_mean_vfe')
-    M, err = counters[:2].tolist()                     # the one host read
-    if err:
-        raise ValueError('mean_vfe: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (B, err))
-    feats = torch.empty((M, C), dtype=torch.float32, device=dev)
-    check(L.pcp_mean_vfe_features(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), M, _p(feats), _stream()),
-          'pcp_mean_vfe_features')
-    return feats, coords[:M], M
-
-
-def _i3(v):
-    v = [int(v)] * 3 if isinstance(v, int) else [int(x) for x in v]
-    assert len(v) == 3, v
-    return v
-
-
-class SpconvTable:
-    """the lookup structure of one coordinate set (bitmap + popcount prefix, include/pcp_hip.h); perm None: rows in ascending linear order"""
-
-    def __init__(self, shape4, mem, perm):
-        self.shape4, self.mem, self.perm = tuple(int(v) for v in shape4), mem, perm
-        self.capacity = None                  # set by the device-count forms: the rows the set's buffers hold
-
-
-def _spconv_table_mem(shape4, dev):
-    need = _lib.load().pcp_spconv_table_bytes(*shape4)
-    if need == 0:
-        raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % (tuple(shape4),))
-    return torch.empty(need, dtype=torch.uint8, device=dev)
-
-
-def spconv_table(coords, batch_size, spatial_shape, check_input=True):
-    """the table of coords (N, 4) int32 [b, z, y, x] on a (batch_size, *spatial_shape) grid.  check_input reads the distinct-site count and the
-    range flag back (ValueError on a duplicated or outside coordinate); a producer that guarantees both (mean_vfe) passes False."""
-    _need_cuda(coords)
-    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4 or not coords.is_contiguous():
-        raise ValueError('sparse conv tables: indices must be a contiguous (N, 4) int32 tensor, got %s %s' % (tuple(coords.shape), coords.dtype))
-    shape4 = (int(batch_size),) + tuple(int(v) for v in spatial_shape)
-    n, dev = int(coords.shape[0]), coords.device
-    mem = _spconv_table_mem(shape4, dev)
-    perm = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
-    counters = torch.empty((4,), dtype=torch.int32, device=dev)
-    check(_lib.load().pcp_spconv_table_build(_p(coords), n, *shape4, _p(mem), mem.numel(), _p(perm), _p(counters), _stream()),
-          'pcp_spconv_table_build')
-    if check_input:
-        distinct, bad = counters[:2].tolist()
-        if bad or distinct != n:
-            raise ValueError('sparse conv tables: %d rows name %d distinct sites%s of the grid %s'
-                             % (n, distinct, ' and some lie outside' if bad else '', shape4))
-    return SpconvTable(shape4, mem, perm)
-
-
-def spconv_build_subm(coords, table):
-    """neighbour table (27, N) int32 of SubMConv3d(3, padding 1) over the set `table` describes"""
-    n = int(coords.shape[0])
-    nbr = torch.empty((27, n), dtype=torch.int32, device=coords.device)
-    check(_lib.load().pcp_spconv_build_subm(_p(coords), n, *table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), _p(nbr), _stream()),
-          'pcp_spconv_build_subm')
-    return nbr
-
-
-def spconv_out_shape(spatial_shape, kernel, stride, padding):
-    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
-    return tuple((int(spatial_shape[a]) + 2 * p[a] - k[a]) // s[a] + 1 for a in range(3))
-
-
-def spconv_build_strided(coords, table, kernel, stride, padding):
-    """SparseConv3d's index: -> (out_coords (N_out, 4) int32 in ascending linear order, nbr (K, N_out) int32, out_table).  One host read."""
-    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
-    for name, v, lo, hi in (('kernel', k, 1, 3), ('stride', s, 1, 3), ('padding', p, 0, 2)):
-        if not all(lo <= x <= hi for x in v):
-            raise NotImplementedError('sparse conv: %s %s outside [%d, %d]' % (name, tuple(v), lo, hi))
-    B = table.shape4[0]
-    out_sp = spconv_out_shape(table.shape4[1:], k, s, p)
-    if min(out_sp) < 1:
-        raise ValueError('sparse conv: kernel %s stride %s padding %s leaves no output on the grid %s' % (k, s, p, table.shape4[1:]))
-    L = _lib.load()
-    dev = coords.device
-    n_in = int(coords.shape[0])
-    out_mem = _spconv_table_mem((B,) + out_sp, dev)
-    counters = torch.empty((4,), dtype=torch.int32, device=dev)
-    k3, s3, p3 = (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*s), (ctypes.c_int32 * 3)(*p)
-    check(L.pcp_spconv_strided_sites(_p(coords), n_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), _p(counters), _stream()),
-          'pcp_spconv_strided_sites')
-    n_out = int(counters[0].item())                  # the one host read of a strided layer
-    K = k[0] * k[1] * k[2]
-    out_coords = torch.empty((n_out, 4), dtype=torch.int32, device=dev)
-    nbr = torch.empty((K, n_out), dtype=torch.int32, device=dev)
-    check(L.pcp_spconv_build_strided(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), k3, s3, p3, _p(out_mem), out_mem.numel(),
-                                     n_out, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided')
-    return out_coords, nbr, SpconvTable((B,) + out_sp, out_mem, None)
-
-
-def spconv_pack_weight(weight, cin_pad=None):
-    """(Cout, kz, ky, kx, Cin) -> [K][Cout][cin_pad] float32 contiguous, zero columns behind Cin"""
-    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
-    cin_pad = cin_pad or (16 if cin <= 16 else cin)
-    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 0, 2)
-    if cin_pad != cin:
-        w = torch.nn.functional.pad(w, (0, cin_pad - cin))
-    return w.contiguous()
-
-
-def spconv_pack_weight_dgrad(weight, mirror):
-    """(Cout, kz, ky, kx, Cin) -> [K][Cin][Cout]: the weights of the data gradient dx = spconv3d(dy, table, .).  mirror (a submanifold layer,
-    whose own table serves): W'[k] = W[K - 1 - k]^T; a strided layer (the inverse table, train_ops.spconv_invert_nbr): W'[k] = W[k]^T."""
-    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
-    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 2, 0)
-    if mirror:
-        w = w.flip(0)
-    return w.contiguous()
-
-
-def spconv3d(features, nbr, w_packed, bias, residual=None, relu=False):
-    """out (N_out, Cout) = relu?(sum_k features[nbr[k]] . w_packed[k]^T + bias + residual?) (include/pcp_hip.h: pcp_spconv3d)"""
-    _need_cuda(features, nbr, w_packed, bias, residual)
-    _need_f32('pcp_spconv3d', features, w_packed, bias, residual)
-    if nbr.dtype != torch.int32 or nbr.dim() != 2:
-        raise _lib.PcpError('pcp_spconv3d reads an int32 (K, N_out) neighbour table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
-    for t in (nbr, w_packed, bias, residual):
-        assert t is None or t.is_contiguous()
-    assert features.dim() == 2 and features.stride(1) == 1
-    n_in, cin, ld_in = int(features.shape[0]), int(features.shape[1]), int(features.stride(0)) if features.shape[0] > 1 else int(features.shape[1])
-    K, n_out = int(nbr.shape[0]), int(nbr.shape[1])
-    cout, cin_pad = int(w_packed.shape[1]), int(w_packed.shape[2])
-    if cin < 3 or (16 if cin <= 16 else cin) != cin_pad or (cin_pad, cout) not in SPCONV_CHANNEL_PAIRS:
-        raise NotImplementedError('pcp_spconv3d: the channel pair (Cin, Cout) = (%d, %d) has no kernel; supported: Cin 3..16 -> 16, and %s'
-                                  % (cin, cout, ', '.join('%d -> %d' % p for p in SPCONV_CHANNEL_PAIRS)))
-    assert int(w_packed.shape[0]) == K and tuple(bias.shape) == (cout,), (tuple(w_packed.shape), K, tuple(bias.shape))
-    assert residual is None or tuple(residual.shape) == (n_out, cout)
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=features.device)
-    check(_lib.load().pcp_spconv3d(_p(features), n_in, cin, ld_in, _p(nbr), K, n_out, _p(w_packed), _p(bias), _p(residual), 1 if relu else 0, cout,
-                                   _p(out), _stream()), 'pcp_spconv3d')
-    return out
-
-
-def spconv_dense(features, table):
-    """the NHWC canvas (B, H, W, C * D), channel c * D + d: HeightCompression's dense() + view, every element written by the kernel"""
-    _need_cuda(features)
-    _need_f32('pcp_spconv_dense', features)
-    assert features.is_contiguous() and features.dim() == 2
-    B, D, H, W = table.shape4
-    if D > MEAN_VFE_MAX_NZ:
-        raise NotImplementedError('pcp_spconv_dense: at most %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, D))
-    n, C = int(features.shape[0]), int(features.shape[1])
-    out = torch.empty((B, H, W, C * D), dtype=torch.float32, device=features.device)
-    if table.capacity is not None:
-        # a table of the device-count forms: a site whose row lies at or past the capacity (a dropped tail) reads as empty
-        assert n == table.capacity, (n, table.capacity)
-        check(_lib.load().pcp_spconv_dense_below(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()),
-              'pcp_spconv_dense_below')
-        return out
-    check(_lib.load().pcp_spconv_dense(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()),
-          'pcp_spconv_dense')
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# the SECOND family without a host read in the middle of the forward: the device-count forms (include/pcp_hip.h, `_dev`)
-# ---------------------------------------------------------------------------------------------------------------------
-# the status words of one forward, read once at its end: [0 .. 3] pcp_mean_vfe's counters (M, error word, rows kept), [4] bit L set: level L
-# of the sparse backbone held more rows than its capacity
+# the status words of one device-count forward, read once at its end: [0 .. 3] pcp_mean_vfe's counters (M, error word, rows kept), [4] bit L
+# set: level L of the sparse backbone held more rows than its capacity
 DEV_STATUS_WORDS = 8
 DEV_STATUS_OVERFLOW = 4
 
@@ -1430,10 +1245,16 @@ def _buf(bufs, name, shape, dtype, device):
     return bufs.get(name, shape, dtype, device)
 
 
-def mean_vfe_dev(points, grid, num_features, *, nz, bufs=None):
-    """mean_vfe without its host read.  Returns voxel_features (cap, num_features), voxel_coords (cap, 4) with cap = max(N, 1) rows, of
-    which the first M are written, and the (DEV_STATUS_WORDS,) int32 status tensor: status[0:1] is M on the device, status[1] the error word
-    (dev_status_check raises on it at the forward's final read)."""
+def _count(n, n_dev):
+    """the row-count arguments of a C call: n rows, or (`_dev` symbols) the device count and the capacity n of the buffers behind it"""
+    return (n,) if n_dev is None else (_p(n_dev), n)
+
+
+def _frame_order_error(batch_size, err):
+    return ValueError('mean_vfe: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (batch_size, err))
+
+
+def _mean_vfe(points, grid, num_features, nz, workspace, dev, bufs):
     _need_cuda(points)
     if points.dtype != torch.float32 or points.dim() != 2 or not points.is_contiguous():
         raise ValueError('mean_vfe: points must be a contiguous (N, 1 + C) float32 tensor, got %s %s' % (tuple(points.shape), points.dtype))
@@ -1448,20 +1269,46 @@ def mean_vfe_dev(points, grid, num_features, *, nz, bufs=None):
     if not 1 <= nz <= MEAN_VFE_MAX_NZ:
         raise ValueError('mean_vfe: 1 to %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, nz))
     L = _lib.load()
-    dev = points.device
+    device = points.device
     need = L.pcp_mean_vfe_workspace_bytes(ctypes.byref(grid), n)
     if need == 0:
         raise _lib.PcpError('pcp_mean_vfe: unsupported grid')
+    if workspace is None or workspace.numel() < need or workspace.device != device:
+        workspace = _buf(bufs, 'mv_ws', (need,), torch.uint8, device)
     cap = max(n, 1)
-    workspace = _buf(bufs, 'mv_ws', (need,), torch.uint8, dev)
-    coords = _buf(bufs, 'mv_coords', (cap, 4), torch.int32, dev)
-    feats = _buf(bufs, 'mv_feats', (cap, C), torch.float32, dev)
-    status = torch.zeros((DEV_STATUS_WORDS,), dtype=torch.int32, device=dev)
-    check(L.pcp_mean_vfe(_p(points), n, stride, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(coords), _p(status), _stream()),
+    coords = _buf(bufs, 'mv_coords', (cap, 4), torch.int32, device)
+    # the kernel's counters (M, error word, rows kept): read back here, or the head of the forward's status words
+    counters = (torch.zeros((DEV_STATUS_WORDS,), dtype=torch.int32, device=device) if dev
+                else torch.empty((MEAN_VFE_COUNTERS,), dtype=torch.int32, device=device))
+    check(L.pcp_mean_vfe(_p(points), n, stride, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(coords), _p(counters), _stream()),
           'pcp_mean_vfe')
-    check(L.pcp_mean_vfe_features_dev(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(status), n, _p(feats),
-                                      _stream()), 'pcp_mean_vfe_features_dev')
-    return feats, coords, status
+    if dev:
+        feats = _buf(bufs, 'mv_feats', (cap, C), torch.float32, device)
+        check(L.pcp_mean_vfe_features_dev(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), _p(counters), n,
+                                          _p(feats), _stream()), 'pcp_mean_vfe_features_dev')
+        return feats, coords, counters
+    M, err = counters[:2].tolist()                     # the one host read
+    if err:
+        raise _frame_order_error(B, err)
+    feats = torch.empty((M, C), dtype=torch.float32, device=device)
+    check(L.pcp_mean_vfe_features(_p(points), n, stride, C, ctypes.byref(grid), nz, _p(workspace), workspace.numel(), M, _p(feats), _stream()),
+          'pcp_mean_vfe_features')
+    return feats, coords[:M], M
+
+
+def mean_vfe(points, grid, num_features, *, nz, workspace=None):
+    """the reference's DynamicMeanVFE on the device (include/pcp_hip.h: pcp_mean_vfe).  points: (N, >= 1 + num_features) float32 CUDA rows
+    [b, x, y, z, f...] grouped by ascending frame (ValueError otherwise); grid: make_grid(...), which carries the x / y extent and the z
+    origin and cell height only, hence the keyword nz = cells along z (grid_size[2]).  Returns voxel_features
+    (M, num_features), voxel_coords (M, 4) int32 [b, z, y, x] in ascending merged id, M.  One host read."""
+    return _mean_vfe(points, grid, num_features, nz, workspace, False, None)
+
+
+def mean_vfe_dev(points, grid, num_features, *, nz, bufs=None):
+    """mean_vfe without its host read.  Returns voxel_features (cap, num_features), voxel_coords (cap, 4) with cap = max(N, 1) rows, of
+    which the first M are written, and the (DEV_STATUS_WORDS,) int32 status tensor: status[0:1] is M on the device, status[1] the error word
+    (dev_status_check raises on it at the forward's final read)."""
+    return _mean_vfe(points, grid, num_features, nz, None, True, bufs)
 
 
 def dev_status_check(words, batch_size, levels=None):
@@ -1470,41 +1317,92 @@ def dev_status_check(words, batch_size, levels=None):
     words = [int(v) for v in words]
     err, over = words[1], words[DEV_STATUS_OVERFLOW]
     if err:
-        raise ValueError('mean_vfe: the point rows are not grouped by ascending frame index in [0, %d) (error word %d)' % (int(batch_size), err))
+        raise _frame_order_error(int(batch_size), err)
     if over:
         hit = [i for i in range(31) if over >> i & 1]
         names = ', '.join('level %d (%s, ROW_CAPACITY %d)' % ((i,) + tuple(levels[i])) if levels and i < len(levels) else 'level %d' % i for i in hit)
         raise RuntimeError('sparse backbone: more rows than the capacity at %s; the rows behind it were dropped (overflow word %d)' % (names, over))
 
 
-def spconv_table_dev(coords, n_dev, batch_size, spatial_shape, bufs=None):
-    """spconv_table of the first *n_dev rows of the capacity-sized coords; the sites must be distinct and inside the grid (mean_vfe_dev's
-    are): nothing is read back to check"""
-    _need_cuda(coords, n_dev)
-    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4 or not coords.is_contiguous():
-        raise ValueError('sparse conv tables: indices must be a contiguous (N, 4) int32 tensor, got %s %s' % (tuple(coords.shape), coords.dtype))
-    shape4 = (int(batch_size),) + tuple(int(v) for v in spatial_shape)
-    cap, dev = int(coords.shape[0]), coords.device
+def _i3(v):
+    v = [int(v)] * 3 if isinstance(v, int) else [int(x) for x in v]
+    assert len(v) == 3, v
+    return v
+
+
+class SpconvTable:
+    """the lookup structure of one coordinate set (bitmap + popcount prefix, include/pcp_hip.h); perm None: rows in ascending linear order"""
+
+    def __init__(self, shape4, mem, perm):
+        self.shape4, self.mem, self.perm = tuple(int(v) for v in shape4), mem, perm
+        self.capacity = None                  # set by the device-count forms: the rows the set's buffers hold
+
+
+def _spconv_table_mem(shape4, device, bufs=None, name=None):
     need = _lib.load().pcp_spconv_table_bytes(*shape4)
     if need == 0:
         raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % (tuple(shape4),))
-    mem = _buf(bufs, 'table0', (need,), torch.uint8, dev)
-    perm = _buf(bufs, 'perm0', (max(cap, 1),), torch.int32, dev)
-    counters = torch.empty((4,), dtype=torch.int32, device=dev)
-    check(_lib.load().pcp_spconv_table_build_dev(_p(coords), _p(n_dev), cap, *shape4, _p(mem), mem.numel(), _p(perm), _p(counters), _stream()),
-          'pcp_spconv_table_build_dev')
+    return _buf(bufs, name, (need,), torch.uint8, device)
+
+
+def _spconv_table(coords, n_dev, batch_size, spatial_shape, check_input, bufs):
+    dev = n_dev is not None
+    _need_cuda(coords, n_dev) if dev else _need_cuda(coords)
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4 or not coords.is_contiguous():
+        raise ValueError('sparse conv tables: indices must be a contiguous (N, 4) int32 tensor, got %s %s' % (tuple(coords.shape), coords.dtype))
+    shape4 = (int(batch_size),) + tuple(int(v) for v in spatial_shape)
+    n, device = int(coords.shape[0]), coords.device
+    mem = _spconv_table_mem(shape4, device, bufs, 'table0')
+    # host counts: a row that is not the first of its site keeps -1; device counts: the sites are distinct, every row below the count is written
+    perm = _buf(bufs, 'perm0', (max(n, 1),), torch.int32, device) if dev else torch.full((max(n, 1),), -1, dtype=torch.int32, device=device)
+    counters = torch.empty((4,), dtype=torch.int32, device=device)
+    L = _lib.load()
+    build = L.pcp_spconv_table_build_dev if dev else L.pcp_spconv_table_build
+    check(build(_p(coords), *_count(n, n_dev), *shape4, _p(mem), mem.numel(), _p(perm), _p(counters), _stream()), build.__name__)
+    if check_input:
+        distinct, bad = counters[:2].tolist()
+        if bad or distinct != n:
+            raise ValueError('sparse conv tables: %d rows name %d distinct sites%s of the grid %s'
+                             % (n, distinct, ' and some lie outside' if bad else '', shape4))
     t = SpconvTable(shape4, mem, perm)
-    t.capacity = cap
+    t.capacity = n if dev else None
     return t
+
+
+def spconv_table(coords, batch_size, spatial_shape, check_input=True):
+    """the table of coords (N, 4) int32 [b, z, y, x] on a (batch_size, *spatial_shape) grid.  check_input reads the distinct-site count and the
+    range flag back (ValueError on a duplicated or outside coordinate); a producer that guarantees both (mean_vfe) passes False."""
+    return _spconv_table(coords, None, batch_size, spatial_shape, check_input, None)
+
+
+def spconv_table_dev(coords, n_dev, batch_size, spatial_shape, bufs=None):
+    """spconv_table of the first *n_dev rows of the capacity-sized coords; the sites must be distinct and inside the grid (mean_vfe_dev's
+    are): nothing is read back to check"""
+    return _spconv_table(coords, n_dev, batch_size, spatial_shape, False, bufs)
+
+
+def _spconv_build_subm(coords, table, n_dev, bufs, name):
+    n = int(coords.shape[0])
+    nbr = _buf(bufs, name, (27, n), torch.int32, coords.device)
+    L = _lib.load()
+    build = L.pcp_spconv_build_subm if n_dev is None else L.pcp_spconv_build_subm_dev
+    check(build(_p(coords), *_count(n, n_dev), *table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), _p(nbr), _stream()), build.__name__)
+    return nbr
+
+
+def spconv_build_subm(coords, table):
+    """neighbour table (27, N) int32 of SubMConv3d(3, padding 1) over the set `table` describes"""
+    return _spconv_build_subm(coords, table, None, None, None)
 
 
 def spconv_build_subm_dev(coords, table, n_dev, bufs=None, name='subm'):
     """neighbour table (27, cap) of the first *n_dev rows: entry [k][row] at k * cap + row"""
-    cap = int(coords.shape[0])
-    nbr = _buf(bufs, 'nbr_' + name, (27, cap), torch.int32, coords.device)
-    check(_lib.load().pcp_spconv_build_subm_dev(_p(coords), _p(n_dev), cap, *table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), _p(nbr),
-                                                _stream()), 'pcp_spconv_build_subm_dev')
-    return nbr
+    return _spconv_build_subm(coords, table, n_dev, bufs, 'nbr_' + name)
+
+
+def spconv_out_shape(spatial_shape, kernel, stride, padding):
+    k, s, p = _i3(kernel), _i3(stride), _i3(padding)
+    return tuple((int(spatial_shape[a]) + 2 * p[a] - k[a]) // s[a] + 1 for a in range(3))
 
 
 def spconv_strided_bound(capacity_in, kernel, stride, out_shape4):
@@ -1519,60 +1417,134 @@ def spconv_strided_bound(capacity_in, kernel, stride, out_shape4):
     return max(min(int(capacity_in) * reach, sites), 1)
 
 
-def spconv_build_strided_dev(coords, table, n_dev, kernel, stride, padding, capacity=None, status=None, level=0, bufs=None, name='spconv'):
-    """spconv_build_strided without its host read -> (out_coords (cap, 4), nbr (K, cap), out_table, n_out_dev).  cap: `capacity`, or the exact
-    bound (spconv_strided_bound), which cannot overflow.  More rows than cap: the tail of the ascending linear order is dropped and bit
-    `level` of status[DEV_STATUS_OVERFLOW] is set."""
+def _spconv_build_strided(coords, table, n_dev, kernel, stride, padding, capacity, status, level, bufs, name):
+    """-> (out_coords, nbr, out_table, n_out_dev); n_out_dev None with host counts"""
+    dev = n_dev is not None
     k, s, p = _i3(kernel), _i3(stride), _i3(padding)
     for what, v, lo, hi in (('kernel', k, 1, 3), ('stride', s, 1, 3), ('padding', p, 0, 2)):
         if not all(lo <= x <= hi for x in v):
             raise NotImplementedError('sparse conv: %s %s outside [%d, %d]' % (what, tuple(v), lo, hi))
-    B = table.shape4[0]
     out_sp = spconv_out_shape(table.shape4[1:], k, s, p)
     if min(out_sp) < 1:
         raise ValueError('sparse conv: kernel %s stride %s padding %s leaves no output on the grid %s' % (k, s, p, table.shape4[1:]))
+    out4 = (table.shape4[0],) + out_sp
     L = _lib.load()
-    dev = coords.device
-    cap_in = int(coords.shape[0])
-    bound = spconv_strided_bound(cap_in, k, s, (B,) + out_sp)
-    cap = bound if capacity is None else max(min(int(capacity), bound), 1)
-    need = L.pcp_spconv_table_bytes(B, *out_sp)
-    if need == 0:
-        raise _lib.PcpError('sparse conv tables: unsupported grid (batch, z, y, x) = %s' % ((B,) + out_sp,))
-    out_mem = _buf(bufs, 'table_' + name, (need,), torch.uint8, dev)
-    counters = torch.empty((4,), dtype=torch.int32, device=dev)
-    err = status[DEV_STATUS_OVERFLOW:] if status is not None else None
+    device = coords.device
+    n_in = int(coords.shape[0])
+    out_mem = _spconv_table_mem(out4, device, bufs, 'table_' + name)
+    counters = torch.empty((4,), dtype=torch.int32, device=device)
     k3, s3, p3 = (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*s), (ctypes.c_int32 * 3)(*p)
-    check(L.pcp_spconv_strided_sites_dev(_p(coords), _p(n_dev), cap_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), cap, _p(counters),
-                                         _p(err), 1 << int(level), _stream()), 'pcp_spconv_strided_sites_dev')
-    K = k[0] * k[1] * k[2]
-    out_coords = _buf(bufs, 'coords_' + name, (cap, 4), torch.int32, dev)
-    nbr = _buf(bufs, 'nbr_' + name, (K, cap), torch.int32, dev)
-    check(L.pcp_spconv_build_strided_dev(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), cap_in, k3, s3, p3, _p(out_mem),
-                                         out_mem.numel(), _p(counters), cap, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided_dev')
-    ot = SpconvTable((B,) + out_sp, out_mem, None)
-    ot.capacity = cap
-    return out_coords, nbr, ot, counters[0:1]
+    if dev:
+        # the rows the output buffers hold: `capacity`, or the exact bound, which cannot overflow
+        bound = spconv_strided_bound(n_in, k, s, out4)
+        n_out = bound if capacity is None else max(min(int(capacity), bound), 1)
+        err = status[DEV_STATUS_OVERFLOW:] if status is not None else None
+        check(L.pcp_spconv_strided_sites_dev(_p(coords), _p(n_dev), n_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), n_out,
+                                             _p(counters), _p(err), 1 << int(level), _stream()), 'pcp_spconv_strided_sites_dev')
+    else:
+        check(L.pcp_spconv_strided_sites(_p(coords), n_in, *table.shape4, k3, s3, p3, _p(out_mem), out_mem.numel(), _p(counters), _stream()),
+              'pcp_spconv_strided_sites')
+        n_out = int(counters[0].item())                  # the one host read of a strided layer
+    out_coords = _buf(bufs, 'coords_' + name, (n_out, 4), torch.int32, device)
+    nbr = _buf(bufs, 'nbr_' + name, (k[0] * k[1] * k[2], n_out), torch.int32, device)
+    out_table = SpconvTable(out4, out_mem, None)
+    if dev:
+        check(L.pcp_spconv_build_strided_dev(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), n_in, k3, s3, p3, _p(out_mem),
+                                             out_mem.numel(), _p(counters), n_out, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided_dev')
+        out_table.capacity = n_out
+        return out_coords, nbr, out_table, counters[0:1]
+    check(L.pcp_spconv_build_strided(*table.shape4, _p(table.mem), table.mem.numel(), _p(table.perm), k3, s3, p3, _p(out_mem), out_mem.numel(),
+                                     n_out, _p(out_coords), _p(nbr), _stream()), 'pcp_spconv_build_strided')
+    return out_coords, nbr, out_table, None
 
 
-def spconv3d_dev(features, nbr, n_dev, w_packed, bias, residual=None, relu=False, bufs=None, name='conv'):
-    """spconv3d over the first *n_dev output rows of a (K, cap) neighbour table; out (cap, Cout), rows at or past the count not written"""
-    _need_cuda(features, nbr, w_packed, bias, residual, n_dev)
-    _need_f32('pcp_spconv3d_dev', features, w_packed, bias, residual)
+def spconv_build_strided(coords, table, kernel, stride, padding):
+    """SparseConv3d's index: -> (out_coords (N_out, 4) int32 in ascending linear order, nbr (K, N_out) int32, out_table).  One host read."""
+    return _spconv_build_strided(coords, table, None, kernel, stride, padding, None, None, 0, None, '')[:3]
+
+
+def spconv_build_strided_dev(coords, table, n_dev, kernel, stride, padding, capacity=None, status=None, level=0, bufs=None, name='spconv'):
+    """spconv_build_strided without its host read -> (out_coords (cap, 4), nbr (K, cap), out_table, n_out_dev).  cap: `capacity`, or the exact
+    bound (spconv_strided_bound), which cannot overflow.  More rows than cap: the tail of the ascending linear order is dropped and bit
+    `level` of status[DEV_STATUS_OVERFLOW] is set."""
+    return _spconv_build_strided(coords, table, n_dev, kernel, stride, padding, capacity, status, level, bufs, name)
+
+
+def spconv_pack_weight(weight, cin_pad=None):
+    """(Cout, kz, ky, kx, Cin) -> [K][Cout][cin_pad] float32 contiguous, zero columns behind Cin"""
+    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
+    cin_pad = cin_pad or (16 if cin <= 16 else cin)
+    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 0, 2)
+    if cin_pad != cin:
+        w = torch.nn.functional.pad(w, (0, cin_pad - cin))
+    return w.contiguous()
+
+
+def spconv_pack_weight_dgrad(weight, mirror):
+    """(Cout, kz, ky, kx, Cin) -> [K][Cin][Cout]: the weights of the data gradient dx = spconv3d(dy, table, .).  mirror (a submanifold layer,
+    whose own table serves): W'[k] = W[K - 1 - k]^T; a strided layer (the inverse table, train_ops.spconv_invert_nbr): W'[k] = W[k]^T."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[-1])
+    w = weight.detach().float().reshape(cout, -1, cin).permute(1, 2, 0)
+    if mirror:
+        w = w.flip(0)
+    return w.contiguous()
+
+
+def _spconv3d(features, nbr, n_dev, w_packed, bias, residual, relu, bufs, name):
+    dev = n_dev is not None
+    what = 'pcp_spconv3d_dev' if dev else 'pcp_spconv3d'
+    _need_cuda(features, nbr, w_packed, bias, residual, n_dev) if dev else _need_cuda(features, nbr, w_packed, bias, residual)
+    _need_f32(what, features, w_packed, bias, residual)
     if nbr.dtype != torch.int32 or nbr.dim() != 2:
-        raise _lib.PcpError('pcp_spconv3d_dev reads an int32 (K, capacity) neighbour table, got %s %s' % (tuple(nbr.shape), nbr.dtype))
+        raise _lib.PcpError('%s reads an int32 (K, %s) neighbour table, got %s %s' % (what, 'capacity' if dev else 'N_out', tuple(nbr.shape), nbr.dtype))
     for t in (nbr, w_packed, bias, residual):
         assert t is None or t.is_contiguous()
     assert features.dim() == 2 and features.stride(1) == 1
     n_in, cin, ld_in = int(features.shape[0]), int(features.shape[1]), int(features.stride(0)) if features.shape[0] > 1 else int(features.shape[1])
-    K, cap = int(nbr.shape[0]), int(nbr.shape[1])
+    K, n_out = int(nbr.shape[0]), int(nbr.shape[1])
     cout, cin_pad = int(w_packed.shape[1]), int(w_packed.shape[2])
     if cin < 3 or (16 if cin <= 16 else cin) != cin_pad or (cin_pad, cout) not in SPCONV_CHANNEL_PAIRS:
         raise NotImplementedError('pcp_spconv3d: the channel pair (Cin, Cout) = (%d, %d) has no kernel; supported: Cin 3..16 -> 16, and %s'
                                   % (cin, cout, ', '.join('%d -> %d' % p for p in SPCONV_CHANNEL_PAIRS)))
     assert int(w_packed.shape[0]) == K and tuple(bias.shape) == (cout,), (tuple(w_packed.shape), K, tuple(bias.shape))
-    assert residual is None or tuple(residual.shape) == (cap, cout)
-    out = _buf(bufs, 'feat_' + name, (cap, cout), torch.float32, features.device)
-    check(_lib.load().pcp_spconv3d_dev(_p(features), n_in, cin, ld_in, _p(nbr), cap, K, _p(n_dev), cap, _p(w_packed), _p(bias), _p(residual),
-                                       1 if relu else 0, cout, _p(out), _stream()), 'pcp_spconv3d_dev')
+    assert residual is None or tuple(residual.shape) == (n_out, cout)
+    out = _buf(bufs, name, (n_out, cout), torch.float32, features.device)
+    L = _lib.load()
+    if dev:
+        # n_out is the capacity: the table's row pitch and the most rows the launch covers
+        check(L.pcp_spconv3d_dev(_p(features), n_in, cin, ld_in, _p(nbr), n_out, K, _p(n_dev), n_out, _p(w_packed), _p(bias), _p(residual),
+                                 1 if relu else 0, cout, _p(out), _stream()), what)
+    else:
+        check(L.pcp_spconv3d(_p(features), n_in, cin, ld_in, _p(nbr), K, n_out, _p(w_packed), _p(bias), _p(residual), 1 if relu else 0, cout,
+                             _p(out), _stream()), what)
+    return out
+
+
+def spconv3d(features, nbr, w_packed, bias, residual=None, relu=False):
+    """out (N_out, Cout) = relu?(sum_k features[nbr[k]] . w_packed[k]^T + bias + residual?) (include/pcp_hip.h: pcp_spconv3d)"""
+    return _spconv3d(features, nbr, None, w_packed, bias, residual, relu, None, None)
+
+
+def spconv3d_dev(features, nbr, n_dev, w_packed, bias, residual=None, relu=False, bufs=None, name='conv'):
+    """spconv3d over the first *n_dev output rows of a (K, cap) neighbour table; out (cap, Cout), rows at or past the count not written"""
+    return _spconv3d(features, nbr, n_dev, w_packed, bias, residual, relu, bufs, 'feat_' + name)
+
+
+def spconv_dense(features, table):
+    """the NHWC canvas (B, H, W, C * D), channel c * D + d: HeightCompression's dense() + view, every element written by the kernel"""
+    _need_cuda(features)
+    _need_f32('pcp_spconv_dense', features)
+    assert features.is_contiguous() and features.dim() == 2
+    B, D, H, W = table.shape4
+    if D > MEAN_VFE_MAX_NZ:
+        raise NotImplementedError('pcp_spconv_dense: at most %d cells along z, got %d' % (MEAN_VFE_MAX_NZ, D))
+    n, C = int(features.shape[0]), int(features.shape[1])
+    out = torch.empty((B, H, W, C * D), dtype=torch.float32, device=features.device)
+    L = _lib.load()
+    dense = L.pcp_spconv_dense
+    if table.capacity is not None:
+        # a table of the device-count forms: a site whose row lies at or past the capacity (a dropped tail) reads as empty
+        assert n == table.capacity, (n, table.capacity)
+        dense = L.pcp_spconv_dense_below
+    check(dense(_p(features), n, C, B, D, H, W, _p(table.mem), table.mem.numel(), _p(table.perm), _p(out), _stream()), dense.__name__)
     return out

@@ -45,10 +45,40 @@ class SparseConvTensor:
     def table(self):
         if self._table is None and self.n_dev is not None:
             self._table = ops.spconv_table_dev(self.indices, self.n_dev, self.batch_size, self.spatial_shape, bufs=self.dev.bufs)
-        if self._table is None:
+        elif self._table is None:
             idx = self.indices if self.indices.dtype == torch.int32 and self.indices.is_contiguous() else self.indices.int().contiguous()
             self._table = ops.spconv_table(idx, self.batch_size, self.spatial_shape, check_input=not self.trusted_indices)
         return self._table
+
+    # the three steps of a conv layer in this tensor's form; the device-count form names its buffers by dev.level / dev.convs
+    def _subm_nbr(self):
+        if self.n_dev is None:
+            return ops.spconv_build_subm(self.indices, self.table())
+        return ops.spconv_build_subm_dev(self.indices, self.table(), self.n_dev, bufs=self.dev.bufs, name='subm%d' % self.dev.level)
+
+    def _strided_index(self, key, kernel_size, stride, padding):
+        """-> (out_indices, nbr, out_table, n_out_dev); n_out_dev None in the host-count form"""
+        if self.n_dev is None:
+            return ops.spconv_build_strided(self.indices, self.table(), kernel_size, stride, padding) + (None,)
+        dev = self.dev
+        dev.level += 1
+        built = ops.spconv_build_strided_dev(self.indices, self.table(), self.n_dev, kernel_size, stride, padding, capacity=dev.capacity_of(dev.level),
+                                             status=dev.status, level=dev.level, bufs=dev.bufs, name='strided%d' % dev.level)
+        dev.levels.append((str(key), int(built[0].shape[0])))
+        return built
+
+    def _conv(self, out_indices, out_spatial_shape, nbr, out_table, n_out_dev, w_packed, bias, residual, relu):
+        """the layer's output tensor, in this tensor's form"""
+        if self.n_dev is None:
+            f = ops.spconv3d(self.features, nbr, w_packed, bias, residual=residual, relu=relu)
+        else:
+            self.dev.convs += 1
+            f = ops.spconv3d_dev(self.features, nbr, n_out_dev, w_packed, bias, residual=residual, relu=relu, bufs=self.dev.bufs,
+                                 name='conv%d' % self.dev.convs)
+        out = SparseConvTensor(f, out_indices, out_spatial_shape, self.batch_size, out_table, self.indice_dict)
+        out.trusted_indices = True
+        out.n_dev, out.dev = n_out_dev, self.dev
+        return out
 
     def dense_nhwc(self):
         """(B, H, W, C * D) with channel c * D + d, every element written by one kernel"""
@@ -110,30 +140,16 @@ class SparseConvolution(SparseModule):
 
     def indices_of(self, x):
         """-> (out_indices, out_spatial_shape, nbr, out_table, n_out_dev); n_out_dev None in the host-count form"""
-        dev = x.dev if x.n_dev is not None else None
         if self.subm:
             hit = x.indice_dict.get(('subm', id(x.indices)))
             if hit is None or hit[0] is not x.indices:
-                if dev is not None:
-                    nbr = ops.spconv_build_subm_dev(x.indices, x.table(), x.n_dev, bufs=dev.bufs, name='subm%d' % dev.level)
-                else:
-                    nbr = ops.spconv_build_subm(x.indices, x.table())
-                hit = (x.indices, nbr)
+                hit = (x.indices, x._subm_nbr())
                 x.indice_dict[('subm', id(x.indices))] = hit
             return x.indices, x.spatial_shape, hit[1], x.table(), x.n_dev
         key = self.indice_key if self.indice_key is not None else ('anon', id(self))
         hit = x.indice_dict.get(key)
         if hit is None or hit[0] is not x.indices:
-            if dev is not None:
-                dev.level += 1
-                oc, nbr, ot, n_out = ops.spconv_build_strided_dev(x.indices, x.table(), x.n_dev, self.kernel_size, self.stride, self.padding,
-                                                                  capacity=dev.capacity_of(dev.level), status=dev.status, level=dev.level,
-                                                                  bufs=dev.bufs, name='strided%d' % dev.level)
-                dev.levels.append((str(key), int(oc.shape[0])))
-            else:
-                oc, nbr, ot = ops.spconv_build_strided(x.indices, x.table(), self.kernel_size, self.stride, self.padding)
-                n_out = None
-            hit = (x.indices, oc, nbr, ot, n_out)
+            hit = (x.indices,) + x._strided_index(key, self.kernel_size, self.stride, self.padding)
             x.indice_dict[key] = hit
         _, oc, nbr, ot, n_out = hit
         return oc, list(ot.shape4[1:]), nbr, ot, n_out
@@ -153,17 +169,7 @@ class SparseConvolution(SparseModule):
             raise TypeError('sparse conv layers take a SparseConvTensor')
         if x.indices.dtype != torch.int32 or not x.indices.is_contiguous():
             x = SparseConvTensor(x.features, x.indices.int().contiguous(), x.spatial_shape, x.batch_size, x._table, x.indice_dict)
-        oc, osp, nbr, ot, n_out = self.indices_of(x)
-        if n_out is not None:
-            x.dev.convs += 1
-            f = ops.spconv3d_dev(x.features, nbr, n_out, w_packed, bias, residual=residual, relu=relu, bufs=x.dev.bufs, name='conv%d' % x.dev.convs)
-        else:
-            f = ops.spconv3d(x.features, nbr, w_packed, bias, residual=residual, relu=relu)
-        out = SparseConvTensor(f, oc, osp, x.batch_size, ot, x.indice_dict)
-        out.trusted_indices = True
-        if n_out is not None:
-            out.with_device_count(n_out, x.dev)
-        return out
+        return x._conv(*self.indices_of(x), w_packed, bias, residual, relu)
 
     def forward(self, x):
         if self.training:

@@ -473,3 +473,69 @@ def test_exact_bound_on_isolated_voxels():
     want = ops.spconv3d(feats, hnbr, w, bias, relu=True)
     got = ops.spconv3d_dev(feats, nbr, n_out, w, bias, relu=True)
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+
+
+# ---- both forms through ops alone ----------------------------------------------------------------------------------------------------------------
+
+def _poisoned(rows, cap, fill):
+    buf = torch.full((cap,) + tuple(rows.shape[1:]), fill, dtype=rows.dtype, device='cuda')
+    buf[:rows.shape[0]] = rows
+    return buf
+
+
+@pytest.mark.parametrize('n', [0, 1, 17, 65])
+def test_both_forms_through_the_ops_wrappers(n):
+    """table -> subm -> conv 16 -> 16 -> strided (both geometries) -> conv 32 -> 64 -> dense, residual and ReLU on, through ops.* and ops.*_dev
+    only (the bit comparisons above call the `_dev` symbols themselves): rows below the count and the dense maps bit-equal, the device count
+    the host's, and a second device-count pass over the same DevBuffers allocates nothing"""
+    B, sp = SHAPE4[0], SHAPE4[1:]
+    g = torch.Generator().manual_seed(900 + n)
+
+    def rand(*shape):
+        return torch.randn(shape, generator=g).cuda()
+    coords = torch.from_numpy(_sites(n, 300 + n)).cuda() if n else torch.zeros((0, 4), dtype=torch.int32, device='cuda')
+    f16, f32, res16 = rand(n, 16), rand(n, 32), rand(n, 16)
+    w16, b16 = ops.spconv_pack_weight(rand(16, 3, 3, 3, 16) * 0.2), rand(16)
+    # ---- host counts
+    ht = ops.spconv_table(coords, B, sp)
+    hsub = ops.spconv_build_subm(coords, ht)
+    hc1 = ops.spconv3d(f16, hsub, w16, b16, residual=res16, relu=True)
+    hd1 = ops.spconv_dense(hc1, ht)
+    host = {}
+    for name, (k, s, p) in GEOMS.items():
+        oc, nbr, ot = ops.spconv_build_strided(coords, ht, k, s, p)
+        w, b, res = ops.spconv_pack_weight(rand(64, *k, 32) * 0.2), rand(64), rand(int(oc.shape[0]), 64)
+        out = ops.spconv3d(f32, nbr, w, b, residual=res, relu=True)
+        host[name] = dict(oc=oc, nbr=nbr, w=w, b=b, res=res, out=out, dense=ops.spconv_dense(out, ot), shape4=ot.shape4)
+    # ---- device counts: capacity-sized inputs, poisoned behind the count; one DevBuffers, two passes
+    cap = n + 5
+    dcoords, n_dev = _poisoned(coords, cap, FAR), _i32([n])
+    df16, df32, dres16 = (_poisoned(t, cap, float('nan')) for t in (f16, f32, res16))
+    bufs, held = ops.DevBuffers(), None
+    for _pass in range(2):
+        status = torch.zeros((ops.DEV_STATUS_WORDS,), dtype=torch.int32, device='cuda')
+        dt = ops.spconv_table_dev(dcoords, n_dev, B, sp, bufs=bufs)
+        assert dt.capacity == cap and dt.shape4 == ht.shape4 and torch.equal(dt.perm[:n], ht.perm[:n])
+        dsub = ops.spconv_build_subm_dev(dcoords, dt, n_dev, bufs=bufs, name='subm0')
+        assert tuple(dsub.shape) == (27, cap) and torch.equal(dsub[:, :n], hsub)
+        dc1 = ops.spconv3d_dev(df16, dsub, n_dev, w16, b16, residual=dres16, relu=True, bufs=bufs, name='conv1')
+        assert tuple(dc1.shape) == (cap, 16) and torch.equal(dc1[:n].view(torch.int32), hc1.view(torch.int32))
+        assert torch.equal(ops.spconv_dense(dc1, dt).view(torch.int32), hd1.view(torch.int32))
+        for level, (name, (k, s, p)) in enumerate(GEOMS.items(), 1):
+            h = host[name]
+            n_out = int(h['oc'].shape[0])
+            oc, nbr, ot, n_out_dev = ops.spconv_build_strided_dev(dcoords, dt, n_dev, k, s, p, status=status, level=level, bufs=bufs, name=name)
+            cap_out = ot.capacity
+            assert int(n_out_dev[0]) == n_out and cap_out >= max(n_out, 1) and ot.shape4 == h['shape4'], name
+            assert tuple(oc.shape) == (cap_out, 4) and tuple(nbr.shape) == (k[0] * k[1] * k[2], cap_out), name
+            assert torch.equal(oc[:n_out], h['oc']) and torch.equal(nbr[:, :n_out], h['nbr']), name
+            out = ops.spconv3d_dev(df32, nbr, n_out_dev, h['w'], h['b'], residual=_poisoned(h['res'], cap_out, float('nan')), relu=True, bufs=bufs,
+                                   name='conv_' + name)
+            assert tuple(out.shape) == (cap_out, 64) and torch.equal(out[:n_out].view(torch.int32), h['out'].view(torch.int32)), name
+            assert torch.equal(ops.spconv_dense(out, ot).view(torch.int32), h['dense'].view(torch.int32)), name
+        assert status.tolist() == [0] * ops.DEV_STATUS_WORDS
+        now = {key: (t.data_ptr(), t.numel()) for key, t in bufs._t.items()}
+        assert held is None or now == held, 'the second pass allocated'
+        held = now
+    assert sorted(held) == sorted(['table0', 'perm0', 'nbr_subm0', 'feat_conv1'] + [pre + name for name in GEOMS
+                                                                                    for pre in ('table_', 'coords_', 'nbr_', 'feat_conv_')])
